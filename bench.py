@@ -6,13 +6,18 @@ lidar; scan L2 vs CPU ref.  The job steps --global-envs (65536) single-agent
 envs split over the ranks (strong scaling: 65536 on one MI355X, 8192 per GPU
 at 8).  One "step" = one f110_step launch: ST dynamics (RK4) + 1080-beam EDT
 sphere-trace + TTC/GJK/ray_cast + obs pack for every env of the shard, with
-scan noise and device-side autoreset on.  At N=1 the line also carries the
-8192-env C3 shard and the 4096-env C2 workload (`secondary`), the one-stream
-runner a policy loop uses (`single_stream`), the scan check of the timed
-kernel against the CPU oracle (`scan_check`), the roofline and the CPU
-baseline.
+scan noise and device-side autoreset on.  A plain run sets up, warms up,
+times the K steps and prints the headline line (metric, value, ms_per_step,
+config).  `--full` adds everything else, each in passes of its own after the
+timed steps: the trajectory digest, the one-stream runner a policy loop uses
+(`single_stream`), the scan check of the timed kernel against the CPU oracle
+(`scan_check`), the roofline and, at N=1, the 8192-env C3 shard, the
+4096-env C2 workload, C4 and C5 (`secondary`) and the CPU baseline.
+`--dump-outputs DIR` writes what the timed runner returned from its last
+timed step (a fixed seeded sample of envs) as DIR/<name>.npy: the inputs
+depend on the arguments alone, so two builds can be compared array by array.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 `--gpus N > 1` without a launcher (no WORLD_SIZE in the environment) starts
@@ -22,7 +27,7 @@ with the same arguments and exits with its return code.  Under a launcher,
 WORLD_SIZE must equal --gpus (else exit 2).
 
 Prints ONE JSON line on rank 0.  See DESIGN.md §Measurement for the
-roofline accounting; the cpu_baseline leg (rank 0, N=1) times the C oracle
+roofline accounting; the cpu_baseline leg (--full, rank 0, N=1) times the C oracle
 (oracle/) on the host cores for a bounded sample of the same workload.
 """
 from __future__ import annotations
@@ -95,7 +100,20 @@ def parse():
                     help="step: the env step (headline); ddpg: config 5, the batched train_ddpg loop")
     ap.add_argument("--ddpg-batch", type=int, default=4096)
     ap.add_argument("--ddpg-memory", type=int, default=1 << 20)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the env-step bench measures or checks: "
+                         "trajectory digest, counting replay, one-context and per-kernel passes, roofline, scan "
+                         "check against the CPU oracle, the secondary configurations and the CPU baseline (the "
+                         "--no-* options trim that set); without it a run only sets up, warms up, times the "
+                         "--steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed runner returned from its last timed step (obs, collisions, "
+                         "terminated of a fixed seeded sample of envs) as DIR/<name>.npy, float32 / float64")
+    args = ap.parse_args()
+    if args.dump_outputs and args.workload == "ddpg":
+        ap.error("--dump-outputs covers the env-step workload only (the ddpg loop's clock ramp runs a "
+                 "wall-time-dependent number of learner updates, so its outputs differ from run to run)")
+    return args
 
 
 def free_port() -> int:
@@ -438,6 +456,58 @@ def ray_kernel_name(sm, shared=False):
     return names.get(sm.ray_kernel, str(sm.ray_kernel))
 
 
+DUMP_ENVS = 8192  # --dump-outputs: sampled envs (8192 obs rows of 1084 f32 = 36 MB)
+DUMP_MAX_BYTES = 48 << 20  # of obs rows; with the small arrays beside them the dump stays under 64 MB
+
+
+def dump_env_ids(G: int, obs_dim: int, seed: int):
+    """The envs --dump-outputs writes: every env when that fits, else a fixed
+    sample of global env ids (sorted, without replacement, drawn from the
+    run's seed alone, so two builds dump the same envs)."""
+    import numpy as np
+    n = min(G, DUMP_ENVS, max(1, DUMP_MAX_BYTES // (4 * obs_dim)))
+    if n == G:
+        return np.arange(G, dtype=np.int64)
+    return np.sort(np.random.default_rng([seed, 0x64756D70]).choice(G, size=n, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname, runner, shard, G, seed, D, rank):
+    """Write what the timed runner's last step returned to its caller (the
+    minimal outputs: obs f32, collisions, terminated) for the sampled envs as
+    DIR/<name>.npy, with their global ids in env_ids.npy.  Each rank fills the
+    rows of the envs it owns; the sum over ranks (zeros elsewhere) is the job's
+    array, written by rank 0."""
+    import numpy as np
+    import torch
+    sims = getattr(runner, "sims", [runner])
+    if hasattr(runner, "join"):
+        runner.join()
+    torch.cuda.synchronize()
+    obs_dim = int(sims[0].out.obs.shape[1])
+    ids = dump_env_ids(G, obs_dim, seed)
+    mine = (ids >= shard.offset) & (ids < shard.offset + shard.count)
+    rows = torch.from_numpy(np.nonzero(mine)[0])
+    local = torch.from_numpy(ids[mine] - shard.offset).to(sims[0].device)
+    arrays = {"obs": torch.cat([sm.out.obs for sm in sims], 0),
+              "collisions": torch.cat([sm.out.collisions for sm in sims], 0),
+              "terminated": torch.cat([sm.out.terminated for sm in sims], 0)}
+    out = {}
+    for name, t in arrays.items():
+        t = t.reshape(t.shape[0], -1)
+        buf = torch.zeros(len(ids), t.shape[1], dtype=torch.float32)
+        buf[rows] = t[local].to(torch.float32).cpu()
+        out[name] = D.sum_tensor_over_ranks(buf).numpy()
+    if rank != 0:
+        return None
+    os.makedirs(dirname, exist_ok=True)
+    out["terminated"] = out["terminated"].reshape(-1)
+    out["env_ids"] = ids.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "envs": int(len(ids)), "of": int(G),
+            "arrays": {name: list(a.shape) for name, a in out.items()}}
+
+
 def scan_check_multi(O, scanner, runner, act, threads, S=256):
     """Multi-agent scan check of the timed kernel: the agent ray_cast edits
     the traced scans, so the oracle steps a sample of S envs in lock-step
@@ -648,13 +718,53 @@ def main():
 
     runner = make(E, shard.offset, kind)
     elapsed = timed(runner, poses0, acts)
-    traj = digest(runner)
-    lookups, rays = count_replay(runner, poses0, acts)
-    mean_look = lookups / max(rays, 1)
+    # the timed runner's outputs are still those of its last timed step here
+    dumped = dump_outputs(args.dump_outputs, runner, shard, G, args.seed, D, rank) if args.dump_outputs else None
     total_env_steps = D.sum_over_ranks(E * K)
     RUNNER_TEXT = {
         "streams": "StreamShards: unjoined stream sub-shards of the three-launch step, actions resident in HBM",
         "one": "one BatchSim context, three launches per step (k_agents, ray kernel, k_post)"}
+    result = {
+        "metric": metric_name(G, A),
+        "value": total_env_steps / elapsed,
+        "unit": "env-steps/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": W,
+        "ms_per_step": elapsed / K * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak" if weak else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic: i.i.d. uniform random actions, centerline spawn poses, Spielberg map",
+        "full": bool(args.full),
+        "config": {
+            "workload": f"{G} {'single' if A == 1 else f'{A}'}-agent envs"
+                        + (f" ({E} per GPU x {world})" if world > 1 else " on one GPU"),
+            "global_envs": G, "envs_per_gpu": E, "agents": A, "beams": getattr(runner, "sims", [runner])[0].B,
+            "map": args.map,
+            "integrator": "RK4", "scan_noise": not args.no_noise, "autoreset": True,
+            "parallelism": f"env-shard x{world} (no collectives)",
+            "dist": D.describe(),
+            "streams_per_gpu": runner.S if not isinstance(runner, BatchSim) else 1,
+            "ramp": ramp,
+            "runner": RUNNER_TEXT[runner.kind] + "; minimal outputs (obs, collisions, terminated): no f32 "
+                      "info['scans'] copy, lap_times/counts, sim_time, was_reset",
+            "runner_kind": runner.kind,
+        },
+    }
+    if dumped:
+        result["dumped_outputs"] = dumped
+    if not args.full:
+        # a plain run ends here: everything below takes passes of its own (--full)
+        runner.close()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        D.shutdown()
+        return
+    traj = digest(runner)
+    lookups, rays = count_replay(runner, poses0, acts)
+    mean_look = lookups / max(rays, 1)
     sim = runner if getattr(runner, "kind", "") == policy_kind else make(E, shard.offset, policy_kind)
     prof = runner if isinstance(runner, BatchSim) else sim  # the per-kernel pass: the headline's own kernel
 
@@ -880,39 +990,14 @@ def main():
                 roof[k] = busy[k]
         roof["busy_source"] = busy["file"]
 
-    result = {
-        "metric": metric_name(G, A),
-        "value": total_env_steps / elapsed,
-        "unit": "env-steps/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": W,
-        "ms_per_step": elapsed / K * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak" if weak else "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic: i.i.d. uniform random actions, centerline spawn poses, Spielberg map",
-        "config": {
-            "workload": f"{G} {'single' if A == 1 else f'{A}'}-agent envs"
-                        + (f" ({E} per GPU x {world})" if world > 1 else " on one GPU"),
-            "global_envs": G, "envs_per_gpu": E, "agents": A, "beams": B, "map": args.map,
-            "integrator": "RK4", "scan_noise": not args.no_noise, "autoreset": True,
-            "parallelism": f"env-shard x{world} (no collectives)",
-            "dist": D.describe(),
-            "streams_per_gpu": runner.S if not isinstance(runner, BatchSim) else 1,
-            "ramp": ramp,
-            "runner": RUNNER_TEXT[runner.kind] + "; minimal outputs (obs, collisions, terminated): no f32 "
-                      "info['scans'] copy, lap_times/counts, sim_time, was_reset",
-            "runner_kind": runner.kind,
-        },
+    result.update({
         "trajectory_digest": traj,
         "single_stream": single,
         "single_stream_full_outputs": full_outputs,
         "scan_l2_vs_cpu": checks["l2"] if checks and "l2" in checks else None,
         "scan_check": checks,
         "roofline": roof,
-    }
+    })
     if rank == 0 and world == 1 and not args.no_secondary:
         sec = {}
         for label, n in (("C3_shard_8192", 8192), ("C2_4096", 4096)):

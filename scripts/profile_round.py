@@ -4,8 +4,8 @@
   python scripts/profile_round.py r01 --collect  # here: raw csvs merged back under
                                                  # gpurun_out/prof_r01 -> profiles/
 
-1. kernel trace + stats of `bench.py` (same command as the headline, fewer
-   steps, no cpu leg) -> profiles/<tag>_kernel_stats.csv (+ summary json)
+1. kernel trace + stats of `bench.py --full` (the headline and its one-context
+   passes, fewer steps, no cpu leg) -> profiles/<tag>_kernel_stats.csv (+ summary json)
    (+ k_rays averages split by grid size: sub-shard vs isolated launches)
 2. PMC passes (bench --streams 1: every k_rays launch is the isolated E-car one), one counter group per run (FETCH_SIZE, WRITE_SIZE,
    TCC_HIT/TCC_MISS): per-launch HBM-side bytes of k_rays -> profiles/pmc_traffic.json
@@ -26,7 +26,7 @@ ENVS = int(os.environ.get("PROFILE_ENVS", "65536"))  # the headline configuratio
 REFILL = os.environ.get("PROFILE_REFILL")
 SUFFIX = "" if not REFILL else ("_fx" if REFILL == "0" else f"_fxs{REFILL}")
 NO_TRACE = os.environ.get("PROFILE_NO_TRACE") == "1"
-BENCH = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "300", "--warmup", "50", "--no-cpu-baseline",
+BENCH = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "300", "--warmup", "50", "--no-cpu-baseline",
          "--no-secondary", "--no-full-outputs", "--global-envs", str(ENVS)]
 env = dict(os.environ, TMPDIR="/tmp")
 

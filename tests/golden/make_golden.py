@@ -345,9 +345,10 @@ def gen_raycast_ttc(rng):
     tscans[200:260] = np.round(rng.uniform(0.4, 0.5, (60, ang.shape[0])) * 1024.0) / 1024.0
     ttc = np.array([lm.check_ttc_jit(tscans[i], vel[i], ang, tables["beam_cosines"],
                                      tables["side_distances"], 0.005) for i in range(m)])
-    save("raycast_ttc.npz", poses=poses, opp_poses=opp, scans_in=scans_in, scans_out=np.asarray(out),
-         ex_angles=ex_ang, ex_vertices=ex_v, ex_out=ex_out,
-         ttc_vel=vel, ttc_scans=tscans, ttc_out=ttc.astype(np.uint8))
+    # two files: together they would exceed the 1 MiB limit for a committed file
+    save("raycast.npz", poses=poses, opp_poses=opp, scans_in=scans_in, scans_out=np.asarray(out),
+         ex_angles=ex_ang, ex_vertices=ex_v, ex_out=ex_out)
+    save("ttc.npz", ttc_vel=vel, ttc_scans=tscans, ttc_out=ttc.astype(np.uint8))
 
 
 # ------------------------------------------------------------- simulator ----

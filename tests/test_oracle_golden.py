@@ -106,7 +106,7 @@ def test_collision(oracle_mod):
 
 
 def test_raycast_ttc(oracle_mod):
-    r = golden("raycast_ttc.npz")
+    r = {**golden("raycast.npz"), **golden("ttc.npz")}  # one generator (gen_raycast_ttc), two files
     t = golden("tables.npz")
     out = np.stack([oracle_mod.ray_cast(p, s, t["scan_angles"], oracle_mod.get_vertices(o, 0.58, 0.31))
                     for p, s, o in zip(r["poses"], r["scans_in"], r["opp_poses"])])
