@@ -57,6 +57,22 @@ class F110WgradOp(ctypes.Structure):  # f110_wgrad_op
                [(n, ctypes.c_int32) for n in ("N", "KX", "ldg", "ldx", "ldw")]
 
 
+class F110RayKnobs(ctypes.Structure):  # f110_ray_knobs (include/f110_debug.h)
+    _fields_ = [(n, ctypes.c_int32) for n in
+                ("kernel", "lanes", "refill", "fxs_lds", "count_slots", "wtrace", "heavy_list", "heavy_on",
+                 "heavy_use", "heavy_cap", "has_rm", "has_rmp", "fxs_ok", "rotated", "E", "A", "B", "theta_dis",
+                 "ray_wpb", "has_geo")]
+
+
+class F110RayPlan(ctypes.Structure):  # f110_ray_plan
+    _fields_ = [(n, ctypes.c_int32) for n in ("family", "rot", "mask", "handoff", "lds", "count", "trace")] + \
+               [("grid", ctypes.c_uint32), ("block", ctypes.c_uint32)] + \
+               [(n, ctypes.c_int32) for n in ("wpb", "nch", "G4", "HB", "geo_blocks", "table", "wcost", "geo_ready")]
+
+
+RAY_FAMILIES = ("tiled_flat", "tiled_chunked", "fx", "fxn_clamped", "fxn_padded", "fxs")  # F110_RAY_*
+RAY_TABLES = ("tiled", "rowmajor", "padded")  # F110_TABLE_*
+
 REWARD_STATE_BYTES = 8 * 12 + 4 * 4   # f110_reward_state
 
 ABI_VERSION = 3  # include/f110.h F110_ABI_VERSION
@@ -75,6 +91,7 @@ EXPORTS = [
     "f110_default_reward_params", "f110_reward", "f110_replay_create", "f110_replay_destroy", "f110_replay_add", "f110_replay_add_env",
     "f110_replay_sample", "f110_replay_update_priorities", "f110_replay_length", "f110_replay_arrays",
     "f110_debug_wave_trace", "f110_debug_set_ray_gate", "f110_debug_disable_heavy_first", "f110_debug_ray_kernel", "f110_debug_ray_lanes", "f110_debug_ray_refill", "f110_debug_set_ray_refill", "f110_debug_read_counter", "f110_step_n", "f110_debug_set_ray_lanes", "f110_set_reset_dtype", "f110_set_device_share", "f110_host_np_sincosf", "f110_host_sincos", "f110_host_sincos_series", "f110_host_map_table", "f110_get_lap_state",
+    "f110_host_ray_plan", "f110_host_ray_rules",
     "f110_dynamics_ks_batch", "f110_collision_batch", "f110_collision_multiple", "f110_adam_step", "f110_ddpg_scratch_floats", "f110_ddpg_actor_head", "f110_ddpg_actor_explore",
     "f110_ddpg_actor_head_bwd", "f110_ddpg_td_target", "f110_ddpg_critic_loss", "f110_ddpg_critic_loss_bwd",
     "f110_ddpg_q_mean", "f110_ddpg_q_mean_bwd", "f110_ddpg_relu_bwd_scratch_floats", "f110_ddpg_relu_bwd",
@@ -207,6 +224,8 @@ def load(build_if_missing: bool = True):
     L.f110_host_sincos_series.restype = None
     L.f110_host_map_table.argtypes = [_P, i32, i32, ctypes.c_double, i32, i32, _P, i64, _P]
     L.f110_host_map_table.restype = ctypes.c_int64
+    L.f110_host_ray_plan.argtypes = [ctypes.POINTER(F110RayKnobs), i32, ctypes.POINTER(F110RayPlan)]
+    L.f110_host_ray_rules.argtypes = [i64, i64, i32, i32, i32, ctypes.POINTER(i32)]
     L.f110_adam_step.argtypes = [_P, _P, _P, _P, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                  ctypes.c_double, _P, _P, ctypes.c_double, _P]
     f32 = ctypes.c_float

@@ -92,14 +92,9 @@ struct f110_ctx {
     int ray_wpb = 1;  // one-wave blocks (4-car blocks measured slower)
     int64_t wtrace_n = 0;
     bool wtrace_armed = false;
-    // the fixed-point ray kernel's row-major EDT (see StepArgs::rm)
-    double *rm = nullptr;
-    int32_t rm_w = 0;
-    uint32_t rm_oob = 0, rm_zero = 0;
-    const double *rmp = nullptr;  // the padded table of k_rays_fxn / k_rays_fxs (shared, see MapTables)
-    int32_t rmp_w = 0, rmp_P = 0, rmp_h = 0;
-    uint32_t rmp_zero = 0;
-    bool fx_pad = false;    // the padded table is wanted (from 32768 cars or with refill; F110_FX_PAD=0: never)
+    FxTable rm{}, rmp{};  // the fixed-point kernels' clamped and padded EDT (shared, see MapTables)
+    int32_t rmp_h = 0;    // rows of the padded table
+    bool fx_pad = false;    // the padded table may be built (the fixed-point kernels, unless F110_FX_PAD=0 at create)
     int32_t fx_refill = 0;   // waves per car of k_rays_fxs (0 = k_rays_fxn; f110_debug_set_ray_refill)
     bool fxs_lds = false;    // single-agent k_rays_fxs with the LDS theta table (f110_set_device_share, > 1 context)
     bool count_slots = false;  // f110_debug_set_simt: lane-slot counter of the fixed-point loops (f110_debug_read_simt)
@@ -595,17 +590,15 @@ static int ensure_padded_table(f110_ctx *ctx);
 
 // the map entry's padded table (if it was built) for the context
 static void adopt_padded_table(f110_ctx *c) {
-    if (!c->maps || !c->maps->rmp) return;
-    c->rmp = c->maps->rmp;
-    c->rmp_w = c->maps->rmp_w;
-    c->rmp_h = c->maps->rmp_h;
-    c->rmp_P = c->maps->rmp_P;
-    c->rmp_zero = c->maps->rmp_zero;
+    const MapTables *m = c->maps;
+    if (!m || !m->rmp) return;
+    c->rmp = FxTable{m->rmp, m->rmp_w, m->rmp_P, 0, m->rmp_zero};
+    c->rmp_h = m->rmp_h;
 }
 
 // k_rays_fxs's offsets (kFxsBase) need q + P below 2^20 for every lookup: the padded
 // table's rows and columns below 2^20 (else the refill runs k_rays_fxn instead)
-static bool fxs_ok(const f110_ctx *c) { return c->rmp && c->rmp_w < (1 << 20) && c->rmp_h < (1 << 20); }
+static bool fxs_ok(const f110_ctx *c) { return c->rmp.dt && c->rmp.w < (1 << 20) && c->rmp_h < (1 << 20); }
 
 // k_rays_fxs's waves per car for `cars` traced at once on the device (one context's cars, or the
 // device's under f110_set_device_share).  Round 5 (profiles/r05_ab/shard_rules_*.jsonl, env-steps/s,
@@ -616,6 +609,52 @@ static bool fxs_ok(const f110_ctx *c) { return c->rmp && c->rmp_w < (1 << 20) &&
 // waves shortens the longest car's chain, the launch's tail where the grid is one round deep; where
 // it is many rounds deep the extra waves re-fetch the car's neighbourhood on other CUs.
 static int32_t refill_waves(int64_t cars) { return cars >= 32768 ? 1 : cars >= 16384 ? 2 : 3; }
+
+// The size rules, the one place that has them: the knobs of a context of `own` cars on a
+// device that traces device_cars at once in `contexts` contexts.  f110_create applies them with
+// device_cars = own and one context, f110_set_device_share with the caller's figures.
+struct RayRules {
+    int32_t lanes, refill, heavy_first, fxs_lds;
+};
+static RayRules ray_rules(int64_t own, int64_t device_cars, int32_t contexts, int32_t kernel, bool pad_allowed) {
+    RayRules r{1, 0, 0, 0};
+    if (kernel != 3) {
+        // one ray per lane, no refill.  Heavy-first (the tiled kernels) pays where one ray grid is a few
+        // rounds of waves deep (16384 cars: 0.281 vs 0.287 ms), costs where it is deep (65536: 1.288 vs
+        // 1.251 ms) or one round or less (8192 cars 0.172 vs 0.167, 4096 cars 0.124 vs 0.109 ms;
+        // profiles/r02_ray_ab/ab_heavy.json, profiles/r03_ab/small_shards.json), and beside other
+        // contexts, which fill this one's tail
+        r.heavy_first = contexts == 1 && own > 8192 && own < 32768;
+        return r;
+    }
+    // k_rays_fxs (one or a few waves per car, two chunk slots with refill, padded EDT) at every size
+    // since round 5, when closed slots stopped gathering (DESIGN §3.11); it takes no heavy-first list
+    // and needs 2 rays per lane.  Without the padded table (F110_FX_PAD=0) the old size rule: 2 rays
+    // per lane from 12288 cars
+    r.lanes = pad_allowed || device_cars >= 12288 ? 2 : 1;
+    r.refill = pad_allowed ? refill_waves(device_cars) : 0;
+    // the LDS theta table's 8-wave blocks leave idle slots that other contexts fill: it pays beside
+    // them (65536 cars in 2 sub-shards 89.5 -> 95.9 M) but not alone (one context 88.3 -> 87.2 M,
+    // DESIGN §3.14)
+    r.fxs_lds = contexts > 1;
+    return r;
+}
+
+extern "C" int f110_host_ray_rules(int64_t own_cars, int64_t device_cars, int32_t contexts, int32_t kernel,
+                                   int32_t pad_allowed, int32_t out[4]) {
+    if (!out || contexts < 1 || own_cars < 1 || device_cars < own_cars || kernel < 1 || kernel > 3)
+        return fail(F110_E_INVALID, "f110_host_ray_rules: bad arguments");
+    const RayRules r = ray_rules(own_cars, device_cars, contexts, kernel, pad_allowed != 0);
+    std::memcpy(out, &r, sizeof r);  // {lanes, refill, heavy_first, fxs_lds}
+    return F110_OK;
+}
+
+extern "C" int f110_host_ray_plan(const f110_ray_knobs *in, int32_t masked, f110_ray_plan *out) {
+    if (!in || !out || in->E < 1 || in->A < 1 || in->B < 2 || in->ray_wpb < 1)
+        return fail(F110_E_INVALID, "f110_host_ray_plan: bad arguments");
+    *out = plan_ray_launch(*in, masked != 0);
+    return F110_OK;
+}
 
 extern "C" int f110_create(f110_ctx **out, int32_t device, const f110_config *cfg, const f110_params *params,
                            const uint32_t *edt_k, int32_t H, int32_t W, double resolution, const double origin[3],
@@ -657,11 +696,15 @@ extern "C" int f110_create(f110_ctx **out, int32_t device, const f110_config *cf
     c->inc = (double)C.theta_dis * (C.fov / (double)(C.n_beams - 1)) / (2. * kPi);  // laser_models.py:367-368
     c->beam_incr = C.fov / (double)(C.n_beams - 1);
     c->n_spawn = n_spawn;
-    // F110_RAY_KERNEL (A/B): 1 k_rays_tiled in flat ray order, 2 chunked, 3 the fixed-point kernels
+    // The two environment overrides (A/B), read here and nowhere else.  F110_RAY_KERNEL: 1 k_rays_tiled
+    // in flat ray order, 2 chunked, 3 the fixed-point kernels; F110_FX_PAD=0 never builds the padded
+    // table (the context then steps with k_rays_fxn on the clamped table, or k_rays_fx).
     if (const char *v = std::getenv("F110_RAY_KERNEL")) {
         const int k = std::atoi(v);
         c->ray_kernel = k >= 2 && k <= 3 ? k : 1;
     }
+    bool pad_allowed = true;
+    if (const char *v = std::getenv("F110_FX_PAD")) pad_allowed = std::atoi(v) != 0;
     {
         // chunked dispatch order: descending beam chunks (the scan's left edge
         // to its right edge).  Measured against the flat order and five other
@@ -672,7 +715,19 @@ extern "C" int f110_create(f110_ctx **out, int32_t device, const f110_config *cf
         c->nch = nch;
         for (int i = 0; i < nch && i < kMaxChunks; ++i) c->chunk_order[i] = (uint8_t)(nch - 1 - i);
     }
+    // the fixed-point kernels' preconditions, and their row-major table's byte offsets (one padding
+    // column / row, a zero cell) stay 32-bit: else the chunked tiled kernel
+    if (c->ray_kernel == 3 && (!fx_eligible(H, W, resolution, origin, C.eps, edt_k, c->ray_wpb) ||
+                               ((uint64_t)W + 16) / 16 * 16 * ((uint64_t)H + 1) * 8 + 128 >= (1ull << 32)))
+        c->ray_kernel = 2;
     const size_t EA = (size_t)C.n_envs * C.n_agents;
+    const bool fx_ok = c->ray_kernel == 3;
+    c->fx_pad = fx_ok && pad_allowed;
+    const RayRules rules = ray_rules((int64_t)EA, (int64_t)EA, 1, c->ray_kernel, c->fx_pad);
+    c->fx_ilp = fx_ok ? 2 : 1;  // not rules.lanes: alone, 2 also without the padded table (the 12288-car rule
+                                // is f110_set_device_share's)
+    c->fx_refill = rules.refill;
+    if (!rules.heavy_first) c->heavy_T = 0;
 
     auto cleanup = [&](int code, const std::string &msg) {
         for (void *q : c->allocs) (void)hipFree(q);
@@ -726,25 +781,6 @@ extern "C" int f110_create(f110_ctx **out, int32_t device, const f110_config *cf
     ALLOC(c->ctr, (size_t)kCtrSlots * kCtrStride);
     ALLOC(c->pa, (size_t)C.n_agents);
     if (spawn_poses && n_spawn > 0) ALLOC(c->spawn, (size_t)n_spawn * C.n_agents * 3);
-    if (c->ray_kernel == 3 && !fx_eligible(H, W, resolution, origin, C.eps, edt_k, c->ray_wpb)) c->ray_kernel = 2;
-    if (c->ray_kernel == 3) {
-        // the row-major table's byte offsets (one padding column / row, a zero cell) stay 32-bit
-        const uint64_t rm_bytes = ((uint64_t)W + 16) / 16 * 16 * ((uint64_t)H + 1) * 8 + 128;
-        if (rm_bytes >= (1ull << 32)) c->ray_kernel = 2;
-    }
-    // k_rays_fxs (one or a few waves per car, two chunk slots with refill, padded EDT) at every size
-    // since round 5, when closed slots stopped gathering (DESIGN §3.11); it takes no heavy-first list
-    // and needs 2 rays per lane (k_rays_fxn<2> runs the masked resets)
-    if (c->ray_kernel == 3) {
-        c->fx_ilp = 2;
-        c->heavy_T = 0;
-    } else if (EA >= 32768 || EA <= 8192) {
-        // heavy-first (the tiled kernels) pays where one ray grid is a few rounds of waves deep (16384
-        // cars: 0.281 vs 0.287 ms), costs where it is deep (65536: 1.288 vs 1.251 ms) or one round or
-        // less (8192 cars 0.172 vs 0.167, 4096 cars 0.124 vs 0.109 ms; profiles/r02_ray_ab/ab_heavy.json,
-        // profiles/r03_ab/small_shards.json)
-        c->heavy_T = 0;
-    }
     if (c->ray_kernel >= 2 && c->heavy_T > 0) {
         // up to 1/6 of the waves (measured: ~7% of the waves have a ray longer
         // than 40 lookups and carry ~46% of the wave-iterations)
@@ -787,12 +823,7 @@ extern "C" int f110_create(f110_ctx **out, int32_t device, const f110_config *cf
         e = hipMemcpy(c->spawn, spawn_poses, (size_t)n_spawn * C.n_agents * 3 * sizeof(double),
                       hipMemcpyHostToDevice);
     // PAD: the clamp-free loop on a table padded by the max range (+ 8 cells of margin), which
-    // k_rays_fxs needs (its offsets, kFxsBase); F110_FX_PAD=0 (A/B) never builds it: the context then
-    // steps with k_rays_fxn / k_rays_fx.
-    const bool fx_ok = c->ray_kernel == 3;
-    c->fx_pad = fx_ok;
-    if (const char *v = std::getenv("F110_FX_PAD")) c->fx_pad = fx_ok && std::atoi(v) != 0;
-    c->fx_refill = fx_ok && c->fx_pad ? refill_waves(EA) : 0;
+    // k_rays_fxs needs (its offsets, kFxsBase)
     const double pad_q = std::ceil(C.max_range / resolution) + 8.0;
     const int32_t fx_pad_cells = pad_q > 0.0 && pad_q < 65536.0 ? (int32_t)pad_q : 0;  // else no padded table
     if (e == hipSuccess)
@@ -802,10 +833,7 @@ extern "C" int f110_create(f110_ctx **out, int32_t device, const f110_config *cf
         c->dt = c->maps->dt;
         c->dt_tiled = c->maps->dt_tiled;
         if (fx_ok) {
-            c->rm = c->maps->rm;
-            c->rm_w = c->maps->rm_w;
-            c->rm_oob = c->maps->rm_oob;
-            c->rm_zero = c->maps->rm_zero;
+            c->rm = FxTable{c->maps->rm, c->maps->rm_w, 0, c->maps->rm_oob, c->maps->rm_zero};
             if (c->fx_pad) adopt_padded_table(c);
         }
     }
@@ -827,13 +855,37 @@ extern "C" int f110_destroy(f110_ctx *ctx) {
 
 static TiledMapView tiled_view(const f110_ctx *c) { return make_tiled_view(map_view(c), c->dt_tiled); }
 
+// The context state plan_ray_launch reads, for a step (heavy-first runs its list) or a reset.
+static RayKnobs ray_knobs(const f110_ctx *c, bool step) {
+    const TiledMapView t = tiled_view(c);
+    RayKnobs k{};
+    k.kernel = c->ray_kernel;
+    k.lanes = c->fx_ilp;
+    k.refill = c->fx_refill;
+    k.fxs_lds = c->fxs_lds;
+    k.count_slots = c->count_slots;
+    k.wtrace = c->wtrace_armed;
+    k.heavy_list = c->wcost != nullptr;
+    k.heavy_on = !c->heavy_off;
+    k.heavy_use = step && c->wcost && c->ray_kernel >= 2 && !c->heavy_off;
+    k.heavy_cap = c->heavy_cap;
+    k.has_rm = c->rm.dt != nullptr;
+    k.has_rmp = c->rmp.dt != nullptr;
+    k.fxs_ok = fxs_ok(c);
+    k.rotated = !(t.os == 0.0 && t.oc == 1.0);
+    k.E = c->cfg.n_envs;
+    k.A = c->cfg.n_agents;
+    k.B = c->cfg.n_beams;
+    k.theta_dis = c->cfg.theta_dis;
+    k.ray_wpb = c->ray_wpb;
+    k.has_geo = c->geo != nullptr;
+    return k;
+}
+
 static StepArgs make_step_args(f110_ctx *c, const f110_outputs *out) {
     StepArgs a{};
     a.map = map_view(c);
     a.tmap = tiled_view(c);
-    a.ray_kernel = c->ray_kernel;
-    a.ray_wpb = c->ray_wpb;
-    for (int i = 0; i < kMaxChunks; ++i) a.chunk_order[i] = c->chunk_order[i];
     a.sines = c->sines;
     a.cosines = c->cosines;
     a.angles = c->angles;
@@ -899,30 +951,25 @@ static StepArgs make_step_args(f110_ctx *c, const f110_outputs *out) {
         a.heavy_count = c->heavy_count;
         a.heavy_cap = c->heavy_cap;
         a.heavy_T = c->heavy_T;
-        a.heavy_on = c->heavy_off ? 0 : 1;
     }
     a.reset_f32 = c->reset_f32 ? 1 : 0;
-    a.rm = c->rm;
-    a.rm_w = c->rm_w;
-    a.rm_oob = c->rm_oob;
-    a.rm_zero = c->rm_zero;
-    a.rmp = c->rmp;
-    a.rmp_w = c->rmp_w;
-    a.rmp_P = c->rmp_P;
-    a.rmp_zero = c->rmp_zero;
-    a.fx_pad = c->rmp ? 1 : 0;
-    a.fxs_ok = fxs_ok(c) ? 1 : 0;
-    a.count_slots = c->count_slots ? 1 : 0;
-    a.fx_refill = c->fx_refill;
-    a.fxs_lds = c->fxs_lds ? 1 : 0;
-    a.fx_ilp = c->fx_ilp;
-    a.gate_wait = c->gate_wait;
-    a.gate_record = c->gate_record;
+    return a;
+}
+
+// What the launch reads beside StepArgs; a step's or a reset's (ray_knobs)
+static RayLaunch ray_launch(f110_ctx *c, bool step) {
+    RayLaunch r{};
+    r.k = ray_knobs(c, step);
+    r.rm = c->rm;
+    r.rmp = c->rmp;
+    for (int i = 0; i < kMaxChunks; ++i) r.chunk_order[i] = c->chunk_order[i];
+    r.gate_wait = c->gate_wait;
+    r.gate_record = c->gate_record;
     if (c->wtrace_armed) {  // one traced ray launch
-        a.wtrace = c->wtrace;
+        r.wtrace = c->wtrace;
         c->wtrace_armed = false;
     }
-    return a;
+    return r;
 }
 
 extern "C" int f110_reset(f110_ctx *ctx, const double *poses, const uint8_t *env_mask, const f110_outputs *out,
@@ -931,11 +978,12 @@ extern "C" int f110_reset(f110_ctx *ctx, const double *poses, const uint8_t *env
     if (use_device(ctx) != F110_OK) return F110_E_HIP;
     if (out && out->obs_stride && out->obs_stride < (int64_t)ctx->cfg.n_beams + 4 * ctx->cfg.n_agents)
         return fail(F110_E_INVALID, "f110_reset: obs_stride < n_beams + 4*n_agents");
+    const RayLaunch r = ray_launch(ctx, /*step=*/false);
     StepArgs a = make_step_args(ctx, out);
     a.mode = 1;
     a.reset_poses = poses;
     a.reset_mask = env_mask;
-    HIP_TRY(launch_env_step(a, (hipStream_t)stream, ctx->next_prof_events()));
+    HIP_TRY(launch_env_step(a, r, (hipStream_t)stream, ctx->next_prof_events()));
     return F110_OK;
 }
 
@@ -948,9 +996,10 @@ static int step_n(f110_ctx *ctx, const void *actions, int32_t actions_dtype, int
     if (use_device(ctx) != F110_OK) return F110_E_HIP;
     if (out && out->obs_stride && out->obs_stride < (int64_t)ctx->cfg.n_beams + 4 * ctx->cfg.n_agents)
         return fail(F110_E_INVALID, std::string(who) + ": obs_stride < n_beams + 4*n_agents");
+    const RayLaunch r = ray_launch(ctx, /*step=*/true);
     StepArgs a = make_step_args(ctx, out);
     a.mode = 0;
-    a.heavy_build = a.heavy_use = (a.wcost && a.ray_kernel >= 2 && !ctx->heavy_off) ? 1 : 0;  // not on resets
+    a.heavy_build = r.k.heavy_use;  // k_agents builds the list this step's ray launch runs
     const int64_t packed = (int64_t)ctx->cfg.n_envs * ctx->cfg.n_agents * 2;  // action elements per step
     if (step_stride != 0 && step_stride < packed)
         return fail(F110_E_INVALID, std::string(who) + ": step_stride < n_envs * n_agents * 2");
@@ -961,7 +1010,7 @@ static int step_n(f110_ctx *ctx, const void *actions, int32_t actions_dtype, int
         else
             a.actions = static_cast<const float *>(actions) + (size_t)t * stride;
         if (t) a.parity = (int32_t)(ctx->launch_n++ & 1);
-        HIP_TRY(launch_env_step(a, (hipStream_t)stream, ctx->next_prof_events()));
+        HIP_TRY(launch_env_step(a, r, (hipStream_t)stream, ctx->next_prof_events()));
     }
     return F110_OK;
 }
@@ -1011,28 +1060,27 @@ extern "C" void f110_host_np_sincosf(const float *x, int64_t n, int32_t cos_op, 
 
 extern "C" int f110_debug_ray_kernel(const f110_ctx *ctx) {
     if (!ctx) return fail(F110_E_INVALID, "f110_debug_ray_kernel: null context");
-    return ctx->ray_kernel;
+    const int f = plan_ray_launch(ray_knobs(ctx, true), /*masked=*/false).family;
+    return f == F110_RAY_TILED_FLAT ? 1 : f == F110_RAY_TILED_CHUNKED ? 2 : 3;
 }
 
 extern "C" int f110_debug_ray_lanes(const f110_ctx *ctx) {
     if (!ctx) return fail(F110_E_INVALID, "f110_debug_ray_lanes: null context");
-    return ctx->ray_kernel == 3 ? ctx->fx_ilp : 1;
+    const int f = plan_ray_launch(ray_knobs(ctx, true), /*masked=*/false).family;
+    return f >= F110_RAY_FXN_CLAMPED ? 2 : 1;
 }
 
-// k_rays_fxs's waves per car for unmasked steps, as launch_env_step decides it
+// k_rays_fxs's waves per car for unmasked steps
 extern "C" int f110_debug_ray_refill(const f110_ctx *ctx) {
     if (!ctx) return fail(F110_E_INVALID, "f110_debug_ray_refill: null context");
-    const bool fx = ctx->ray_kernel == 3 && ctx->fx_ilp == 2 && fxs_ok(ctx);
-    const int waves = std::min<int>(ctx->fx_refill, (ctx->cfg.n_beams + 63) / 64);  // as the launch clamps it
-    return fx && waves > 0 && (ctx->heavy_off || !ctx->wcost) ? waves : 0;
+    const RayPlan p = plan_ray_launch(ray_knobs(ctx, true), /*masked=*/false);
+    return p.family == F110_RAY_FXS ? p.G4 : 0;
 }
 
 // The padded EDT of k_rays_fxn / k_rays_fxs (built on first use, shared with
-// the map entry): F110_FX_PAD=0 keeps the clamped table (A/B runs).
+// the map entry): F110_FX_PAD=0 at f110_create keeps the clamped table (A/B runs).
 static int ensure_padded_table(f110_ctx *ctx) {
-    bool pad = true;
-    if (const char *v = std::getenv("F110_FX_PAD")) pad = std::atoi(v) != 0;
-    if (!pad || ctx->rmp || !ctx->maps) return F110_OK;
+    if (!ctx->fx_pad || ctx->rmp.dt || !ctx->maps) return F110_OK;
     const double pad_q = std::ceil(ctx->cfg.max_range / ctx->res) + 8.0;
     if (pad_q > 0.0 && pad_q < 65536.0) {
         std::lock_guard<std::mutex> g(g_maps_mu);
@@ -1043,14 +1091,12 @@ static int ensure_padded_table(f110_ctx *ctx) {
             HIP_TRY(build_padded_table(t, (int32_t)pad_q, host_dt(t->k.data(), t->k.size(), res)));
         }
     }
-    if (ctx->maps->rmp) {
-        ctx->fx_pad = true;
-        adopt_padded_table(ctx);
-    }
+    adopt_padded_table(ctx);
     return F110_OK;
 }
 
-// waves > 0 also turns heavy-first off: k_rays_fxs takes no heavy-first list
+// The one coupling between the knobs: waves > 0 also turns heavy-first off (k_rays_fxs takes no
+// heavy-first list) and builds the padded table it reads.  Every other setter writes its own knob only.
 extern "C" int f110_debug_set_ray_refill(f110_ctx *ctx, int32_t waves) {
     if (!ctx) return fail(F110_E_INVALID, "f110_debug_set_ray_refill: null context");
     if (waves < 0 || waves > 16) return fail(F110_E_INVALID, "f110_debug_set_ray_refill: waves must be in 0..16");
@@ -1082,33 +1128,20 @@ extern "C" int f110_debug_set_ray_lanes(f110_ctx *ctx, int32_t n) {
     return F110_OK;
 }
 
-// The product-side form of the three knobs above for a caller that splits one GPU's cars over
-// several concurrent contexts (streams.StreamShards): f110_create's size rules applied to the cars
-// the device traces at once.
+// For a caller that splits one GPU's cars over several concurrent contexts (streams.StreamShards):
+// f110_create's size rules (ray_rules) applied to the cars the device traces at once.
 extern "C" int f110_set_device_share(f110_ctx *ctx, int64_t device_cars, int32_t contexts) {
     if (!ctx) return fail(F110_E_INVALID, "f110_set_device_share: null context");
     const int64_t own = (int64_t)ctx->cfg.n_envs * ctx->cfg.n_agents;
     if (contexts < 1 || device_cars < own)
         return fail(F110_E_INVALID, "f110_set_device_share: contexts >= 1 and device_cars >= this context's cars");
     if (ctx->launch_n != 0) return fail(F110_E_INVALID, "f110_set_device_share: call before the first reset/step");
-    if (ctx->ray_kernel != 3) {  // one ray per lane, no refill: only the heavy-first rule applies
-        if (contexts > 1) ctx->heavy_off = true;
-        return F110_OK;
-    }
-    // k_rays_fxs at every size, its waves per car by the device's cars (refill_waves); without the
-    // padded table (F110_FX_PAD=0) the old size rule: 2 rays per lane from 12288 cars
-    const int lanes = (ctx->fx_pad || device_cars >= 12288) ? 2 : 1;
-    const int refill = (lanes == 2 && ctx->fx_pad) ? refill_waves(device_cars) : 0;
-    int rc = f110_debug_set_ray_lanes(ctx, lanes);
-    if (rc == F110_OK) rc = f110_debug_set_ray_refill(ctx, refill);
-    if (rc == F110_OK && contexts > 1) {
-        ctx->heavy_off = true;  // the other contexts fill this one's tail
-        // and its 8-wave blocks' idle slots: the LDS theta table pays off beside other contexts
-        // (65536 cars in 2 sub-shards 89.5 -> 95.9 M) but not alone (one context 88.3 -> 87.2 M,
-        // DESIGN §3.14)
-        ctx->fxs_lds = true;
-    }
-    return rc;
+    const RayRules r = ray_rules(own, device_cars, contexts, ctx->ray_kernel, ctx->fx_pad);
+    if (!r.heavy_first) ctx->heavy_off = true;
+    if (ctx->ray_kernel != 3) return F110_OK;
+    ctx->fx_ilp = r.lanes;
+    ctx->fxs_lds = r.fxs_lds;
+    return f110_debug_set_ray_refill(ctx, r.refill);  // with the padded table, see there
 }
 
 extern "C" int f110_debug_set_ray_gate(f110_ctx *ctx, void *wait_event, void *record_event) {

@@ -18,7 +18,8 @@ constexpr int kRayBlock = 256; // threads per block of the ray kernels
 constexpr int kMaxMultiBodies = 64;  // f110_collision_multiple: bodies per set
 constexpr int kMaxChunks = 32;  // 64-beam chunks per scan (n_beams <= 2048) for the chunked ray dispatch
 
-// Everything one env step (k_agents, a ray kernel, a post kernel) needs, passed by value.
+// What the kernels of one env step (k_agents, the post kernels) read, passed by value; what only the
+// host reads to launch them travels beside it (RayLaunch below).
 struct PairGeom;  // below
 
 struct StepArgs {
@@ -31,45 +32,19 @@ struct StepArgs {
     const f110_params *pa;                    // [A] RaceCar params (update_pose, ray_cast boxes)
     int32_t E, A, B, theta_dis, integrator, ego, autoreset, mode;  // mode 0 step, 1 reset
     int32_t reset_f32;        // resets follow F110Env.reset(options=float32 poses) (f110_set_reset_dtype)
-    int32_t ray_wpb;          // chunked ray kernel: waves (cars) per block (1)
-    int32_t ray_kernel;       // 1: k_rays_tiled, flat ray order; 2: chunked; 3: the fixed-point kernels
-                              // (k_rays_fx / k_rays_fxn / k_rays_fxs: fixed-point cell index, scalar per-car set-up)
-    uint8_t chunk_order[kMaxChunks];  // beam-chunk dispatch order of the chunked ray kernel
-    uint64_t *wtrace;         // diagnostic wave trace of the next ray launch (f110_debug_wave_trace) or null
-    hipEvent_t gate_wait;     // f110_debug_set_ray_gate: waited on before the ray launch, or null
-    hipEvent_t gate_record;   // f110_debug_set_ray_gate: recorded after the ray launch, or null
     // heavy-first ray dispatch (chunked kernel): per (car, chunk) wave cost of
     // the previous ray launch, this step's list of predicted-heavy waves
     uint8_t *wcost;           // [EA][nch] min(255, longest ray of the wave) or null
     uint32_t *heavy_list;     // [2][heavy_cap] (car << 8 | chunk), by step parity
     uint32_t *heavy_mask;     // [EA] chunks of the car that are in the heavy list
     uint32_t *heavy_count;    // [2] list lengths, by step parity
-    int32_t heavy_cap, heavy_T, heavy_build, heavy_use, parity, ray_nch;
-    int32_t heavy_on;         // heavy-first enabled for this context (wcost is written for the next step)
-    // k_rays_fx / k_rays_fxn's row-major EDT: rows of rm_w cells (128-B
-    // aligned), columns W..rm_w-1 and row H hold dt[-1,-1], a 0.0 at byte
-    // rm_zero past the end; rm_oob = byte offset of dt[H-1][W-1]
-    const double *rm;
-    int32_t rm_w;
-    uint32_t rm_oob, rm_zero;
-    // k_rays_fxn's padded row-major EDT (PAD): rows of rmp_w cells, rmp_P
-    // cells of dt[-1,-1] on every side (cell (r, c) at row r + P, column
-    // c + P), a 0.0 at byte rmp_zero past the end; null = not built
-    const double *rmp;
-    int32_t rmp_w, rmp_P;
-    uint32_t rmp_zero;
-    int32_t fx_pad;     // the padded table is built (k_rays_fxn on it unless F110_FX_PAD=0; k_rays_fxs)
-    int32_t fxs_ok;     // the padded table's rows and columns are below 2^20 (kFxsBase's offsets)
-    int32_t fx_refill;  // waves per car of k_rays_fxs (two chunk slots with refill; 0 = off)
-    int32_t fxs_lds;    // single-agent k_rays_fxs in 8-wave blocks with the theta table in LDS (shared device)
+    int32_t heavy_cap, heavy_T, heavy_build, parity, ray_nch;
     uint32_t *hmask;    // [E*A] k_agents' hand-off chunk masks (A >= 2 dividing 64), or null
     PairGeom *geo;      // [E][A][A-1] pair geometry (A >= 2), see RayArgs::geo
     int32_t geo_ready;  // set by launch_env_step: this step's ray kernel computed geo
-    int32_t count_slots;  // f110_debug_set_simt: lane-slot counter of the fixed-point loops
     int32_t hcheck;       // f110_debug_set_handoff_check bit 0: the hand-off buffer is NaN-poisoned before the
                           // ray launch and k_post_multi counts its reads outside hmask (ctr[.][6]); bit 2:
                           // k_agents stores empty masks (a forced miss, the check's own test)
-    int32_t fx_ilp;     // rays per lane of the fixed-point ray kernel (1: k_rays_fx, 2: k_rays_fxn / k_rays_fxs)
     double fov, eps, max_range, dt, lidar_dist, ttc_thresh, noise_std, inc, beam_incr;
     double side_max;  // max of the RaceCar side table (the TTC pre-test of k_rays_fxs)
     uint64_t seed;
@@ -230,6 +205,34 @@ constexpr uint32_t kFxsBand = 64u;  // 2^-26 in units of 2^-32
 constexpr int kFxsWaves = 8;         // k_rays_fxs: work items (one wave each) per block, sharing one LDS theta table
 constexpr int kFxsLdsTheta = 2048;   // theta table entries the block's LDS copy holds (32 KB; theta_dis 2000)
 
+// The ray launch of one f110_step / f110_reset, decided in one place: RayKnobs is the context state
+// the decision reads (plain values, include/f110_debug.h), RayPlan the kernel family, its template
+// flags, the launch shape and the EDT table.  plan_ray_launch is pure host code: no HIP call, no
+// context, no environment (tests/test_host_lib.py checks it on the CPU through f110_host_ray_plan).
+using RayKnobs = f110_ray_knobs;
+using RayPlan = f110_ray_plan;
+RayPlan plan_ray_launch(const RayKnobs &k, bool masked);
+
+// A row-major EDT of the fixed-point kernels: rows of w cells, a 0.0 at byte `zero` past the end.
+// The clamped one (k_rays_fx / k_rays_fxn): 128-B aligned rows, columns W..w-1 and row H hold
+// dt[-1,-1], oob = byte offset of dt[H-1][W-1], P = 0.  The padded one (k_rays_fxn<PAD> /
+// k_rays_fxs): P cells of dt[-1,-1] on every side (cell (r, c) at row r + P, column c + P), oob = 0.
+struct FxTable {
+    const double *dt;  // null: not built
+    int32_t w, P;
+    uint32_t oob, zero;
+};
+
+// What launch_env_step needs beside StepArgs and no kernel reads through it.
+struct RayLaunch {
+    RayKnobs k;
+    FxTable rm, rmp;                  // the clamped and the padded table
+    uint8_t chunk_order[kMaxChunks];  // beam-chunk dispatch order of the chunked kernels
+    uint64_t *wtrace;                 // diagnostic wave trace of this ray launch (f110_debug_wave_trace) or null
+    hipEvent_t gate_wait;             // f110_debug_set_ray_gate: waited on before the ray launch, or null
+    hipEvent_t gate_record;           //   recorded after it, or null
+};
+
 struct ScanArgs {
     MapView map;
     const double *sines, *cosines;
@@ -366,7 +369,8 @@ struct AdamArgs {
 };
 hipError_t launch_adam(const AdamArgs &a, hipStream_t s);
 
-hipError_t launch_env_step(const StepArgs &a, hipStream_t s, hipEvent_t *ev = nullptr);  // ev: 6 events or null
+hipError_t launch_env_step(const StepArgs &a, const RayLaunch &r, hipStream_t s,
+                           hipEvent_t *ev = nullptr);  // ev: 6 events or null
 hipError_t launch_scan_batch(const ScanArgs &a, hipStream_t s);
 hipError_t launch_gap_follow(const GapFollowArgs &a, hipStream_t s);
 hipError_t launch_reward(const RewardArgs &a, hipStream_t s);

@@ -625,7 +625,7 @@ __device__ __forceinline__ uint32_t dhi(double v) { return (uint32_t)(__double_a
 __device__ __forceinline__ uint32_t dlo(double v) { return (uint32_t)__double_as_longlong(v); }
 
 // The fixed-point loop's EDT: the row-major table of k_rays_fx / k_rays_fxn
-// (StepArgs::rm), rows of k1 = wt * 8 bytes: row * k1 + col * 8, and off-map
+// (FxTable, f110_internal.h), rows of k1 = wt * 8 bytes: row * k1 + col * 8, and off-map
 // indices are clamped into the padding, which holds dt[-1,-1], instead of
 // selected.  Measured at 65536 envs: 1.184 vs 1.210 ms for the
 // 4x4-tiled table; an inexact f32 8x4-tiled or u16 8x8-tiled table (4x the
@@ -2068,14 +2068,99 @@ __global__ void __launch_bounds__(kMultiBlock, 6) k_post_multi(StepArgs a) {
 #endif
 }
 
-// One f110_step / f110_reset: k_agents, the ray kernel, the post stage.
-// The ray kernel by context (f110_create's rules):
-//   ray_kernel 1 / 2: k_rays_tiled in flat / chunked order (rotated maps, or
-//                     where the fixed-point preconditions fail);
-//   ray_kernel 3:     k_rays_fx (1 ray per lane), k_rays_fxn<2> (2 rays per
-//                     lane, padded or clamped table) or, for unmasked steps
-//                     without heavy-first, k_rays_fxs (fx_refill waves per car).
-hipError_t launch_env_step(const StepArgs &a, hipStream_t s, hipEvent_t *ev) {
+// The ray launch of a context, the one place that decides it:
+//   kernel 1:  k_rays_tiled in flat ray order, kBlock rays per block;
+//   kernel 2:  k_rays_tiled chunked: HB heavy-first blocks (steps of a context that keeps a list),
+//              then a block per (chunk, wpb cars); also kernel 3 on a rotated map;
+//   kernel 3:  the fixed-point kernels (f110_create checked their preconditions: axis-aligned map,
+//              one-wave blocks, W, H < 2^21, |origin / res| < 2^20, EDT entries 0 or > eps):
+//              k_rays_fx (1 ray per lane, clamped table), k_rays_fxn<2> (2 rays per lane, a block
+//              per chunk group, on the padded table where it exists) or, for unmasked launches
+//              of a context with refill waves, fxs_ok and no heavy-first, k_rays_fxs.
+RayPlan plan_ray_launch(const RayKnobs &k, bool masked) {
+    const int EA = k.E * k.A, chunks = (k.B + 63) / 64;
+    const bool single = k.A == 1, fx = k.kernel == 3 && !k.rotated && k.ray_wpb == 1 && k.has_rm;
+    const bool pair = fx && k.lanes == 2, pad = pair && k.has_rmp;  // k_rays_fxn<2>; on the padded table
+    RayPlan p{};
+    p.rot = k.rotated != 0;
+    p.mask = masked;
+    p.handoff = !single;  // HANDOFF for A >= 2
+    p.family = F110_RAY_TILED_FLAT;
+    p.table = pad ? F110_TABLE_PADDED : fx ? F110_TABLE_ROWMAJOR : F110_TABLE_TILED;
+    p.grid = (uint32_t)(((int64_t)EA * k.B + kBlock - 1) / kBlock);
+    p.block = (uint32_t)kBlock;
+    if (k.kernel < 2) return p;
+    p.family = pad ? F110_RAY_FXN_PADDED : pair ? F110_RAY_FXN_CLAMPED : fx ? F110_RAY_FX : F110_RAY_TILED_CHUNKED;
+    p.wpb = k.ray_wpb;
+    p.G4 = (EA + p.wpb - 1) / p.wpb;
+    p.nch = pair ? (chunks + 1) / 2 : chunks;  // k_rays_fxn: chunk groups per car (heavy list / wcost units)
+    p.wcost = k.heavy_list && k.heavy_on;  // the cost bytes feed the next step's heavy-first list only
+    if (k.heavy_use && !masked) p.HB = (k.heavy_cap + p.wpb - 1) / p.wpb;
+    p.trace = k.wtrace && !fx && !k.rotated && !masked;  // f110_debug_wave_trace
+    p.grid = (uint32_t)(p.HB + p.G4 * p.nch);
+    p.block = 64u * (uint32_t)p.wpb;
+    if (pad && k.refill > 0 && k.fxs_ok && !masked && p.HB == 0 && !p.wcost) {
+        // k_rays_fxs: one or a few waves per car, two chunk slots with refill (no heavy-first)
+        p.family = F110_RAY_FXS;
+        p.lds = single && k.fxs_lds && k.theta_dis <= kFxsLdsTheta;
+        p.count = k.count_slots != 0;  // f110_debug_set_simt: the variant that counts lookups, rays, lane slots
+        p.G4 = std::min(k.refill, chunks);  // waves per car
+        p.geo_ready = !single && k.has_geo;  // leading geometry items (a multiple of 8: XCD mapping kept)
+        p.geo_blocks = p.geo_ready ? ((EA * (k.A - 1) + 63) / 64 + 7) / 8 * 8 : 0;
+        const int wpb = p.lds ? kFxsWaves : 1;  // k_rays_fxs's work items per block
+        p.grid = (uint32_t)((p.geo_blocks + EA * p.G4 + wpb - 1) / wpb);
+        p.block = 64u * (uint32_t)wpb;
+    }
+    return p;
+}
+
+// The kernel of a plan: every ray kernel the library instantiates is named here.
+#define RAY_FN(...) reinterpret_cast<const void *>(&__VA_ARGS__)
+static const void *ray_kernel_fn(const RayPlan &p) {
+    const int v2 = (p.mask ? 2 : 0) + (p.handoff ? 1 : 0), vt = (p.rot ? 4 : 0) + v2;
+    switch (p.family) {
+    case F110_RAY_TILED_FLAT:
+    case F110_RAY_TILED_CHUNKED: {  // <ROT, MASK, HANDOFF, CH>; <.., TRACE>: the diagnostic wave trace
+        static const void *const fn[2][8] = {
+            {RAY_FN(k_rays_tiled<false, false, false, false>), RAY_FN(k_rays_tiled<false, false, true, false>),
+             RAY_FN(k_rays_tiled<false, true, false, false>), RAY_FN(k_rays_tiled<false, true, true, false>),
+             RAY_FN(k_rays_tiled<true, false, false, false>), RAY_FN(k_rays_tiled<true, false, true, false>),
+             RAY_FN(k_rays_tiled<true, true, false, false>), RAY_FN(k_rays_tiled<true, true, true, false>)},
+            {RAY_FN(k_rays_tiled<false, false, false, true>), RAY_FN(k_rays_tiled<false, false, true, true>),
+             RAY_FN(k_rays_tiled<false, true, false, true>), RAY_FN(k_rays_tiled<false, true, true, true>),
+             RAY_FN(k_rays_tiled<true, false, false, true>), RAY_FN(k_rays_tiled<true, false, true, true>),
+             RAY_FN(k_rays_tiled<true, true, false, true>), RAY_FN(k_rays_tiled<true, true, true, true>)}};
+        static const void *const trace[2] = {RAY_FN(k_rays_tiled<false, false, false, true, true>),
+                                             RAY_FN(k_rays_tiled<false, false, true, true, true>)};
+        return p.trace ? trace[p.handoff] : fn[p.family == F110_RAY_TILED_CHUNKED][vt];
+    }
+    case F110_RAY_FX:
+    case F110_RAY_FXN_CLAMPED:
+    case F110_RAY_FXN_PADDED: {  // k_rays_fx<MASK, HANDOFF>, k_rays_fxn<2, MASK, HANDOFF, PAD>
+        static const void *const fn[3][4] = {
+            {RAY_FN(k_rays_fx<false, false>), RAY_FN(k_rays_fx<false, true>), RAY_FN(k_rays_fx<true, false>),
+             RAY_FN(k_rays_fx<true, true>)},
+            {RAY_FN(k_rays_fxn<2, false, false>), RAY_FN(k_rays_fxn<2, false, true>),
+             RAY_FN(k_rays_fxn<2, true, false>), RAY_FN(k_rays_fxn<2, true, true>)},
+            {RAY_FN(k_rays_fxn<2, false, false, true>), RAY_FN(k_rays_fxn<2, false, true, true>),
+             RAY_FN(k_rays_fxn<2, true, false, true>), RAY_FN(k_rays_fxn<2, true, true, true>)}};
+        return fn[p.family - F110_RAY_FX][v2];
+    }
+    case F110_RAY_FXS: {  // <HANDOFF, LDS, COUNT>: single, single with the LDS theta table, multi-agent
+        static const void *const fn[2][3] = {
+            {RAY_FN(k_rays_fxs<false, false, false>), RAY_FN(k_rays_fxs<false, true, false>),
+             RAY_FN(k_rays_fxs<true, false, false>)},
+            {RAY_FN(k_rays_fxs<false, false, true>), RAY_FN(k_rays_fxs<false, true, true>),
+             RAY_FN(k_rays_fxs<true, false, true>)}};
+        return fn[p.count][p.lds ? 1 : p.handoff ? 2 : 0];
+    }
+    }
+    return nullptr;
+}
+#undef RAY_FN
+
+// One f110_step / f110_reset: k_agents, the ray kernel plan_ray_launch chose, the post stage.
+hipError_t launch_env_step(const StepArgs &a, const RayLaunch &r, hipStream_t s, hipEvent_t *ev) {
     const int EA = a.E * a.A;
     hipError_t e;
     auto evk = [&](int i) -> hipEvent_t { return ev ? ev[i] : nullptr; };  // (start, stop) per kernel
@@ -2085,25 +2170,27 @@ hipError_t launch_env_step(const StepArgs &a, hipStream_t s, hipEvent_t *ev) {
     else
         hipExtLaunchKernelGGL(k_agents<false>, dim3((EA + 63) / 64), dim3(64), 0, s, evk(0), evk(1), 0, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (a.gate_wait && (e = hipStreamWaitEvent(s, a.gate_wait, 0)) != hipSuccess) return e;
+    if (r.gate_wait && (e = hipStreamWaitEvent(s, r.gate_wait, 0)) != hipSuccess) return e;
     const bool single = a.A == 1;
     // f110_debug_set_handoff_check: every hand-off entry NaN (all-ones) before the ray launch, so a
     // k_post_multi read of an entry the ray kernel skipped cannot pass for a fresh one
     if ((a.hcheck & 1) && !single && (e = hipMemsetAsync(a.scan, 0xFF, (size_t)EA * a.B * sizeof(double), s)) != hipSuccess)
         return e;
     RayArgs ra{};
+    ra.reset_mask = a.mode == 1 ? a.reset_mask : nullptr;
+    const RayPlan p = plan_ray_launch(r.k, ra.reset_mask != nullptr);
+    // the common fields
     ra.m = a.tmap;
     ra.sines = a.sines;
     ra.cosines = a.cosines;
     ra.ray0 = a.ray0;
     ra.runs = a.runs;
     ra.nruns = a.nruns;
-    ra.reset_mask = a.mode == 1 ? a.reset_mask : nullptr;
     ra.scan = a.scan;
     ra.noise_ext = a.noise_ext;
     ra.noise_step = a.noise_step;
     ra.ctr = a.ctr;
-    ra.count_slots = a.count_slots;
+    ra.count_slots = r.k.count_slots;
     ra.eps = a.eps;
     ra.max_range = a.max_range;
     ra.noise_std = a.noise_std;
@@ -2127,146 +2214,66 @@ hipError_t launch_env_step(const StepArgs &a, hipStream_t s, hipEvent_t *ev) {
     ra.obs_rinv = obs_reciprocal(ra.lidar_max);
     ra.scans_f32 = a.out.scans;
     ra.scans_f64 = a.out.scans_f64;
-    const bool rot = !(a.tmap.os == 0.0 && a.tmap.oc == 1.0);
-    const bool mask = ra.reset_mask != nullptr;
-    const bool ch = a.ray_kernel >= 2;
-    const int64_t R = (int64_t)EA * a.B;
-    dim3 g2((unsigned)((R + kBlock - 1) / kBlock));
-    if (ch) {
-        ra.wpb = a.ray_wpb;
-        ra.G4 = (EA + ra.wpb - 1) / ra.wpb;
-        ra.nch = (a.B + 63) / 64;
-        for (int i = 0; i < kMaxChunks; ++i) ra.order[i] = a.chunk_order[i];
-        // the per-wave cost bytes feed the next step's heavy-first list only:
-        // not written when heavy-first is off (the stream sub-shard runner)
-        ra.wcost = a.heavy_on ? a.wcost : nullptr;
-        if (a.heavy_use && !mask) {
-            ra.HB = (a.heavy_cap + ra.wpb - 1) / ra.wpb;
-            ra.heavy_list = a.heavy_list + (size_t)a.parity * a.heavy_cap;
-            ra.heavy_mask = a.heavy_mask;
-            ra.heavy_count = a.heavy_count + a.parity;
-        }
-        g2 = dim3((unsigned)(ra.HB + ra.G4 * ra.nch));
+    ra.wtrace = r.wtrace;
+    ra.wpb = p.wpb;
+    ra.G4 = p.G4;
+    ra.nch = p.nch;
+    ra.HB = p.HB;
+    if (p.family != F110_RAY_TILED_FLAT) std::copy(r.chunk_order, r.chunk_order + kMaxChunks, ra.order);
+    if (p.wcost) ra.wcost = a.wcost;
+    if (p.HB) {  // this step's list of heavy waves
+        ra.heavy_list = a.heavy_list + (size_t)a.parity * a.heavy_cap;
+        ra.heavy_mask = a.heavy_mask;
+        ra.heavy_count = a.heavy_count + a.parity;
     }
-    const int vt = (rot ? 4 : 0) + (mask ? 2 : 0) + (single ? 0 : 1);  // HANDOFF for A >= 2
-    const void *tiled_fn[2][8] = {
-        {reinterpret_cast<const void *>(&k_rays_tiled<false, false, false, false>),
-         reinterpret_cast<const void *>(&k_rays_tiled<false, false, true, false>),
-         reinterpret_cast<const void *>(&k_rays_tiled<false, true, false, false>),
-         reinterpret_cast<const void *>(&k_rays_tiled<false, true, true, false>),
-         reinterpret_cast<const void *>(&k_rays_tiled<true, false, false, false>),
-         reinterpret_cast<const void *>(&k_rays_tiled<true, false, true, false>),
-         reinterpret_cast<const void *>(&k_rays_tiled<true, true, false, false>),
-         reinterpret_cast<const void *>(&k_rays_tiled<true, true, true, false>)},
-        {reinterpret_cast<const void *>(&k_rays_tiled<false, false, false, true>),
-         reinterpret_cast<const void *>(&k_rays_tiled<false, false, true, true>),
-         reinterpret_cast<const void *>(&k_rays_tiled<false, true, false, true>),
-         reinterpret_cast<const void *>(&k_rays_tiled<false, true, true, true>),
-         reinterpret_cast<const void *>(&k_rays_tiled<true, false, false, true>),
-         reinterpret_cast<const void *>(&k_rays_tiled<true, false, true, true>),
-         reinterpret_cast<const void *>(&k_rays_tiled<true, true, false, true>),
-         reinterpret_cast<const void *>(&k_rays_tiled<true, true, true, true>)}};
-    const void *f = tiled_fn[ch ? 1 : 0][vt];
-    unsigned bdim = ch ? 64u * (unsigned)ra.wpb : (unsigned)kBlock;
-    bool geo_ready = false;  // the ray launch computes the pairs' ray_cast geometry (k_post_multi reads it)
-    bool fxs = false, lds = false;  // k_rays_fxs; with the LDS theta table
-    // the fixed-point kernels (f110_create checked their preconditions: axis-aligned map,
-    // one-wave blocks, W, H < 2^21, |origin / res| < 2^20, EDT entries 0 or > eps)
-    const bool fx = a.ray_kernel == 3 && !rot && ra.wpb == 1 && a.rm;
-    if (fx) {
-        const int v2 = (mask ? 2 : 0) + (single ? 0 : 1);
-        // the row-major EDT (dt[-1,-1] in the padding column / row, a zero cell past the end)
-        ra.m.dt = a.rm;
-        ra.m.wt = a.rm_w;
-        ra.m.oob = (int32_t)a.rm_oob;
-        ra.fx_zero = a.rm_zero;
-        ra.fx_cx = std::fma(-a.tmap.ox, a.tmap.inv_res, kFxMagic);
-        ra.fx_cy = std::fma(-a.tmap.oy, a.tmap.inv_res, kFxMagic);
-        ra.fx_lim = 2097152.0 - 32.0 - a.max_range * a.tmap.inv_res;
-        const void *fn_1[4] = {reinterpret_cast<const void *>(&k_rays_fx<false, false>),
-                               reinterpret_cast<const void *>(&k_rays_fx<false, true>),
-                               reinterpret_cast<const void *>(&k_rays_fx<true, false>),
-                               reinterpret_cast<const void *>(&k_rays_fx<true, true>)};
-        f = fn_1[v2];
-        if (a.fx_ilp == 2) {
-            const bool pad = a.fx_pad && a.rmp;
-            const void *fn_2[2][4] = {{reinterpret_cast<const void *>(&k_rays_fxn<2, false, false>),
-                                       reinterpret_cast<const void *>(&k_rays_fxn<2, false, true>),
-                                       reinterpret_cast<const void *>(&k_rays_fxn<2, true, false>),
-                                       reinterpret_cast<const void *>(&k_rays_fxn<2, true, true>)},
-                                      {reinterpret_cast<const void *>(&k_rays_fxn<2, false, false, true>),
-                                       reinterpret_cast<const void *>(&k_rays_fxn<2, false, true, true>),
-                                       reinterpret_cast<const void *>(&k_rays_fxn<2, true, false, true>),
-                                       reinterpret_cast<const void *>(&k_rays_fxn<2, true, true, true>)}};
-            f = fn_2[pad ? 1 : 0][v2];
-            ra.nch = (ra.nch + 1) / 2;  // chunk groups per car (heavy list / wcost units)
-            g2 = dim3((unsigned)(ra.HB + ra.G4 * ra.nch));
-            if (pad) {
-                // the padded table (PAD): t = x / res + 2^24 + P; a car's rays stay in the
-                // table when its origin's q + P lies in [Rn, W or H + 2P - Rn),
-                // Rn = max_range / res + 2 cells (each lookup is within max_range of it)
-                const double P = (double)a.rmp_P, Rn = std::ceil(a.max_range * a.tmap.inv_res) + 2.0;
-                ra.m.dt = a.rmp;
-                ra.m.wt = a.rmp_w;
-                ra.m.oob = 0;
-                ra.fx_zero = a.rmp_zero;
-                ra.fxp_P = a.rmp_P;
-                ra.fx_cx = std::fma(-a.tmap.ox, a.tmap.inv_res, kFxpBase + P);
-                ra.fx_cy = std::fma(-a.tmap.oy, a.tmap.inv_res, kFxpBase + P);
-                ra.fxp_lo = Rn;
-                ra.fxp_hx = (double)a.tmap.W + 2.0 * P - Rn;
-                ra.fxp_hy = (double)a.tmap.H + 2.0 * P - Rn;
-                ra.fxs_cx = std::fma(-a.tmap.ox, a.tmap.inv_res, kFxsBase + P + kFxsShift);
-                ra.fxs_cy = std::fma(-a.tmap.oy, a.tmap.inv_res, kFxsBase + P + kFxsShift);
-                if (a.fx_refill > 0 && a.fxs_ok && !mask && ra.HB == 0 && !ra.wcost) {
-                    // one wave per car, two chunk slots with refill (k_rays_fxs; no heavy-first)
-                    lds = single && a.fxs_lds && a.theta_dis <= kFxsLdsTheta;
-                    // COUNT (f110_debug_set_simt): the variant that counts lookups, rays, lane slots
-                    const void *fxs_fn[2][3] = {
-                        {reinterpret_cast<const void *>(&k_rays_fxs<false, false, false>),
-                         reinterpret_cast<const void *>(&k_rays_fxs<false, true, false>),
-                         reinterpret_cast<const void *>(&k_rays_fxs<true, false, false>)},
-                        {reinterpret_cast<const void *>(&k_rays_fxs<false, false, true>),
-                         reinterpret_cast<const void *>(&k_rays_fxs<false, true, true>),
-                         reinterpret_cast<const void *>(&k_rays_fxs<true, false, true>)}};
-                    f = fxs_fn[a.count_slots ? 1 : 0][lds ? 1 : single ? 0 : 2];
-                    fxs = true;
-                    ra.G4 = std::min(a.fx_refill, (a.B + 63) / 64);  // waves per car
-                    if (!single && a.geo) {  // leading geometry items (a multiple of 8: XCD mapping kept)
-                        ra.geo = a.geo;
-                        ra.hmask = a.hmask;
-                        ra.geo_blocks = ((ra.EA * (a.A - 1) + 63) / 64 + 7) / 8 * 8;
-                        ra.st = a.st;
-                        ra.pa = a.pa;
-                        ra.fov = a.fov;
-                        ra.beam_incr = a.beam_incr;
-                        geo_ready = true;
-                    }
-                    const int wpb = lds ? kFxsWaves : 1;  // k_rays_fxs's work items per block
-                    g2 = dim3((unsigned)((ra.geo_blocks + ra.EA * ra.G4 + wpb - 1) / wpb));
-                    bdim = 64u * (unsigned)wpb;
-                }
-            }
+    // the EDT table (ra.m is the 4x4-tiled one so far) and the cell-index constants that go with it
+    if (p.table != F110_TABLE_TILED) {
+        const bool pad = p.table == F110_TABLE_PADDED;
+        const FxTable &t = pad ? r.rmp : r.rm;
+        const TiledMapView &tm = a.tmap;
+        // clamped: t = x / res + 1.5 * 2^22 (kFxMagic); padded (PAD): t = x / res + 2^24 + P
+        const double P = (double)t.P, base = pad ? kFxpBase + P : kFxMagic;
+        ra.m.dt = t.dt;
+        ra.m.wt = t.w;
+        ra.m.oob = (int32_t)t.oob;
+        ra.fx_zero = t.zero;
+        ra.fxp_P = t.P;
+        ra.fx_cx = std::fma(-tm.ox, tm.inv_res, base);
+        ra.fx_cy = std::fma(-tm.oy, tm.inv_res, base);
+        ra.fx_lim = 2097152.0 - 32.0 - a.max_range * tm.inv_res;
+        if (pad) {
+            // a car's rays stay in the padded table when its origin's q + P lies in [Rn, W or H + 2P - Rn),
+            // Rn = max_range / res + 2 cells (each lookup is within max_range of it)
+            const double Rn = std::ceil(a.max_range * tm.inv_res) + 2.0;
+            ra.fxp_lo = Rn;
+            ra.fxp_hx = (double)tm.W + 2.0 * P - Rn;
+            ra.fxp_hy = (double)tm.H + 2.0 * P - Rn;
+            ra.fxs_cx = std::fma(-tm.ox, tm.inv_res, kFxsBase + P + kFxsShift);
+            ra.fxs_cy = std::fma(-tm.oy, tm.inv_res, kFxsBase + P + kFxsShift);
         }
-        if (!fxs) bdim = 64u;
     }
-    if (a.wtrace && ch && !rot && !mask && !fx)  // diagnostic wave trace (f110_debug_wave_trace)
-        f = single ? reinterpret_cast<const void *>(&k_rays_tiled<false, false, false, true, true>)
-                   : reinterpret_cast<const void *>(&k_rays_tiled<false, false, true, true, true>);
-    ra.wtrace = a.wtrace;
+    if (p.geo_ready) {  // k_rays_fxs<HANDOFF>'s leading items compute the pairs' ray_cast geometry
+        ra.geo = a.geo;
+        ra.hmask = a.hmask;
+        ra.geo_blocks = p.geo_blocks;
+        ra.st = a.st;
+        ra.pa = a.pa;
+        ra.fov = a.fov;
+        ra.beam_incr = a.beam_incr;
+    }
     void *args[] = {&ra};
-    if ((e = hipExtLaunchKernel(f, g2, dim3(bdim), args, 0u, s, evk(2), evk(3), 0)) != hipSuccess) return e;
+    if ((e = hipExtLaunchKernel(ray_kernel_fn(p), dim3(p.grid), dim3(p.block), args, 0u, s, evk(2), evk(3), 0)) != hipSuccess)
+        return e;
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (a.gate_record && (e = hipEventRecord(a.gate_record, s)) != hipSuccess) return e;
+    if (r.gate_record && (e = hipEventRecord(r.gate_record, s)) != hipSuccess) return e;
     if (single)
         hipExtLaunchKernelGGL(k_post_single, dim3((a.E + 63) / 64), dim3(64), 0, s, evk(4), evk(5), 0, a);
     else {
         StepArgs pa_ = a;
-        pa_.geo_ready = geo_ready ? 1 : 0;
+        pa_.geo_ready = p.geo_ready;  // k_post_multi reads the geometry the ray launch computed
         hipExtLaunchKernelGGL(k_post_multi, dim3(a.E), dim3(kMultiBlock), 0, s, evk(4), evk(5), 0, pa_);
     }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    return hipSuccess;
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------

@@ -339,12 +339,14 @@ class BatchSim:
 
     @property
     def ray_kernel(self) -> int:
-        """The ray kernel this context launches (f110_debug_ray_kernel: 3 = the fixed-point kernels)."""
+        """The ray kernel this context's steps launch, read from the launch plan (plan_ray_launch,
+        DESIGN §3.5; f110_debug_ray_kernel: 1 / 2 k_rays_tiled flat / chunked, 3 the fixed-point kernels)."""
         return _lib.check(self.L.f110_debug_ray_kernel(self.ctx), "f110_debug_ray_kernel")
 
     @property
     def ray_lanes(self) -> int:
-        """Rays per lane of the fixed-point ray kernel (f110_debug_ray_lanes: 1 = k_rays_fx, 2 = k_rays_fxn / fxs)."""
+        """Rays per lane of the planned kernel (plan_ray_launch; f110_debug_ray_lanes: 1 = k_rays_fx or
+        k_rays_tiled, 2 = k_rays_fxn / fxs)."""
         return _lib.check(self.L.f110_debug_ray_lanes(self.ctx), "f110_debug_ray_lanes")
 
     def set_ray_lanes(self, n: int):
@@ -358,8 +360,8 @@ class BatchSim:
 
     @property
     def ray_refill(self) -> int:
-        """k_rays_fxs's waves per car for unmasked steps (f110_debug_ray_refill), 0 when k_rays_fxn /
-        k_rays_fx trace this context's rays."""
+        """k_rays_fxs's waves per car in the plan of an unmasked step (plan_ray_launch;
+        f110_debug_ray_refill), 0 when k_rays_fxn / k_rays_fx trace this context's rays."""
         return _lib.check(self.L.f110_debug_ray_refill(self.ctx), "f110_debug_ray_refill")
 
     def disable_heavy_first(self):

@@ -87,7 +87,9 @@ class StreamShards:
         # the ray kernel for the cars the GPU traces at once (f110_set_device_share applies
         # f110_create's size rules to the device's cars: 8192 envs as 4 x 2048 53.1 vs 47.6 M env-steps/s
         # with 1 vs 2 rays per lane, 32768 as 2 x 16384 69.2 vs 62.6 M with k_rays_fxs);
-        # explicit ray_lanes / refill (A/B runs) go through the f110_debug_* knobs instead
+        # that single call is the product path.  Explicit ray_lanes / refill / heavy_first (A/B runs,
+        # tests, scripts/) go through the f110_debug_* knobs instead; what they leave unset falls back
+        # to the A/B defaults of rounds 3 and 4 below, which are not the product's size rules
         explicit = ray_lanes is not None or refill is not None or heavy_first
         cars = n_envs * self.n_agents
         for s in range(self.S):

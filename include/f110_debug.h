@@ -136,6 +136,50 @@ F110_API int f110_debug_set_ray_refill(f110_ctx *ctx, int32_t waves);
  * Diagnostic / tuning, no reference counterpart. */
 F110_API int f110_debug_set_ray_lanes(f110_ctx *ctx, int32_t n);
 
+/* ---- the ray launch plan (host) --------------------------------------------
+ * Which ray kernel a context launches, on which grid and EDT table, is one
+ * pure function of the plain values below (plan_ray_launch in
+ * f110_kernels.hip): f110_step / f110_reset launch what it
+ * returns, and the f110_debug_ray_* getters read it. */
+enum { F110_RAY_TILED_FLAT = 0, F110_RAY_TILED_CHUNKED, F110_RAY_FX, F110_RAY_FXN_CLAMPED, F110_RAY_FXN_PADDED,
+       F110_RAY_FXS };
+enum { F110_TABLE_TILED = 0, F110_TABLE_ROWMAJOR, F110_TABLE_PADDED };
+typedef struct f110_ray_knobs {
+    int32_t kernel;       /* f110_debug_ray_kernel: 1, 2 or 3, after f110_create's fallbacks */
+    int32_t lanes;        /* rays per lane of the fixed-point kernels (1 or 2) */
+    int32_t refill;       /* k_rays_fxs's waves per car (0: off) */
+    int32_t fxs_lds;      /* k_rays_fxs in 8-wave blocks with the theta table in LDS (a shared device) */
+    int32_t count_slots;  /* f110_debug_set_simt */
+    int32_t wtrace;       /* a wave trace is armed for this launch */
+    int32_t heavy_list;   /* the context has a heavy-first list, */
+    int32_t heavy_on;     /*   keeps it up (the launch writes the per-wave costs), */
+    int32_t heavy_use;    /*   and this launch runs it (steps, not resets); */
+    int32_t heavy_cap;    /*   its capacity in waves */
+    int32_t has_rm, has_rmp;  /* the clamped row-major / the padded EDT table exists */
+    int32_t fxs_ok;       /* the padded table's rows and columns are below 2^20 */
+    int32_t rotated;      /* the map's origin has a yaw */
+    int32_t E, A, B, theta_dis, ray_wpb;
+    int32_t has_geo;      /* the pair-geometry buffer exists (A >= 2) */
+} f110_ray_knobs;
+typedef struct f110_ray_plan {
+    int32_t family;                                /* F110_RAY_* */
+    int32_t rot, mask, handoff, lds, count, trace; /* the kernel's template flags */
+    uint32_t grid, block;
+    int32_t wpb, nch, G4, HB, geo_blocks;          /* RayArgs' launch shape */
+    int32_t table;                                 /* F110_TABLE_*: the EDT the launch reads */
+    int32_t wcost;                                 /* the launch writes the per-wave cost bytes */
+    int32_t geo_ready;                             /* the launch computes the pair geometry */
+} f110_ray_plan;
+/* The plan of a launch with these knobs (masked: f110_reset with an env mask).  Host test hook. */
+F110_API int f110_host_ray_plan(const f110_ray_knobs *in, int32_t masked, f110_ray_plan *out);
+/* The size rules of f110_create (device_cars = own_cars, contexts = 1) and
+ * f110_set_device_share: out = {rays per lane, k_rays_fxs's waves per car,
+ * heavy-first on, fxs_lds} for a context of own_cars on a device that traces
+ * device_cars at once in `contexts` contexts, whose ray kernel is `kernel` and
+ * which may build the padded table (pad_allowed).  Host test hook. */
+F110_API int f110_host_ray_rules(int64_t own_cars, int64_t device_cars, int32_t contexts, int32_t kernel,
+                                 int32_t pad_allowed, int32_t out[4]);
+
 /* ---- host-side test hooks (no device work) -------------------------------
  * The lookup tables f110_create uploads: ScanSimulator2D sines/cosines
  * (laser_models.py:379-381) and RaceCar's class-level beam tables

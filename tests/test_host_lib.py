@@ -452,3 +452,114 @@ def test_host_map_tables(L, H, W, pad):
             grid[pad:pad + H, pad:pad + W] = dt
         ref[rows * cols] = 0.0
         assert np.array_equal(out, ref)
+
+
+# f110_ray_knobs of the flagship context: the fixed-point kernels with 2 rays per lane, the padded table
+# within k_rays_fxs's offsets, one refill wave, 65536 single-agent cars, 1080 beams (17 chunks, 9 groups)
+_KNOBS = dict(kernel=3, lanes=2, refill=1, fxs_lds=0, count_slots=0, wtrace=0, heavy_list=0, heavy_on=1,
+              heavy_use=0, heavy_cap=0, has_rm=1, has_rmp=1, fxs_ok=1, rotated=0, E=65536, A=1, B=1080,
+              theta_dis=2000, ray_wpb=1, has_geo=0)
+_SHARED = dict(fxs_lds=1, E=32768)                       # one of two contexts sharing the device
+_MULTI = dict(A=2, E=8192, refill=2, has_geo=1)          # 16384 cars in two-agent envs
+_TILED = dict(kernel=2, has_rm=0, has_rmp=0, refill=0, lanes=1)
+# capacity of f110_create's list at 16384 cars: max(64, (16384 * 17 / 6 + 3) / 4 * 4)
+_HEAVY = dict(_TILED, E=16384, heavy_list=1, heavy_on=1, heavy_use=1, heavy_cap=46424)
+_PLAN_ROWS = [
+    # (knobs over _KNOBS, masked, expected plan fields)
+    ({}, False, dict(family="fxs", table="padded", lds=0, count=0, mask=0, handoff=0, grid=65536, block=64, G4=1,
+                     HB=0, geo_blocks=0, geo_ready=0)),
+    (dict(count_slots=1), False, dict(family="fxs", lds=0, count=1, grid=65536, block=64, G4=1)),
+    (_SHARED, False, dict(family="fxs", lds=1, count=0, grid=4096, block=512, G4=1)),
+    (dict(_SHARED, theta_dis=4096), False, dict(family="fxs", lds=0, grid=32768, block=64)),  # > kFxsLdsTheta
+    (_MULTI, False, dict(family="fxs", handoff=1, lds=0, G4=2, geo_blocks=256, grid=33024, block=64, geo_ready=1)),
+    (dict(_MULTI, fxs_lds=1), False, dict(family="fxs", handoff=1, lds=0, grid=33024, block=64)),  # LDS: A = 1 only
+    (dict(_MULTI, has_geo=0), False, dict(family="fxs", handoff=1, geo_blocks=0, grid=32768, geo_ready=0)),
+    (dict(refill=3, B=130, E=200), False, dict(family="fxs", G4=3, grid=600, block=64)),
+    (dict(refill=16, B=130, E=200), False, dict(family="fxs", G4=3, grid=600, block=64)),
+    (dict(refill=16), False, dict(family="fxs", G4=16, grid=16 * 65536)),
+    (dict(refill=3, B=64, E=200), False, dict(family="fxs", G4=1, grid=200)),
+    # a masked reset runs k_rays_fxn<2, MASK, ., PAD> whatever the step runs: a block per (car, chunk group)
+    ({}, True, dict(family="fxn_padded", table="padded", mask=1, handoff=0, lds=0, count=0, nch=9, grid=9 * 65536,
+                    block=64, geo_ready=0)),
+    (dict(count_slots=1), True, dict(family="fxn_padded", mask=1, count=0, grid=9 * 65536, block=64)),
+    (_SHARED, True, dict(family="fxn_padded", mask=1, lds=0, grid=9 * 32768, block=64)),
+    (_MULTI, True, dict(family="fxn_padded", mask=1, handoff=1, grid=9 * 16384, block=64, geo_blocks=0,
+                        geo_ready=0)),
+    (dict(has_rmp=0, fxs_ok=0), False, dict(family="fxn_clamped", table="rowmajor", nch=9, grid=9 * 65536,
+                                            block=64)),  # F110_FX_PAD=0
+    (dict(has_rmp=0, fxs_ok=0), True, dict(family="fxn_clamped", table="rowmajor", mask=1, grid=9 * 65536)),
+    (dict(fxs_ok=0), False, dict(family="fxn_padded", table="padded", nch=9, grid=9 * 65536, block=64)),
+    (dict(refill=0), False, dict(family="fxn_padded", table="padded", grid=9 * 65536)),
+    (dict(lanes=1), False, dict(family="fx", table="rowmajor", nch=17, grid=17 * 65536, block=64)),
+    (dict(lanes=1, A=2, E=150), True, dict(family="fx", mask=1, handoff=1, grid=17 * 300, block=64)),
+    # the tiled kernels: chunked with the heavy-first list's blocks leading, on steps only
+    (_HEAVY, False, dict(family="tiled_chunked", table="tiled", wcost=1, HB=46424, nch=17, G4=16384,
+                         grid=46424 + 17 * 16384, block=64, rot=0)),
+    (_HEAVY, True, dict(family="tiled_chunked", wcost=1, HB=0, grid=17 * 16384, mask=1)),
+    (dict(_HEAVY, heavy_use=0), False, dict(family="tiled_chunked", wcost=1, HB=0, grid=17 * 16384)),  # a reset
+    (dict(_HEAVY, heavy_on=0, heavy_use=0), False, dict(family="tiled_chunked", wcost=0, HB=0, grid=17 * 16384)),
+    (dict(_TILED), False, dict(family="tiled_chunked", wcost=0, HB=0, grid=17 * 65536, block=64)),  # no list
+    (dict(_TILED, kernel=1, E=300), False, dict(family="tiled_flat", table="tiled", grid=1266, block=256, rot=0,
+                                                nch=0, G4=0, HB=0)),
+    (dict(_TILED, kernel=1, E=300, A=2, rotated=1), True, dict(family="tiled_flat", grid=2532, block=256, rot=1,
+                                                               mask=1, handoff=1)),
+    (dict(_TILED, rotated=1), False, dict(family="tiled_chunked", table="tiled", rot=1, grid=17 * 65536)),
+    (dict(rotated=1), False, dict(family="tiled_chunked", table="tiled", rot=1, grid=17 * 65536, block=64)),
+    # the wave trace: the chunked tiled kernel on an axis-aligned map without a mask; ignored otherwise
+    (dict(_TILED, wtrace=1), False, dict(family="tiled_chunked", trace=1, grid=17 * 65536)),
+    (dict(_TILED, wtrace=1, A=2, E=100), False, dict(family="tiled_chunked", trace=1, handoff=1, grid=17 * 200)),
+    (dict(_TILED, wtrace=1), True, dict(family="tiled_chunked", trace=0)),
+    (dict(_TILED, wtrace=1, rotated=1), False, dict(family="tiled_chunked", trace=0, rot=1)),
+    (dict(_TILED, wtrace=1, kernel=1), False, dict(family="tiled_flat", trace=0)),
+    (dict(wtrace=1), False, dict(family="fxs", trace=0)),
+    (dict(wtrace=1, lanes=1), False, dict(family="fx", trace=0)),
+]
+
+
+@pytest.mark.parametrize("row", range(len(_PLAN_ROWS)))
+def test_ray_plan(L, row):
+    """plan_ray_launch (f110_host_ray_plan), the one function that decides a
+    context's ray kernel, grid and EDT table: the family,
+    template flags and launch shape for each kind of context, as literals."""
+    from f110_gymnasium_ros2_jazzy_amd import _lib
+    over, masked, want = _PLAN_ROWS[row]
+    k = _lib.F110RayKnobs(**dict(_KNOBS, **over))
+    p = _lib.F110RayPlan()
+    assert L.f110_host_ray_plan(ctypes.byref(k), int(masked), ctypes.byref(p)) == 0
+    got = {n: getattr(p, n) for n, _ in p._fields_}
+    got["family"] = _lib.RAY_FAMILIES[p.family]
+    got["table"] = _lib.RAY_TABLES[p.table]
+    assert {n: got[n] for n in want} == want
+
+
+def test_ray_plan_rejects_bad_knobs(L):
+    from f110_gymnasium_ros2_jazzy_amd import _lib
+    p = _lib.F110RayPlan()
+    assert L.f110_host_ray_plan(None, 0, ctypes.byref(p)) < 0
+    assert L.f110_host_ray_plan(ctypes.byref(_lib.F110RayKnobs(**dict(_KNOBS, ray_wpb=0))), 0, ctypes.byref(p)) < 0
+
+
+@pytest.mark.parametrize("own,device,contexts,kernel,pad,want", [
+    # the fixed-point kernels with the padded table: k_rays_fxs's waves per car by the device's cars
+    (4096, 4096, 1, 3, 1, (2, 3, 0, 0)), (8192, 8192, 1, 3, 1, (2, 3, 0, 0)), (16383, 16383, 1, 3, 1, (2, 3, 0, 0)),
+    (16384, 16384, 1, 3, 1, (2, 2, 0, 0)), (32767, 32767, 1, 3, 1, (2, 2, 0, 0)),
+    (32768, 32768, 1, 3, 1, (2, 1, 0, 0)), (65536, 65536, 1, 3, 1, (2, 1, 0, 0)),
+    # a shared device: the device's cars decide the waves, several contexts the LDS theta table
+    (4096, 8192, 1, 3, 1, (2, 3, 0, 0)), (16384, 32768, 2, 3, 1, (2, 1, 0, 1)), (8192, 32768, 4, 3, 1, (2, 1, 0, 1)),
+    (4096, 16384, 4, 3, 1, (2, 2, 0, 1)), (2048, 8192, 4, 3, 1, (2, 3, 0, 1)),
+    # the tiled kernels: one ray per lane, no refill; heavy-first between 8192 and 32768 cars, alone
+    (8192, 8192, 1, 2, 1, (1, 0, 0, 0)), (8193, 8193, 1, 2, 1, (1, 0, 1, 0)), (16384, 16384, 1, 2, 1, (1, 0, 1, 0)),
+    (32767, 32767, 1, 2, 0, (1, 0, 1, 0)), (32768, 32768, 1, 2, 1, (1, 0, 0, 0)),
+    (16384, 32768, 1, 2, 1, (1, 0, 1, 0)), (16384, 32768, 2, 2, 1, (1, 0, 0, 0)), (16384, 16384, 1, 1, 1, (1, 0, 1, 0)),
+    # without the padded table (F110_FX_PAD=0): no refill, 2 rays per lane from 12288 device cars
+    (4096, 4096, 1, 3, 0, (1, 0, 0, 0)), (12287, 12287, 1, 3, 0, (1, 0, 0, 0)), (12288, 12288, 1, 3, 0, (2, 0, 0, 0)),
+    (4096, 16384, 4, 3, 0, (2, 0, 0, 1)), (2048, 8192, 4, 3, 0, (1, 0, 0, 1)),
+])
+def test_ray_size_rules(L, own, device, contexts, kernel, pad, want):
+    """The size rules of f110_create and f110_set_device_share
+    (f110_host_ray_rules): rays per lane, k_rays_fxs's waves per
+    car, heavy-first, the LDS theta table."""
+    out = (ctypes.c_int32 * 4)()
+    assert L.f110_host_ray_rules(own, device, contexts, kernel, pad, out) == 0
+    assert tuple(out) == want
+    assert L.f110_host_ray_rules(device + 1, device, contexts, kernel, pad, out) < 0
