@@ -75,6 +75,9 @@ RAY_TABLES = ("tiled", "rowmajor", "padded")  # F110_TABLE_*
 
 REWARD_STATE_BYTES = 8 * 12 + 4 * 4   # f110_reward_state
 
+PARAM_FIELDS = tuple(n for n, _ in F110Params._fields_)
+DYN_FIELDS = PARAM_FIELDS[:16]  # the fields a context may hold per env (f110_set_env_params)
+
 ABI_VERSION = 3  # include/f110.h F110_ABI_VERSION
 F32 = 0
 F64 = 1
@@ -92,6 +95,8 @@ EXPORTS = [
     "f110_replay_sample", "f110_replay_update_priorities", "f110_replay_length", "f110_replay_arrays",
     "f110_debug_wave_trace", "f110_debug_set_ray_gate", "f110_debug_disable_heavy_first", "f110_debug_ray_kernel", "f110_debug_ray_lanes", "f110_debug_ray_refill", "f110_debug_set_ray_refill", "f110_debug_read_counter", "f110_step_n", "f110_debug_set_ray_lanes", "f110_set_reset_dtype", "f110_set_device_share", "f110_host_np_sincosf", "f110_host_sincos", "f110_host_sincos_series", "f110_host_map_table", "f110_get_lap_state",
     "f110_host_ray_plan", "f110_host_ray_rules",
+    "f110_set_env_params", "f110_get_env_params", "f110_set_param_randomization",
+    "f110_host_check_param_ranges", "f110_host_param_draw",
     "f110_dynamics_ks_batch", "f110_collision_batch", "f110_collision_multiple", "f110_adam_step", "f110_ddpg_scratch_floats", "f110_ddpg_actor_head", "f110_ddpg_actor_explore",
     "f110_ddpg_actor_head_bwd", "f110_ddpg_td_target", "f110_ddpg_critic_loss", "f110_ddpg_critic_loss_bwd",
     "f110_ddpg_q_mean", "f110_ddpg_q_mean_bwd", "f110_ddpg_relu_bwd_scratch_floats", "f110_ddpg_relu_bwd",
@@ -226,6 +231,12 @@ def load(build_if_missing: bool = True):
     L.f110_host_map_table.restype = ctypes.c_int64
     L.f110_host_ray_plan.argtypes = [ctypes.POINTER(F110RayKnobs), i32, ctypes.POINTER(F110RayPlan)]
     L.f110_host_ray_rules.argtypes = [i64, i64, i32, i32, i32, ctypes.POINTER(i32)]
+    PP = ctypes.POINTER(F110Params)
+    L.f110_set_env_params.argtypes = [_P, PP, _P]
+    L.f110_get_env_params.argtypes = [_P, PP, _P]
+    L.f110_set_param_randomization.argtypes = [_P, PP, PP, u64, _P]
+    L.f110_host_check_param_ranges.argtypes = [PP, PP, PP, i32]
+    L.f110_host_param_draw.argtypes = [u64, i64, i32, u64, PP, PP, PP]
     L.f110_adam_step.argtypes = [_P, _P, _P, _P, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                  ctypes.c_double, _P, _P, ctypes.c_double, _P]
     f32 = ctypes.c_float

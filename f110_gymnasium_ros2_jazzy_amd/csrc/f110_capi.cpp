@@ -101,6 +101,12 @@ struct f110_ctx {
     int32_t hcheck = 0;        // f110_debug_set_handoff_check: bit 0 poison + count misses, bit 1 mask off,
                                // bit 2 an empty mask (the check's own test)
     int fx_ilp = 1;         // rays per lane (f110_debug_set_ray_lanes; default by car count)
+    // per-env vehicle params (f110_set_env_params / f110_set_param_randomization); the buffers are
+    // allocated by the first setter that needs them and kept until f110_destroy
+    double *ptab = nullptr;    // [kDynFields][E*A]
+    double *prange = nullptr;  // [A][2][kDynFields]
+    bool ptab_on = false, prange_on = false;  // the steps read the table / redraw rows at resets
+    uint64_t pseed = 0;
 
     hipEvent_t *next_prof_events() {
         if (prof_n >= prof_max) return nullptr;
@@ -953,6 +959,11 @@ static StepArgs make_step_args(f110_ctx *c, const f110_outputs *out) {
         a.heavy_T = c->heavy_T;
     }
     a.reset_f32 = c->reset_f32 ? 1 : 0;
+    if (c->ptab_on) {
+        a.ptab = c->ptab;
+        a.prange = c->prange_on ? c->prange : nullptr;
+        a.pseed = c->pseed;
+    }
     return a;
 }
 
@@ -1309,6 +1320,152 @@ extern "C" int f110_set_params(f110_ctx *ctx, const f110_params *params, int32_t
     HIP_TRY(hipMemcpyAsync(ctx->pa, ctx->agent_p.data(), ctx->agent_p.size() * sizeof(f110_params),
                            hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));  // agent_p may change again before an async copy would have read it
+    return F110_OK;
+}
+
+// ------------------------------------------------- per-env vehicle params --
+static const char *const kParamNames[19] = {"mu", "C_Sf", "C_Sr", "lf", "lr", "h", "m", "I", "s_min", "s_max",
+                                            "sv_min", "sv_max", "v_switch", "a_max", "v_min", "v_max",
+                                            "width", "length", "lidar_max"};
+static_assert(sizeof(f110_params) == 19 * sizeof(double), "f110_params is 19 doubles");
+
+static const double *fields(const f110_params &p) { return reinterpret_cast<const double *>(&p); }
+
+// One row against its agent's params: every value finite, width / length / lidar_max the agent's.
+// F110_OK, or F110_E_INVALID with the message "<who>: <field><where()> ..." (where: only built then).
+template <class Where>
+static int check_param_row(const char *who, const f110_params &row, const f110_params &agent, Where where) {
+    for (int k = 0; k < 19; ++k) {
+        const double v = fields(row)[k];
+        if (!std::isfinite(v))
+            return fail(F110_E_INVALID, std::string(who) + ": " + kParamNames[k] + where() + " is not finite");
+        if (k >= kDynFields && v != fields(agent)[k])
+            return fail(F110_E_INVALID, std::string(who) + ": " + kParamNames[k] + where() +
+                                            " differs from the agent's (the car boxes and the obs scale do not vary per env)");
+    }
+    return F110_OK;
+}
+
+static int check_param_ranges(const char *who, const f110_params *lo, const f110_params *hi, const f110_params *agents,
+                              int32_t n_agents) {
+    if (!lo || !hi || !agents || n_agents <= 0) return fail(F110_E_INVALID, std::string(who) + ": null argument");
+    for (int i = 0; i < n_agents; ++i) {
+        const std::string where = " (agent " + std::to_string(i) + ")";
+        int rc = check_param_row(who, lo[i], agents[i], [&] { return " lo" + where; });
+        if (rc == F110_OK) rc = check_param_row(who, hi[i], agents[i], [&] { return " hi" + where; });
+        if (rc != F110_OK) return rc;
+        for (int k = 0; k < kDynFields; ++k) {
+            if (fields(lo[i])[k] > fields(hi[i])[k])
+                return fail(F110_E_INVALID, std::string(who) + ": " + kParamNames[k] + where + " has lo > hi");
+            if (!std::isfinite(fields(hi[i])[k] - fields(lo[i])[k]))
+                return fail(F110_E_INVALID, std::string(who) + ": " + kParamNames[k] + where + " hi - lo is not finite");
+        }
+    }
+    return F110_OK;
+}
+
+extern "C" int f110_host_check_param_ranges(const f110_params *lo, const f110_params *hi, const f110_params *agent_params,
+                                            int32_t n_agents) {
+    return check_param_ranges("f110_host_check_param_ranges", lo, hi, agent_params, n_agents);
+}
+
+extern "C" int f110_host_param_draw(uint64_t seed, int64_t env, int32_t agent, uint64_t episode, const f110_params *lo,
+                                    const f110_params *hi, f110_params *out) {
+    if (!lo || !hi || !out || agent < 0 || agent >= kMaxAgents)
+        return fail(F110_E_INVALID, "f110_host_param_draw: null argument or bad agent");
+    double range[2 * kDynFields], v[kDynFields];
+    std::memcpy(range, lo, sizeof(double) * kDynFields);
+    std::memcpy(range + kDynFields, hi, sizeof(double) * kDynFields);
+    param_draw(seed, (uint64_t)env, agent, episode, range, v);
+    *out = *lo;
+    std::memcpy(out, v, sizeof(v));
+    return F110_OK;
+}
+
+// The table (allocated on first use, kept until f110_destroy) filled with row(g), car g's f110_params.
+template <class Row>
+static int upload_param_table(f110_ctx *ctx, hipStream_t s, Row row) {
+    const size_t EA = (size_t)ctx->cfg.n_envs * ctx->cfg.n_agents;
+    if (!ctx->ptab) {
+        hipError_t e = ctx->alloc(&ctx->ptab, (size_t)kDynFields * EA);
+        if (e != hipSuccess) return fail(F110_E_ALLOC, std::string("hipMalloc ptab: ") + hipGetErrorString(e));
+    }
+    std::vector<double> t((size_t)kDynFields * EA);
+    for (size_t g = 0; g < EA; ++g)
+        for (int k = 0; k < kDynFields; ++k) t[(size_t)k * EA + g] = fields(row(g))[k];
+    HIP_TRY(hipMemcpyAsync(ctx->ptab, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // t goes out of scope
+    return F110_OK;
+}
+
+extern "C" int f110_set_env_params(f110_ctx *ctx, const f110_params *params, void *stream) {
+    if (!ctx) return fail(F110_E_INVALID, "f110_set_env_params: null context");
+    if (!params) {  // back to the per-agent params (the randomization redraws table rows: off with it)
+        ctx->ptab_on = ctx->prange_on = false;
+        return F110_OK;
+    }
+    const size_t E = (size_t)ctx->cfg.n_envs, A = (size_t)ctx->cfg.n_agents, EA = E * A;
+    for (size_t g = 0; g < EA; ++g) {
+        const int rc = check_param_row("f110_set_env_params", params[g], ctx->agent_p[g % A], [&] {
+            return " (env " + std::to_string(g / A) + ", agent " + std::to_string(g % A) + ")";
+        });
+        if (rc != F110_OK) return rc;
+    }
+    if (use_device(ctx) != F110_OK) return F110_E_HIP;
+    const int rc = upload_param_table(ctx, (hipStream_t)stream, [&](size_t g) -> const f110_params & { return params[g]; });
+    if (rc == F110_OK) ctx->ptab_on = true;
+    return rc;
+}
+
+extern "C" int f110_get_env_params(f110_ctx *ctx, f110_params *out, void *stream) {
+    if (!ctx || !out) return fail(F110_E_INVALID, "f110_get_env_params: null argument");
+    const size_t E = (size_t)ctx->cfg.n_envs, A = (size_t)ctx->cfg.n_agents, EA = E * A;
+    if (use_device(ctx) != F110_OK) return F110_E_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<double> t;
+    if (ctx->ptab_on) {
+        t.resize((size_t)kDynFields * EA);
+        HIP_TRY(hipMemcpyAsync(t.data(), ctx->ptab, t.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t g = 0; g < EA; ++g) {
+        out[g] = ctx->agent_p[g % A];
+        if (ctx->ptab_on)
+            for (int k = 0; k < kDynFields; ++k) reinterpret_cast<double *>(&out[g])[k] = t[(size_t)k * EA + g];
+    }
+    return F110_OK;
+}
+
+extern "C" int f110_set_param_randomization(f110_ctx *ctx, const f110_params *lo, const f110_params *hi, uint64_t seed,
+                                            void *stream) {
+    if (!ctx) return fail(F110_E_INVALID, "f110_set_param_randomization: null context");
+    if (!lo && !hi) {  // off; the table stays as it stands
+        ctx->prange_on = false;
+        return F110_OK;
+    }
+    const int A = ctx->cfg.n_agents;
+    const int rc = check_param_ranges("f110_set_param_randomization", lo, hi, ctx->agent_p.data(), A);
+    if (rc != F110_OK) return rc;  // (before any device call)
+    if (use_device(ctx) != F110_OK) return F110_E_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    if (!ctx->prange) {
+        hipError_t e = ctx->alloc(&ctx->prange, (size_t)A * 2 * kDynFields);
+        if (e != hipSuccess) return fail(F110_E_ALLOC, std::string("hipMalloc prange: ") + hipGetErrorString(e));
+    }
+    if (!ctx->ptab_on) {  // no table in force: one of the per-agent params
+        const int rt = upload_param_table(ctx, s, [&](size_t g) -> const f110_params & { return ctx->agent_p[g % (size_t)A]; });
+        if (rt != F110_OK) return rt;
+    }
+    std::vector<double> r((size_t)A * 2 * kDynFields);
+    for (int i = 0; i < A; ++i)
+        for (int k = 0; k < kDynFields; ++k) {
+            r[((size_t)i * 2) * kDynFields + k] = fields(lo[i])[k];
+            r[((size_t)i * 2 + 1) * kDynFields + k] = fields(hi[i])[k];
+        }
+    HIP_TRY(hipMemcpyAsync(ctx->prange, r.data(), r.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ctx->pseed = seed;
+    ctx->ptab_on = ctx->prange_on = true;
     return F110_OK;
 }
 

@@ -9,6 +9,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/f110.h"
@@ -1269,6 +1270,38 @@ F110_HD uint32_t spawn_draw(uint64_t seed, uint64_t env, uint64_t episode) {
     U4 c = {(uint32_t)episode, (uint32_t)(episode >> 32), 0x5BA3Eu, 0u};
     U4 r = philox(c, (uint32_t)seed ^ (uint32_t)env, (uint32_t)(seed >> 32) ^ (uint32_t)(env >> 32) ^ 0xA5A5A5A5u);
     return r.x;
+}
+
+// ------------------------------------------------- per-env vehicle params --
+// The 16 dynamics fields of f110_params (mu .. v_max, the struct's leading doubles) are the ones a
+// context may hold per car (f110_set_env_params); width, length and lidar_max stay per agent.
+constexpr int kDynFields = 16;
+static_assert(offsetof(f110_params, width) == kDynFields * sizeof(double), "the dynamics fields lead f110_params");
+
+// Domain randomization (f110_set_param_randomization): field k of a resetting car is
+// lo[k] + u * (hi[k] - lo[k]) with u = r * 2^-32 for a Philox4x32 word r (no FMA: the library is
+// built with contraction off).  Keyed by (seed, global env id) like spawn_draw; counter =
+// (episode, tag 0xD0A17 -- not spawn_draw's 0x5BA3E --, agent * 4 + k / 4), word k % 4 of the block:
+// four Philox blocks per car.  episode counts from the env's last explicit reset (0 for f110_reset,
+// the finished episode's number + 1 for an autoreset), as the spawn draws do.  hi == lo gives lo.
+// range: the agent's (lo[16], hi[16]).
+F110_HD void param_draw(uint64_t seed, uint64_t env, int agent, uint64_t episode, const double *range,
+                        double out[kDynFields]) {
+    const uint32_t k0 = (uint32_t)seed ^ (uint32_t)env;
+    const uint32_t k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(env >> 32) ^ 0xA5A5A5A5u;
+#pragma unroll
+    for (int j = 0; j < kDynFields / 4; ++j) {
+        const U4 c = {(uint32_t)episode, (uint32_t)(episode >> 32), 0xD0A17u, (uint32_t)(agent * 4 + j)};
+        const U4 r = philox(c, k0, k1);
+        const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = 4 * j + q;
+            const double lo = range[k], hi = range[kDynFields + k];
+            const double u = (double)w[q] * (1.0 / 4294967296.0);
+            out[k] = lo + u * (hi - lo);
+        }
+    }
 }
 
 }  // namespace f110

@@ -81,6 +81,10 @@ struct StepArgs {
     const uint8_t *reset_mask;  // [E] or null
     f110_outputs out;
     unsigned long long *ctr;    // [kCtrSlots][16]: [0] lookups, [1] rays (see count_rays), [2] lane slots of the fixed-point loops
+    // per-env vehicle params (f110_set_env_params; last, so that every field above keeps its kernarg offset)
+    double *ptab;          // [kDynFields][E*A] the dynamics fields per car (k_agents<., PENV>), or null: a.pa[ag]
+    const double *prange;  // [A][2][kDynFields] (lo, hi) a resetting car redraws its row from, or null
+    uint64_t pseed;        // f110_set_param_randomization's seed
 };
 
 // RN(1 / lidar_max) in f32 for k_rays_fxs's obs division, or 0 (the IEEE

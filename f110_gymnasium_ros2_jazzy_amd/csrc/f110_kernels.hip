@@ -211,7 +211,11 @@ __device__ void handoff_chunks(const StepArgs &a, int g, const float *sx, const 
 // HMASK: the context keeps hand-off chunk masks (A >= 2 dividing 64): the block's new poses meet in
 // LDS after the update and each car's mask is written at the end; without it the update's stores
 // follow it directly (the single-agent form, one dependent chain less to schedule around a barrier).
-template <bool HMASK>
+// PENV: the context holds a per-car table of the dynamics fields (a.ptab, f110_set_env_params): the
+// car's row is loaded with the prologue and update_pose reads a local f110_params built from it
+// (width, length, lidar_max from a.pa[ag]); with a range table too (a.prange) a resetting car first
+// redraws its row (param_draw) and stores it.  Without PENV nothing of this is compiled in.
+template <bool HMASK, bool PENV>
 __global__ void __launch_bounds__(64) k_agents(StepArgs a) {
     const int g = blockIdx.x * 64 + threadIdx.x;
     const int EA = a.E * a.A;
@@ -226,8 +230,13 @@ __global__ void __launch_bounds__(64) k_agents(StepArgs a) {
     int cnt = 0, gate = 0;
     uint32_t episode = 0;
     uint64_t nstep = 0;
+    double pv[PENV ? kDynFields : 1] = {};  // the car's table row (padding threads read none)
     if (valid) {
         if (ag == 0) nstep = a.nstep[e];
+        if (PENV) {
+#pragma unroll
+            for (int k = 0; k < kDynFields; ++k) pv[k] = a.ptab[(size_t)k * EA + g];
+        }
 #pragma unroll
         for (int k = 0; k < 7; ++k) s[k] = a.st[(size_t)k * EA + g];
         b0 = a.sb[g];
@@ -368,9 +377,21 @@ __global__ void __launch_bounds__(64) k_agents(StepArgs a) {
         a.near_start[g] = 1;
         a.lap_times[g] = 0.0f;
         a.lap_counts[g] = 0.0f;
+        if (PENV && a.prange) {  // domain randomization: this episode's car, in force from the reset's own step
+            param_draw(a.pseed, genv, ag, a.mode == 1 ? 0ull : (uint64_t)episode + 1ull,
+                       a.prange + (size_t)ag * 2 * kDynFields, pv);
+#pragma unroll
+            for (int k = 0; k < kDynFields; ++k) a.ptab[(size_t)k * EA + g] = pv[k];
+        }
     }
     aphase(0);
-    update_pose(s, b0, b1, cnt, raw_steer, vel, a.pa[ag], a.dt, a.integrator, tab);  // RaceCar.params (per agent)
+    if (PENV) {
+        f110_params lp = a.pa[ag];  // width, length, lidar_max stay the agent's
+        __builtin_memcpy(&lp, pv, kDynFields * sizeof(double));  // the leading doubles (f110_device.h)
+        update_pose(s, b0, b1, cnt, raw_steer, vel, lp, a.dt, a.integrator, tab);
+    } else {
+        update_pose(s, b0, b1, cnt, raw_steer, vel, a.pa[ag], a.dt, a.integrator, tab);  // RaceCar.params (per agent)
+    }
     aphase(1);
     act = true;
     if (!HMASK) tail();
@@ -2165,10 +2186,17 @@ hipError_t launch_env_step(const StepArgs &a, const RayLaunch &r, hipStream_t s,
     hipError_t e;
     auto evk = [&](int i) -> hipEvent_t { return ev ? ev[i] : nullptr; };  // (start, stop) per kernel
     // 64-thread blocks: a few thousand cars must still spread over all CUs
-    if (a.hmask)
-        hipExtLaunchKernelGGL(k_agents<true>, dim3((EA + 63) / 64), dim3(64), 0, s, evk(0), evk(1), 0, a);
-    else
-        hipExtLaunchKernelGGL(k_agents<false>, dim3((EA + 63) / 64), dim3(64), 0, s, evk(0), evk(1), 0, a);
+    // (a context without a per-env table launches the table-free instantiations, as before there was one)
+    if (a.ptab) {
+        if (a.hmask)
+            hipExtLaunchKernelGGL((k_agents<true, true>), dim3((EA + 63) / 64), dim3(64), 0, s, evk(0), evk(1), 0, a);
+        else
+            hipExtLaunchKernelGGL((k_agents<false, true>), dim3((EA + 63) / 64), dim3(64), 0, s, evk(0), evk(1), 0, a);
+    } else if (a.hmask) {
+        hipExtLaunchKernelGGL((k_agents<true, false>), dim3((EA + 63) / 64), dim3(64), 0, s, evk(0), evk(1), 0, a);
+    } else {
+        hipExtLaunchKernelGGL((k_agents<false, false>), dim3((EA + 63) / 64), dim3(64), 0, s, evk(0), evk(1), 0, a);
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (r.gate_wait && (e = hipStreamWaitEvent(s, r.gate_wait, 0)) != hipSuccess) return e;
     const bool single = a.A == 1;

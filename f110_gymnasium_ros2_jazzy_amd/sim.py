@@ -35,6 +35,54 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _known_fields(d, what):
+    bad = [k for k in d if k not in _lib.PARAM_FIELDS]
+    if bad:
+        raise ValueError(f"{what}: unknown vehicle parameter {bad[0]!r} (known: {', '.join(_lib.PARAM_FIELDS)})")
+
+
+def env_param_rows(params: dict, agent_params: list, n_envs: int) -> np.ndarray:
+    """[E, A, 19] float64 rows of f110_params (f110_set_env_params' argument): the agents' params
+    with the given fields (scalar, [E] or [E, A]) laid over them.  Host only."""
+    _known_fields(params, "set_env_params")
+    E, A = int(n_envs), len(agent_params)
+    rows = np.empty((E, A, len(_lib.PARAM_FIELDS)), np.float64)
+    for i, k in enumerate(_lib.PARAM_FIELDS):
+        rows[:, :, i] = np.array([float(d[k]) for d in agent_params])[None, :]
+        if k in params:
+            v = np.asarray(params[k], dtype=np.float64)
+            if v.ndim == 1 and v.shape[0] == E:
+                v = v[:, None]
+            elif v.ndim not in (0, 2) or (v.ndim == 2 and v.shape != (E, A)):
+                raise ValueError(f"set_env_params: {k} must be a scalar, [{E}] or [{E}, {A}]; got {v.shape}")
+            rows[:, :, i] = v
+    return rows
+
+
+def param_range_rows(ranges, agent_params: list):
+    """(lo, hi) [A, 19] float64 rows of f110_params (f110_set_param_randomization's arguments) from
+    field -> (lo, hi), or one such dict per agent; fields left out get lo = hi = the agent's value.
+    Host only."""
+    A = len(agent_params)
+    per_agent = [ranges] * A if isinstance(ranges, dict) else list(ranges)
+    if len(per_agent) != A:
+        raise ValueError(f"param ranges: one dict, or one per agent ({A}); got {len(per_agent)}")
+    lo = np.empty((A, len(_lib.PARAM_FIELDS)), np.float64)
+    hi = np.empty_like(lo)
+    for a, (r, base) in enumerate(zip(per_agent, agent_params)):
+        _known_fields(r, "param ranges")
+        for i, k in enumerate(_lib.PARAM_FIELDS):
+            if k in r:
+                try:
+                    l, h = r[k]
+                except (TypeError, ValueError):
+                    raise ValueError(f"param ranges: {k} must be a (lo, hi) pair") from None
+                lo[a, i], hi[a, i] = float(l), float(h)
+            else:
+                lo[a, i] = hi[a, i] = float(base[k])
+    return lo, hi
+
+
 class BatchSim:
     """Batched simulator on one device.
 
@@ -64,6 +112,7 @@ class BatchSim:
             if hasattr(p, k):
                 setattr(p, k, float(v))
         self.params = p
+        self._agent_params = [p.as_dict() for _ in range(int(n_agents))]
         c = _lib.default_config()
         c.n_envs, c.n_agents, c.n_beams = int(n_envs), int(n_agents), int(num_beams)
         c.integrator, c.ego_idx, c.autoreset = int(integrator), int(ego_idx), int(bool(autoreset))
@@ -196,6 +245,56 @@ class BatchSim:
                 setattr(p, k, float(params[k]))
         _lib.check(self.L.f110_set_params(self.ctx, ctypes.byref(p), int(agent_idx), self._stream()),
                    "f110_set_params")
+        for i in range(self.A):  # the per-agent params as the context holds them (agent_params)
+            if agent_idx < 0 or i == agent_idx:
+                self._agent_params[i] = p.as_dict()
+
+    # ---- per-env vehicle params (f110_set_env_params) ---------------------
+    def agent_params(self) -> list:
+        """The per-agent params (one dict per agent): the create params, as update_params changed them."""
+        return [dict(d) for d in self._agent_params]
+
+    def set_env_params(self, params: dict | None):
+        """Vehicle dynamics that differ from env to env (f110_set_env_params).
+
+        params: field -> scalar, [E] or [E, A] array; fields left out keep the per-agent params
+        (agent_params).  Only the 16 dynamics fields (_lib.DYN_FIELDS) may differ from the agent's
+        value: width, length and lidar_max are refused by the library when they do.  ``None``
+        drops the table (and the randomization): every env drives the per-agent params again."""
+        if params is None:
+            _lib.check(self.L.f110_set_env_params(self.ctx, None, self._stream()), "f110_set_env_params")
+            return
+        rows = env_param_rows(params, self._agent_params, self.E)
+        _lib.check(self.L.f110_set_env_params(self.ctx, rows.ctypes.data_as(ctypes.POINTER(_lib.F110Params)),
+                                              self._stream()), "f110_set_env_params")
+
+    def env_params(self) -> dict:
+        """The params in force: field -> [E, A] float64 NumPy array (f110_get_env_params; the table
+        if one is set -- under randomization the cars drawn at each env's last reset -- else the
+        per-agent params for every env).  Waits for the current stream."""
+        rows = np.empty((self.E, self.A, len(_lib.PARAM_FIELDS)), np.float64)
+        _lib.check(self.L.f110_get_env_params(self.ctx, rows.ctypes.data_as(ctypes.POINTER(_lib.F110Params)),
+                                              self._stream()), "f110_get_env_params")
+        return {k: np.ascontiguousarray(rows[..., i]) for i, k in enumerate(_lib.PARAM_FIELDS)}
+
+    def set_param_randomization(self, ranges, seed: int | None = None):
+        """Domain randomization on the device (f110_set_param_randomization): every car that resets
+        (reset(), or an autoreset inside step / step_n / a captured graph) redraws its dynamics,
+        field = lo + u (hi - lo), u uniform in [0, 1), keyed by (seed, global env id, agent, field,
+        episode); the other cars keep theirs.
+
+        ranges: field -> (lo, hi), or one such dict per agent; fields left out stay at the agent's
+        value (lo = hi).  ``None`` turns it off (the table stays as it stands).  seed: default the
+        context's seed."""
+        if ranges is None:
+            _lib.check(self.L.f110_set_param_randomization(self.ctx, None, None, 0, self._stream()),
+                       "f110_set_param_randomization")
+            return
+        lo, hi = param_range_rows(ranges, self._agent_params)
+        PP = ctypes.POINTER(_lib.F110Params)
+        sd = (int(self.cfg.seed) if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
+        _lib.check(self.L.f110_set_param_randomization(self.ctx, lo.ctypes.data_as(PP), hi.ctypes.data_as(PP), sd,
+                                                       self._stream()), "f110_set_param_randomization")
 
     def set_scan_noise(self, noise):
         """Caller-supplied scan noise for the following step/reset calls

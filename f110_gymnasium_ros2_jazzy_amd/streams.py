@@ -27,6 +27,7 @@ from __future__ import annotations
 import collections
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -198,6 +199,39 @@ class StreamShards:
             if rc < 0:
                 _lib.check(rc, "f110_step")
         self._hold(a)
+
+    # ---- per-env vehicle params: each sub-shard gets its rows (BatchSim.set_env_params) ----
+    def set_env_params(self, params: dict | None):
+        """BatchSim.set_env_params for the E envs: [E] / [E, A] arrays are split over the sub-shards."""
+        self._fork()
+        for s, sm in enumerate(self.sims):
+            part = params
+            if params is not None:
+                part = {}
+                for k, v in params.items():
+                    v = np.asarray(v, dtype=np.float64)
+                    if v.ndim >= 1 and v.shape[0] != self.E:
+                        raise ValueError(f"set_env_params: {k} must be a scalar, [{self.E}] or "
+                                         f"[{self.E}, {self.n_agents}]; got {v.shape}")
+                    part[k] = v if v.ndim == 0 else v[self._sl[s]]
+            with torch.cuda.stream(self.streams[s]):
+                sm.set_env_params(part)
+
+    def set_param_randomization(self, ranges, seed: int | None = None):
+        """BatchSim.set_param_randomization on every sub-shard: the draws are keyed by global env id,
+        so the cars are those of one E-env context."""
+        self._fork()
+        for s, sm in enumerate(self.sims):
+            with torch.cuda.stream(self.streams[s]):
+                sm.set_param_randomization(ranges, seed=seed)
+
+    def env_params(self) -> dict:
+        """field -> [E, A] float64 NumPy array of the params in force (BatchSim.env_params)."""
+        parts = []
+        for s, sm in enumerate(self.sims):
+            with torch.cuda.stream(self.streams[s]):
+                parts.append(sm.env_params())
+        return {k: np.concatenate([p[k] for p in parts], 0) for k in parts[0]}
 
     def join(self):
         cur = self._caller()

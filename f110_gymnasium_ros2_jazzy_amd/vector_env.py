@@ -23,6 +23,12 @@ t-1 (or of the reset).  ``step`` then takes the other agents' actions
 ([N, 2] for two agents) and ``infos["opponent_actions"]`` shows the
 opponent's.
 
+``param_ranges`` ({field: (lo, hi)}, or one such dict per agent) turns on the
+device's domain randomization of the vehicle dynamics: every reset and
+autoreset redraws the resetting cars' friction, mass, ... from the ranges
+(keyed by global env id and episode); ``env.sim.env_params()`` shows the cars
+in force.  The infos are unchanged.
+
 Multi-GPU: give each rank its block of envs (distributed.shard_range) and
 ``env_offset`` = the block's first global id; RNG streams are keyed by global
 env id, so results do not depend on the GPU count.
@@ -34,7 +40,7 @@ import torch
 
 from .f110_env import DEFAULT_PARAMS, _box
 from .maps import centerline_spawns, load_map
-from .sim import BatchSim
+from .sim import BatchSim, param_range_rows
 
 
 class F110VectorEnv:
@@ -44,10 +50,13 @@ class F110VectorEnv:
                  params: dict | None = None, seed: int = 42, timestep: float = 0.01, device=0,
                  spawn_poses: np.ndarray | None = None, noise_std: float = 0.01, env_offset: int = 0,
                  ego_idx: int = 0, as_numpy: bool = False, autoreset: bool = True, opponent: str | None = None,
-                 opponent_idx: int = 1, reward_fn=None, infos: str = "full", options_dtype=np.float32, **kwargs):
+                 opponent_idx: int = 1, reward_fn=None, infos: str = "full", options_dtype=np.float32,
+                 param_ranges=None, param_seed: int | None = None, **kwargs):
         self.num_envs = int(num_envs)
         self.num_agents = int(num_agents)
         self.params = dict(params or DEFAULT_PARAMS)
+        if param_ranges is not None:  # an unknown field: ValueError before anything is built
+            param_range_rows(param_ranges, [{**DEFAULT_PARAMS, **self.params}] * self.num_agents)
         self.timestep = timestep
         self.as_numpy = as_numpy
         self.track = load_map(map, map_ext)
@@ -58,6 +67,10 @@ class F110VectorEnv:
                             device=device, seed=seed, timestep=timestep, ego_idx=ego_idx, noise_std=noise_std,
                             autoreset=autoreset, spawn_poses=self.spawn_poses, env_offset=env_offset, **kwargs)
         self.device = self.sim.device
+        # domain randomization (BatchSim.set_param_randomization), on before the first reset: every
+        # reset and device autoreset redraws the resetting cars' dynamics; sim.env_params() shows them
+        if param_ranges is not None:
+            self.sim.set_param_randomization(param_ranges, seed=param_seed)
         # F110Env.reset computes start_rot in the dtype of its options
         # (f110_env.py:448-451): autoresets and option-less resets follow
         # options_dtype (train_ddpg passes float32 poses); an explicit

@@ -172,6 +172,49 @@ F110_API int f110_step_n(f110_ctx *ctx, const void *actions, int32_t actions_dty
  * pointer; the call is ordered on `stream` and returns when it is applied. */
 F110_API int f110_set_params(f110_ctx *ctx, const f110_params *params, int32_t agent_idx, void *stream);
 
+/* ---- per-env vehicle params (no reference counterpart: the reference has one
+ * params dict per car) ------------------------------------------------------
+ * The 16 dynamics fields (mu .. v_max, the leading doubles of f110_params) may
+ * differ from env to env: the context then keeps a device table of them per
+ * car, which the cars' update_pose (pid, clips, RK4 / Euler, clamps) reads
+ * instead of the per-agent params.  width, length and lidar_max do NOT vary
+ * per env: the car boxes (agent ray_cast, GJK), the TTC side distances and the
+ * obs scale keep reading the per-agent / f110_create params, and a row whose
+ * width, length or lidar_max differs from its agent's current f110_set_params
+ * value is refused.
+ * Precedence: with a table set, the table's dynamics win.  f110_set_params
+ * still updates the per-agent params (the boxes, and the dynamics the context
+ * returns to when the table is dropped) and does not touch the table.
+ *
+ * f110_set_env_params: params is a HOST array [n_envs][n_agents]; NULL drops
+ * the table (and the randomization with it): back to the per-agent params.
+ * F110_E_INVALID, with the field named in f110_last_error, for a non-finite
+ * value or a differing width / length / lidar_max; the table is then
+ * unchanged.  Ordered on `stream`, applied when the call returns. */
+F110_API int f110_set_env_params(f110_ctx *ctx, const f110_params *params, void *stream);
+/* The params in force, out = HOST [n_envs][n_agents]: the table's rows if one
+ * is set (under randomization, the cars drawn at each env's last reset), else
+ * the per-agent params for every env.  Waits for `stream`. */
+F110_API int f110_get_env_params(f110_ctx *ctx, f110_params *out, void *stream);
+/* Domain randomization on the device: from now on a car that resets -- in
+ * f110_reset (its masked envs) or by autoreset inside f110_step / f110_step_n,
+ * a captured graph included -- redraws its 16 dynamics fields before the
+ * reset's own zero-action step, field = lo + u * (hi - lo) with u = r * 2^-32
+ * in [0, 1) for a 32-bit Philox4x32-10 draw r (hi == lo gives exactly lo), and
+ * stores the row in the table; cars that do not reset keep theirs.  The draw
+ * is keyed by (seed, global env id = env_offset + env, agent, field, episode):
+ * episode is 0 for f110_reset and counts the env's autoresets since, so an
+ * explicit reset reproduces the same cars whatever ran before it, and a shard
+ * of the envs (env_offset) draws what the whole batch draws for them.
+ * lo, hi: HOST [n_agents]; NULL, NULL turns it off and keeps the table as it
+ * stands.  Allocates the table if there is none, filled with the per-agent
+ * params.  F110_E_INVALID (field named in f110_last_error, checked before any
+ * device call) for a non-finite value, lo > hi, or a width / length /
+ * lidar_max of lo or hi that differs from the agent's.  Ordered on `stream`,
+ * applied when the call returns. */
+F110_API int f110_set_param_randomization(f110_ctx *ctx, const f110_params *lo, const f110_params *hi, uint64_t seed,
+                                          void *stream);
+
 /* Scan-noise source of the following f110_step / f110_reset calls.
  * noise: device [n_envs][n_beams] f64, or NULL for the built-in stream.
  * The reference draws the noise as rng.normal(0, std_dev, num_beams) from a

@@ -242,6 +242,18 @@ F110_API void f110_host_np_sincosf(const float *x, int64_t n, int32_t cos_op, fl
 F110_API void f110_host_window_ranges(double yaw, double fov, int32_t n_beams, double center, double half,
                                       int32_t ranges_out[4]);
 
+/* f110_set_param_randomization's validation of lo / hi [n_agents] against the
+ * agents' params [n_agents], without a context: F110_OK, or F110_E_INVALID with
+ * the field named in f110_last_error (non-finite, lo > hi, width / length /
+ * lidar_max not the agent's).  Host test hook. */
+F110_API int f110_host_check_param_ranges(const f110_params *lo, const f110_params *hi,
+                                          const f110_params *agent_params, int32_t n_agents);
+/* The row a resetting car draws (the device's param_draw on the host): car
+ * `agent` of global env `env` in episode `episode` under (lo, hi, seed); out's
+ * width / length / lidar_max are lo's.  Host test hook. */
+F110_API int f110_host_param_draw(uint64_t seed, int64_t env, int32_t agent, uint64_t episode, const f110_params *lo,
+                                  const f110_params *hi, f110_params *out);
+
 #ifdef __cplusplus
 }
 #endif
