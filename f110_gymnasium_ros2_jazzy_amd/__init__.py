@@ -4,6 +4,7 @@ Public surface:
   BatchSim        n_envs x n_agents cars on one GPU (sim.py)
   F110Env         drop-in for f110_gym.envs.F110Env (f110_env.py)
   F110VectorEnv   Gymnasium-style vector env (vector_env.py)
+  EpisodeStats    per-env episode returns / lengths and totals on the device (episode.py)
   load_map        map yaml + image -> TrackMap with exact EDT (maps.py)
 """
 from .maps import TrackMap, load_map, centerline_spawns  # noqa: F401
@@ -22,4 +23,7 @@ def __getattr__(name):  # lazy: torch-backed classes
     if name == "F110VectorEnv":
         from .vector_env import F110VectorEnv
         return F110VectorEnv
+    if name == "EpisodeStats":
+        from .episode import EpisodeStats
+        return EpisodeStats
     raise AttributeError(name)

@@ -57,6 +57,18 @@ class F110WgradOp(ctypes.Structure):  # f110_wgrad_op
                [(n, ctypes.c_int32) for n in ("N", "KX", "ldg", "ldx", "ldw")]
 
 
+class F110EpisodeState(ctypes.Structure):  # f110_episode_state (zero bytes = fresh)
+    _fields_ = [("ret", ctypes.c_double), ("len", ctypes.c_int32), ("closed", ctypes.c_int32)]
+
+
+class F110EpisodeTotals(ctypes.Structure):  # f110_episode_totals (zero bytes = fresh)
+    _fields_ = [(n, ctypes.c_int64) for n in ("episodes", "terminated", "truncated", "length_sum")] + \
+               [(n, ctypes.c_double) for n in ("return_sum", "return_min", "return_max")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class F110RayKnobs(ctypes.Structure):  # f110_ray_knobs (include/f110_debug.h)
     _fields_ = [(n, ctypes.c_int32) for n in
                 ("kernel", "lanes", "refill", "fxs_lds", "count_slots", "wtrace", "heavy_list", "heavy_on",
@@ -74,6 +86,8 @@ RAY_FAMILIES = ("tiled_flat", "tiled_chunked", "fx", "fxn_clamped", "fxn_padded"
 RAY_TABLES = ("tiled", "rowmajor", "padded")  # F110_TABLE_*
 
 REWARD_STATE_BYTES = 8 * 12 + 4 * 4   # f110_reward_state
+EPISODE_STATE_BYTES = 16              # f110_episode_state
+EPISODE_TOTALS_BYTES = 56             # f110_episode_totals
 
 PARAM_FIELDS = tuple(n for n, _ in F110Params._fields_)
 DYN_FIELDS = PARAM_FIELDS[:16]  # the fields a context may hold per env (f110_set_env_params)
@@ -97,6 +111,8 @@ EXPORTS = [
     "f110_host_ray_plan", "f110_host_ray_rules",
     "f110_set_env_params", "f110_get_env_params", "f110_set_param_randomization",
     "f110_host_check_param_ranges", "f110_host_param_draw",
+    "f110_set_episode_limits", "f110_host_check_episode_limits",
+    "f110_episode_scratch_bytes", "f110_episode_stats", "f110_host_episode_stats",
     "f110_dynamics_ks_batch", "f110_collision_batch", "f110_collision_multiple", "f110_adam_step", "f110_ddpg_scratch_floats", "f110_ddpg_actor_head", "f110_ddpg_actor_explore",
     "f110_ddpg_actor_head_bwd", "f110_ddpg_td_target", "f110_ddpg_critic_loss", "f110_ddpg_critic_loss_bwd",
     "f110_ddpg_q_mean", "f110_ddpg_q_mean_bwd", "f110_ddpg_relu_bwd_scratch_floats", "f110_ddpg_relu_bwd",
@@ -237,6 +253,11 @@ def load(build_if_missing: bool = True):
     L.f110_set_param_randomization.argtypes = [_P, PP, PP, u64, _P]
     L.f110_host_check_param_ranges.argtypes = [PP, PP, PP, i32]
     L.f110_host_param_draw.argtypes = [u64, i64, i32, u64, PP, PP, PP]
+    L.f110_set_episode_limits.argtypes = [_P, i64, ctypes.c_double, i32, _P, _P]
+    L.f110_host_check_episode_limits.argtypes = [i64, ctypes.c_double, i32]
+    L.f110_episode_scratch_bytes.argtypes = [i64]
+    L.f110_episode_stats.argtypes = [_P, _P, _P, _P, i64, _P, _P, _P, _P, _P, _P, _P]
+    L.f110_host_episode_stats.argtypes = [_P, _P, _P, _P, i64, _P, _P, _P, _P, _P]
     L.f110_adam_step.argtypes = [_P, _P, _P, _P, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                  ctypes.c_double, _P, _P, ctypes.c_double, _P]
     f32 = ctypes.c_float
@@ -267,11 +288,13 @@ def load(build_if_missing: bool = True):
                         "f110_host_np_sincosf", "f110_host_sincos", "f110_host_sincos_series",
                         "f110_host_tables", "f110_host_window_ranges", "f110_track_arrays",
                         "f110_default_reward_params", "f110_ddpg_scratch_floats",
-                        "f110_ddpg_relu_bwd_scratch_floats", "f110_learner_wgrad_scratch_floats"):
+                        "f110_ddpg_relu_bwd_scratch_floats", "f110_learner_wgrad_scratch_floats",
+                        "f110_episode_scratch_bytes"):
             getattr(L, name).restype = ctypes.c_int
     L.f110_ddpg_scratch_floats.restype = i64
     L.f110_ddpg_relu_bwd_scratch_floats.restype = i64
     L.f110_learner_wgrad_scratch_floats.restype = i64
+    L.f110_episode_scratch_bytes.restype = i64
     if L.f110_abi_version() != ABI_VERSION and not (alternate and L.f110_abi_version() == 2):
         raise F110Error(f"libf110.so ABI version mismatch ({L.f110_abi_version()} != {ABI_VERSION})")
     _lib = L

@@ -107,6 +107,12 @@ struct f110_ctx {
     double *prange = nullptr;  // [A][2][kDynFields]
     bool ptab_on = false, prange_on = false;  // the steps read the table / redraw rows at resets
     uint64_t pseed = 0;
+    // episode limits (f110_set_episode_limits); stall: [E], allocated by the first stall limit
+    int64_t max_steps = 0;
+    double stall_speed = 0.0;
+    int32_t stall_steps = 0;
+    int32_t *stall = nullptr;
+    uint8_t *truncated = nullptr;  // caller-owned
 
     hipEvent_t *next_prof_events() {
         if (prof_n >= prof_max) return nullptr;
@@ -964,6 +970,13 @@ static StepArgs make_step_args(f110_ctx *c, const f110_outputs *out) {
         a.prange = c->prange_on ? c->prange : nullptr;
         a.pseed = c->pseed;
     }
+    if (c->max_steps || c->stall_steps) {
+        a.max_steps = c->max_steps;
+        a.stall_speed = c->stall_speed;
+        a.stall_steps = c->stall_steps;
+        a.stall = c->stall_steps ? c->stall : nullptr;
+        a.truncated = c->truncated;
+    }
     return a;
 }
 
@@ -1466,6 +1479,100 @@ extern "C" int f110_set_param_randomization(f110_ctx *ctx, const f110_params *lo
     HIP_TRY(hipStreamSynchronize(s));
     ctx->pseed = seed;
     ctx->ptab_on = ctx->prange_on = true;
+    return F110_OK;
+}
+
+// --------------------------------------------------------- episode limits --
+static int check_episode_limits(const char *who, int64_t max_steps, double stall_speed, int32_t stall_steps) {
+    if (max_steps < 0) return fail(F110_E_INVALID, std::string(who) + ": max_steps is negative");
+    if (stall_steps < 0) return fail(F110_E_INVALID, std::string(who) + ": stall_steps is negative");
+    if (!std::isfinite(stall_speed)) return fail(F110_E_INVALID, std::string(who) + ": stall_speed is not finite");
+    if (stall_speed < 0) return fail(F110_E_INVALID, std::string(who) + ": stall_speed is negative");
+    return F110_OK;
+}
+
+extern "C" int f110_host_check_episode_limits(int64_t max_steps, double stall_speed, int32_t stall_steps) {
+    return check_episode_limits("f110_host_check_episode_limits", max_steps, stall_speed, stall_steps);
+}
+
+extern "C" int f110_set_episode_limits(f110_ctx *ctx, int64_t max_steps, double stall_speed, int32_t stall_steps,
+                                       uint8_t *truncated, void *stream) {
+    if (!ctx) return fail(F110_E_INVALID, "f110_set_episode_limits: null context");
+    const int rc = check_episode_limits("f110_set_episode_limits", max_steps, stall_speed, stall_steps);
+    if (rc != F110_OK) return rc;  // (before any device call)
+    const bool on = max_steps || stall_steps;
+    if (stall_steps && !ctx->stall_steps) {  // the stall limit comes on: every env's counter starts at 0
+        if (use_device(ctx) != F110_OK) return F110_E_HIP;
+        hipStream_t s = (hipStream_t)stream;
+        if (!ctx->stall) {
+            hipError_t e = ctx->alloc(&ctx->stall, (size_t)ctx->cfg.n_envs);  // (zero-filled)
+            if (e != hipSuccess) return fail(F110_E_ALLOC, std::string("hipMalloc stall: ") + hipGetErrorString(e));
+        } else {
+            HIP_TRY(hipMemsetAsync(ctx->stall, 0, (size_t)ctx->cfg.n_envs * sizeof(int32_t), s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    ctx->max_steps = max_steps;
+    ctx->stall_speed = stall_speed;
+    ctx->stall_steps = stall_steps;
+    ctx->truncated = on ? truncated : nullptr;
+    return F110_OK;
+}
+
+// ----------------------------------------------------- episode statistics --
+extern "C" int64_t f110_episode_scratch_bytes(int64_t n_envs) {
+    return (n_envs > 0 ? episode_blocks(n_envs) : 1) * (int64_t)sizeof(EpisodePart);
+}
+
+static int check_episode_args(const char *who, const double *rewards, const uint8_t *terminated,
+                              const uint8_t *was_reset, int64_t n_envs, const f110_episode_state *state,
+                              const f110_episode_totals *totals) {
+    if (!rewards || !terminated || !was_reset || !state || !totals)
+        return fail(F110_E_INVALID, std::string(who) + ": null argument");
+    if (n_envs < 0 || episode_blocks(n_envs) > 0x7fffffff) return fail(F110_E_INVALID, std::string(who) + ": bad n_envs");
+    return F110_OK;
+}
+
+extern "C" int f110_episode_stats(const double *rewards, const uint8_t *terminated, const uint8_t *truncated,
+                                  const uint8_t *was_reset, int64_t n_envs, f110_episode_state *state,
+                                  double *last_return, int32_t *last_length, uint8_t *finished,
+                                  f110_episode_totals *totals, void *scratch, void *stream) {
+    const int rc = check_episode_args("f110_episode_stats", rewards, terminated, was_reset, n_envs, state, totals);
+    if (rc != F110_OK) return rc;
+    if (!scratch) return fail(F110_E_INVALID, "f110_episode_stats: null scratch");
+    EpisodeArgs a{};
+    a.rewards = rewards;
+    a.terminated = terminated;
+    a.truncated = truncated;
+    a.was_reset = was_reset;
+    a.E = n_envs;
+    a.state = state;
+    a.last_return = last_return;
+    a.last_length = last_length;
+    a.finished = finished;
+    a.totals = totals;
+    a.part = static_cast<EpisodePart *>(scratch);
+    HIP_TRY(launch_episode_stats(a, (hipStream_t)stream));
+    return F110_OK;
+}
+
+extern "C" int f110_host_episode_stats(const double *rewards, const uint8_t *terminated, const uint8_t *truncated,
+                                       const uint8_t *was_reset, int64_t n_envs, f110_episode_state *state,
+                                       double *last_return, int32_t *last_length, uint8_t *finished,
+                                       f110_episode_totals *totals) {
+    const int rc = check_episode_args("f110_host_episode_stats", rewards, terminated, was_reset, n_envs, state, totals);
+    if (rc != F110_OK) return rc;
+    EpisodePart call = {0, 0, 0, 0, 0.0, 0.0, 0.0};
+    for (int64_t e = 0; e < n_envs; ++e) {
+        const int code = episode_update(rewards[e], terminated[e], truncated ? truncated[e] : 0, was_reset[e], state[e]);
+        if (finished) finished[e] = code ? 1 : 0;
+        if (code) {
+            if (last_return) last_return[e] = state[e].ret;
+            if (last_length) last_length[e] = state[e].len;
+        }
+        episode_merge(call, episode_part(code, state[e]));
+    }
+    episode_totals_add(*totals, call);
     return F110_OK;
 }
 

@@ -1304,4 +1304,76 @@ F110_HD void param_draw(uint64_t seed, uint64_t env, int agent, uint64_t episode
     }
 }
 
+// ------------------------------------------------------- episode limits --
+// f110_set_episode_limits' flag for an env that did not terminate in the step: n = its steps since
+// the reset, s = its stall counter after this step's update (include/f110.h).
+F110_HD uint8_t truncation_code(uint64_t n, int32_t s, int64_t max_steps, int32_t stall_steps) {
+    if (max_steps && n >= (uint64_t)max_steps) return 1;
+    if (stall_steps && s >= stall_steps) return 2;
+    return 0;
+}
+
+// --------------------------------------------------- episode statistics --
+// One env's row of f110_episode_stats (the semantics of include/f110.h; k_episode and
+// f110_host_episode_stats both call it).  Returns 0: the env does not finish, 1: it finishes
+// terminated, 2: truncated; in the last two st.ret / st.len are the episode's return and length.
+F110_HD int episode_update(double reward, int term, int trunc, int was_reset, f110_episode_state &st) {
+    if (was_reset) {
+        st.ret = 0.0;
+        st.len = 0;
+        st.closed = 0;
+        return 0;
+    }
+    if (st.closed) return 0;
+    st.ret += reward;
+    st.len += 1;
+    if (!(term || trunc)) return 0;
+    st.closed = 1;
+    return term ? 1 : 2;
+}
+
+// The envs finishing in one call (or one block's, or one env's share of them): what the totals add.
+// n == 0: empty (mn / mx unused).
+struct EpisodePart {
+    int64_t n, n_term, n_trunc, len;
+    double sum, mn, mx;
+};
+
+F110_HD EpisodePart episode_part(int code, const f110_episode_state &st) {
+    EpisodePart p = {0, 0, 0, 0, 0.0, 0.0, 0.0};
+    if (code) {
+        p.n = 1;
+        p.n_term = code == 1;
+        p.n_trunc = code == 2;
+        p.len = st.len;
+        p.sum = p.mn = p.mx = st.ret;
+    }
+    return p;
+}
+
+// a += b, in this operand order (the fixed summation order is built from it)
+F110_HD void episode_merge(EpisodePart &a, const EpisodePart &b) {
+    if (b.n) {
+        a.mn = a.n ? (b.mn < a.mn ? b.mn : a.mn) : b.mn;
+        a.mx = a.n ? (b.mx > a.mx ? b.mx : a.mx) : b.mx;
+    }
+    a.n += b.n;
+    a.n_term += b.n_term;
+    a.n_trunc += b.n_trunc;
+    a.len += b.len;
+    a.sum += b.sum;
+}
+
+F110_HD void episode_totals_add(f110_episode_totals &t, const EpisodePart &b) {
+    EpisodePart a = {t.episodes, t.terminated, t.truncated, t.length_sum, t.return_sum, t.return_min, t.return_max};
+    episode_merge(a, b);
+    t.episodes = a.n;
+    t.terminated = a.n_term;
+    t.truncated = a.n_trunc;
+    t.length_sum = a.len;
+    t.return_sum = a.sum;
+    t.return_min = a.mn;
+    t.return_max = a.mx;
+}
+
 }  // namespace f110

@@ -85,6 +85,13 @@ struct StepArgs {
     double *ptab;          // [kDynFields][E*A] the dynamics fields per car (k_agents<., PENV>), or null: a.pa[ag]
     const double *prange;  // [A][2][kDynFields] (lo, hi) a resetting car redraws its row from, or null
     uint64_t pseed;        // f110_set_param_randomization's seed
+    // episode limits (f110_set_episode_limits; appended for the same reason).  Both limits 0: the post
+    // kernels' epilogue is the limit-free one (no load or store of the fields below)
+    int64_t max_steps;     // time limit in steps since the reset (a.nstep's count), 0 = none
+    double stall_speed;    // |ego v| below this counts as standing
+    int32_t stall_steps;   // standing steps in a row that truncate, 0 = none
+    int32_t *stall;        // [E] the stall counters (set when stall_steps != 0)
+    uint8_t *truncated;    // [E] the caller's flag buffer, or null
 };
 
 // RN(1 / lidar_max) in f32 for k_rays_fxs's obs division, or 0 (the IEEE
@@ -289,6 +296,22 @@ struct RewardArgs {
     const uint8_t *reset_mask;
     double *rewards;
 };
+
+// ---- episode statistics (f110_episode.hip) ---------------------------------
+constexpr int kEpisodeBlock = 256;  // envs per block of k_episode (the documented reduction order, f110.h)
+struct EpisodeArgs {
+    const double *rewards;
+    const uint8_t *terminated, *truncated, *was_reset;  // truncated may be null
+    int64_t E;
+    f110_episode_state *state;
+    double *last_return;    // the three per-env outputs may be null
+    int32_t *last_length;
+    uint8_t *finished;
+    f110_episode_totals *totals;
+    EpisodePart *part;      // [episode_blocks(E)] block partials (the caller's scratch)
+};
+inline int64_t episode_blocks(int64_t E) { return (E + kEpisodeBlock - 1) / kEpisodeBlock; }
+hipError_t launch_episode_stats(const EpisodeArgs &a, hipStream_t s);
 
 // ---- prioritized replay (f110_replay.hip) ---------------------------------
 constexpr int kTieCap = 4096;        // keys equal to the selection threshold kept for the tie break

@@ -1748,7 +1748,12 @@ struct EpiEnv {  // per env
     double tprev, ct, st;
     uint64_t nstep;
     uint32_t episode;
+    int32_t stall;  // the stall counter (f110_set_episode_limits with a stall limit; else unused)
 };
+
+// LIM (the post kernels, their epilogue and its loads): an episode limit is on
+// (f110_set_episode_limits).  Without it nothing of the limits is compiled in: a context with both
+// limits 0 launches the limit-free instantiations, the kernels from before there were limits.
 
 __device__ __forceinline__ void epilogue_load_car(const StepArgs &a, int g, EpiCar &c) {
     const int EA = a.E * a.A;
@@ -1759,6 +1764,7 @@ __device__ __forceinline__ void epilogue_load_car(const StepArgs &a, int g, EpiC
     c.lt = a.lap_times[g];
 }
 
+template <bool LIM>
 __device__ __forceinline__ void epilogue_load_env(const StepArgs &a, int e, EpiEnv &v) {
     v.tprev = a.sim_time[e];
     v.ct = a.start_rot[e];  // cos(-th), sin(-th) of the ego start yaw
@@ -1766,12 +1772,15 @@ __device__ __forceinline__ void epilogue_load_env(const StepArgs &a, int e, EpiE
     v.nstep = a.noise_step[e];  // written by this step's k_agents
     const uint32_t ep = a.episode[e];  // (loaded whatever the mode: one round trip with the others)
     v.episode = a.mode == 0 ? ep : 0u;
+    v.stall = (LIM && a.stall_steps) ? a.stall[e] : 0;  // with the others: no dependent round trip
 }
 
 // stl: post-TTC state rows of its A agents (x at [i*stride], y at
-// [i*stride + 1]); col: collision flags; cars / env: the prefetched inputs.
+// [i*stride + 1]); col: collision flags; cars / env: the prefetched inputs;
+// vego: the ego's post-TTC state[3] (read only under a stall limit).
+template <bool LIM>
 __device__ void env_epilogue(const StepArgs &a, int e, const double *stl, int stride, const int32_t *col,
-                             int do_reset, const EpiEnv &v, const EpiCar *cars) {
+                             int do_reset, const EpiEnv &v, const EpiCar *cars, double vego) {
     const int A = a.A;
     const double tnow = (do_reset ? 0.0 : v.tprev) + a.dt;
     a.sim_time[e] = tnow;
@@ -1811,7 +1820,22 @@ __device__ void env_epilogue(const StepArgs &a, int e, const double *stl, int st
     if (a.out.terminated) a.out.terminated[e] = term ? 1 : 0;
     if (a.out.was_reset) a.out.was_reset[e] = (uint8_t)do_reset;
     if (a.out.sim_time) a.out.sim_time[e] = tnow;
-    a.pending[e] = (a.autoreset && term) ? 1 : 0;
+    // episode limits (f110_set_episode_limits): n = v.nstep, this step's noise counter, is the steps
+    // since the env's reset on every path (0 in the reset's own step: k_agents, f110_reset's masked
+    // envs and autoresets alike; + 1 per step below; an unmasked env of a masked reset is not here)
+    bool trunc = false;
+    if (LIM) {
+        int32_t s = 0;
+        if (a.stall_steps) {
+            // (saturating: without autoreset a standing env counts on for as long as it is stepped)
+            s = do_reset ? 0 : (fabs(vego) < a.stall_speed ? (v.stall < INT32_MAX ? v.stall + 1 : v.stall) : 0);
+            a.stall[e] = s;
+        }
+        const uint8_t code = (term || do_reset) ? (uint8_t)0 : truncation_code(v.nstep, s, a.max_steps, a.stall_steps);
+        if (a.truncated) a.truncated[e] = code;
+        trunc = code != 0;
+    }
+    a.pending[e] = (a.autoreset && (term || trunc)) ? 1 : 0;
     // autoreset spawn draws count episodes from the env's last explicit reset, so a
     // reset replays the same trajectory whatever ran before it (the bench's
     // trajectory digest compares N = 1 and N > 1 runs after a clock ramp)
@@ -1823,6 +1847,7 @@ __device__ void env_epilogue(const StepArgs &a, int e, const double *stl, int st
 // k_post_single: single-agent envs after the FUSED ray kernel, one thread per
 // env: the TTC response (RaceCar.check_ttc, base_classes.py:246-249), the
 // pose part of the observation, collisions and the env epilogue.
+template <bool LIM>
 __global__ void __launch_bounds__(64) k_post_single(StepArgs a) {
     reset_next_heavy(a);
     const int e = blockIdx.x * 64 + threadIdx.x;
@@ -1834,10 +1859,11 @@ __global__ void __launch_bounds__(64) k_post_single(StepArgs a) {
     double yaw = a.st[(size_t)4 * EA + e];
     int32_t col = a.ttc_hit[e];
     const int do_reset = a.reset_flag[e];
+    const double vego = (LIM && a.stall_steps) ? a.st[(size_t)3 * EA + e] : 0.0;  // (a stall limit only)
     EpiCar car;
     EpiEnv env;
     epilogue_load_car(a, e, car);
-    epilogue_load_env(a, e, env);
+    epilogue_load_env<LIM>(a, e, env);
     if (col) {  // state[3:] = 0 (yaw included)
 #pragma unroll
         for (int k = 3; k < 7; ++k) a.st[(size_t)k * EA + e] = 0.0;
@@ -1856,7 +1882,7 @@ __global__ void __launch_bounds__(64) k_post_single(StepArgs a) {
         }
     }
     if (a.out.collisions) a.out.collisions[e] = (uint8_t)col;
-    env_epilogue(a, e, stl, 2, &col, do_reset, env, &car);
+    env_epilogue<LIM>(a, e, stl, 2, &col, do_reset, env, &car, col ? 0.0 : vego);
 }
 
 // LDS hand-off between the lanes of ONE wave (no workgroup barrier).
@@ -1900,6 +1926,7 @@ __device__ __forceinline__ int pass_beams(const MultiShared &sh, int pr) {
 }
 
 
+template <bool LIM>
 __global__ void __launch_bounds__(kMultiBlock, 6) k_post_multi(StepArgs a) {
     reset_next_heavy(a);
     __shared__ MultiShared sh;
@@ -1941,7 +1968,7 @@ __global__ void __launch_bounds__(kMultiBlock, 6) k_post_multi(StepArgs a) {
     }
     if (tid == 0) {
         sh.do_reset = a.reset_flag[e];
-        epilogue_load_env(a, e, sh.epe);
+        epilogue_load_env<LIM>(a, e, sh.epe);
     }
     __syncthreads();
     phase(0);
@@ -2082,7 +2109,7 @@ __global__ void __launch_bounds__(kMultiBlock, 6) k_post_multi(StepArgs a) {
         o[3] = sh.col[tid] ? 1.0f : 0.0f;
     }
     if (a.out.collisions && tid < A) a.out.collisions[(size_t)e * A + tid] = (uint8_t)sh.col[tid];
-    if (tid == 0) env_epilogue(a, e, &sh.stl[0][0], 7, sh.col, sh.do_reset, sh.epe, sh.epi);
+    if (tid == 0) env_epilogue<LIM>(a, e, &sh.stl[0][0], 7, sh.col, sh.do_reset, sh.epe, sh.epi, LIM ? sh.stl[a.ego][3] : 0.0);
 #ifdef F110_POST_PHASES
     phase(3);
     if (tid == 0) atomicAdd(a.ctr + (size_t)(e % kCtrSlots) * kCtrStride + 12, 1ull);
@@ -2294,12 +2321,19 @@ hipError_t launch_env_step(const StepArgs &a, const RayLaunch &r, hipStream_t s,
         return e;
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (r.gate_record && (e = hipEventRecord(r.gate_record, s)) != hipSuccess) return e;
-    if (single)
-        hipExtLaunchKernelGGL(k_post_single, dim3((a.E + 63) / 64), dim3(64), 0, s, evk(4), evk(5), 0, a);
-    else {
+    const bool lim = a.max_steps != 0 || a.stall_steps != 0;  // f110_set_episode_limits: the <LIM> post kernels
+    if (single) {
+        if (lim)
+            hipExtLaunchKernelGGL(k_post_single<true>, dim3((a.E + 63) / 64), dim3(64), 0, s, evk(4), evk(5), 0, a);
+        else
+            hipExtLaunchKernelGGL(k_post_single<false>, dim3((a.E + 63) / 64), dim3(64), 0, s, evk(4), evk(5), 0, a);
+    } else {
         StepArgs pa_ = a;
         pa_.geo_ready = p.geo_ready;  // k_post_multi reads the geometry the ray launch computed
-        hipExtLaunchKernelGGL(k_post_multi, dim3(a.E), dim3(kMultiBlock), 0, s, evk(4), evk(5), 0, pa_);
+        if (lim)
+            hipExtLaunchKernelGGL(k_post_multi<true>, dim3(a.E), dim3(kMultiBlock), 0, s, evk(4), evk(5), 0, pa_);
+        else
+            hipExtLaunchKernelGGL(k_post_multi<false>, dim3(a.E), dim3(kMultiBlock), 0, s, evk(4), evk(5), 0, pa_);
     }
     return hipGetLastError();
 }

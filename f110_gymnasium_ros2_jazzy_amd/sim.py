@@ -29,6 +29,7 @@ class StepOut:
     lap_counts: torch.Tensor   # [E, A] f32
     sim_time: torch.Tensor     # [E] f64
     scans_f64: torch.Tensor = None  # [E, A, B] f64 (optional)
+    truncated: torch.Tensor = None  # [E] u8: 0, 1 time limit, 2 stall (set_episode_limits; else None)
 
 
 def _ptr(t):
@@ -295,6 +296,41 @@ class BatchSim:
         sd = (int(self.cfg.seed) if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
         _lib.check(self.L.f110_set_param_randomization(self.ctx, lo.ctypes.data_as(PP), hi.ctypes.data_as(PP), sd,
                                                        self._stream()), "f110_set_param_randomization")
+
+    # ---- episode limits (f110_set_episode_limits) -----------------------------
+    @staticmethod
+    def check_episode_limits(max_steps=None, stall_speed=0.0, stall_steps=None):
+        """(max_steps, stall_speed, stall_steps) as the C ABI takes them (None -> 0), or ValueError:
+        a negative limit, a negative / non-finite stall_speed, or a stall limit without a positive
+        stall_speed (which could never fire).  Host only."""
+        ms, ss, sp = int(max_steps or 0), int(stall_steps or 0), float(stall_speed)
+        if ms < 0:
+            raise ValueError(f"episode limits: max_steps must be >= 0; got {max_steps}")
+        if ss < 0:
+            raise ValueError(f"episode limits: stall_steps must be >= 0; got {stall_steps}")
+        if not np.isfinite(sp) or sp < 0:
+            raise ValueError(f"episode limits: stall_speed must be finite and >= 0; got {stall_speed}")
+        if ss and not sp > 0:
+            raise ValueError("episode limits: stall_steps needs a positive stall_speed")
+        return ms, sp, ss
+
+    def set_episode_limits(self, max_steps=None, stall_speed=0.0, stall_steps=None):
+        """Truncation on the device (f110_set_episode_limits): an env that has run ``max_steps``
+        steps since its reset, or whose ego has been slower than ``stall_speed`` for ``stall_steps``
+        steps in a row, is flagged in ``out.truncated`` (1 time limit, 2 stall; termination wins,
+        then the time limit) and, with autoreset, reset at its next step as a terminated env is.
+        The flags are written by every following reset / step / step_n, with full and minimal
+        outputs alike.  All off (the default arguments): the limit-free path, ``out.truncated`` is
+        None again."""
+        ms, sp, ss = self.check_episode_limits(max_steps, stall_speed, stall_steps)
+        buf = None
+        if ms or ss:
+            buf = self.out.truncated
+            if buf is None:
+                buf = torch.zeros(self.E, dtype=torch.uint8, device=self.device)
+        _lib.check(self.L.f110_set_episode_limits(self.ctx, ms, sp, ss, _ptr(buf), self._stream()),
+                   "f110_set_episode_limits")
+        self.out.truncated = buf
 
     def set_scan_noise(self, noise):
         """Caller-supplied scan noise for the following step/reset calls

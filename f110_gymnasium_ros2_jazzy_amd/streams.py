@@ -225,6 +225,22 @@ class StreamShards:
             with torch.cuda.stream(self.streams[s]):
                 sm.set_param_randomization(ranges, seed=seed)
 
+    def set_episode_limits(self, max_steps=None, stall_speed=0.0, stall_steps=None):
+        """BatchSim.set_episode_limits on every sub-shard (the limits are per env: the sub-shards'
+        flags are those of one E-env context)."""
+        self._fork()
+        for s, sm in enumerate(self.sims):
+            with torch.cuda.stream(self.streams[s]):
+                sm.set_episode_limits(max_steps, stall_speed, stall_steps)
+
+    @property
+    def truncated(self):
+        """[E] u8 truncation flags of all envs (joined), or None with the limits off."""
+        if self.sims[0].out.truncated is None:
+            return None
+        self.join()
+        return torch.cat([sm.out.truncated for sm in self.sims], 0)
+
     def env_params(self) -> dict:
         """field -> [E, A] float64 NumPy array of the params in force (BatchSim.env_params)."""
         parts = []

@@ -39,7 +39,8 @@ class VectorTrainer:
 
     def __init__(self, envs_per_rank: int, map_name: str = "Spielberg_map", batch_size: int = 4096,
                  memory_size: int = 1 << 20, warmup_steps: int = 1000, updates_per_step: int = 1, seed: int = 42,
-                 device=None, env_offset: int = 0, rank_seed: int = 0, graphs: bool = True):
+                 device=None, env_offset: int = 0, rank_seed: int = 0, graphs: bool = True,
+                 max_episode_steps: int | None = None, stall_speed: float = 0.0, stall_steps: int | None = None):
         from .ddpg import DDPGLearner
         from .maps import MAP_DIR
         from .reward import BatchedCenterlineReward, CenterlineTrack
@@ -50,9 +51,13 @@ class VectorTrainer:
         self.track = CenterlineTrack(cl["xy"], cl["w_right"], cl["w_left"], device=self.device.index or 0)
         self.reward_fn = BatchedCenterlineReward(self.N, dt=0.01, progress=self.track, device=self.device,
                                                  **REWARD_KW)
+        # episode limits (device truncation): with any of them on the env also keeps the episode
+        # statistics on the device (one kernel pair per step, inside the step graphs)
+        self.episode_stats = bool(max_episode_steps or stall_steps)
         self.env = F110VectorEnv(self.N, map=map_name, num_agents=2, seed=seed, device=self.device,
                                  env_offset=env_offset, opponent="gap_follow", reward_fn=self.reward_fn,
-                                 infos="minimal")
+                                 infos="minimal", max_episode_steps=max_episode_steps, stall_speed=stall_speed,
+                                 stall_steps=stall_steps, episode_stats=self.episode_stats)
         self.agent = DDPGLearner(obs_dim=self.env.single_observation_space.shape[0], act_dim=2,
                                  action_low=ACTION_LOW, action_high=ACTION_HIGH, gamma=0.99, tau=0.005,
                                  actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size,
@@ -186,6 +191,24 @@ class VectorTrainer:
         self.track.close()
 
 
+def episode_report(tr: VectorTrainer, world: int = 1) -> dict:
+    """The episodes finished since the last report, summed over ranks on the host (print time only),
+    then cleared: episodes, episode_return_mean, episode_length_mean."""
+    t = tr.env.episode_totals()
+    tr.env.reset_episode_totals()
+    v = [float(t["episodes"]), float(t["return_sum"]), float(t["length_sum"])]
+    if world > 1:
+        import torch.distributed as dist
+        w = torch.tensor(v, dtype=torch.float64)
+        if dist.get_backend() != "gloo":
+            w = w.to(tr.device)
+        dist.all_reduce(w)
+        v = w.tolist()
+    n = int(v[0])
+    return {"episodes": n, "episode_return_mean": v[1] / n if n else None,
+            "episode_length_mean": v[2] / n if n else None}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs-per-gpu", type=int, default=4096)
@@ -195,23 +218,30 @@ def main():
     ap.add_argument("--memory", type=int, default=1 << 20)
     ap.add_argument("--updates-per-step", type=int, default=1)
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--max-episode-steps", type=int, default=0, help="time limit per episode in steps (0: none)")
+    ap.add_argument("--stall-speed", type=float, default=0.0, help="ego speed below which a step counts as standing")
+    ap.add_argument("--stall-steps", type=int, default=0, help="standing steps in a row that truncate (0: none)")
     args = ap.parse_args()
     rank, world, local = D.init()
     torch.cuda.set_device(D.local_device_index(local))
     shard = D.shard_range(args.envs_per_gpu * world, world, rank)
     tr = VectorTrainer(shard.count, batch_size=args.batch, memory_size=args.memory, warmup_steps=args.warmup,
                        updates_per_step=args.updates_per_step, seed=args.seed, env_offset=shard.offset,
-                       rank_seed=rank)
+                       rank_seed=rank, max_episode_steps=args.max_episode_steps, stall_speed=args.stall_speed,
+                       stall_steps=args.stall_steps)
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)
     for k in range(args.steps):
         rew, term = tr.step()
         ret += rew
-        if rank == 0 and (k + 1) % 500 == 0:
-            st = tr.last or {}
-            print(json.dumps({"step": k + 1, "env_steps_per_s": shard.count * world * (k + 1) / (time.perf_counter() - t0),
-                              "critic_loss": float(st["critic_loss"]) if st else None,
-                              "mean_return": float(ret.mean())}), flush=True)
+        if (k + 1) % 500 == 0:
+            ep = episode_report(tr, world) if tr.episode_stats else {}  # (every rank: a host all-reduce)
+            if rank == 0:
+                st = tr.last or {}
+                print(json.dumps({"step": k + 1,
+                                  "env_steps_per_s": shard.count * world * (k + 1) / (time.perf_counter() - t0),
+                                  "critic_loss": float(st["critic_loss"]) if st else None,
+                                  "mean_return": float(ret.mean()), **ep}), flush=True)
     tr.close()
     D.shutdown()
 

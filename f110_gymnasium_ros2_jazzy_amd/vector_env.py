@@ -6,7 +6,8 @@ Gymnasium-1.x vector surface (``reset(seed, options) -> (obs, infos)``,
 observations and infos kept as device tensors (``as_numpy=True`` converts).
 
 Per env the semantics are F110Env's (f110_env.py:371-472): reward = timestep,
-terminated = ego collision or 4 lap toggles, truncated = False, flat obs =
+terminated = ego collision or 4 lap toggles, truncated = False (unless episode
+limits are set, below), flat obs =
 [agent-0 scan / lidar_max, (x, y, yaw, collision) per agent].  Autoreset is
 the gymnasium NEXT_STEP mode and runs on the device: the step after an env
 terminates resets it to a pose drawn from ``spawn_poses`` (and performs the
@@ -28,6 +29,24 @@ device's domain randomization of the vehicle dynamics: every reset and
 autoreset redraws the resetting cars' friction, mass, ... from the ranges
 (keyed by global env id and episode); ``env.sim.env_params()`` shows the cars
 in force.  The infos are unchanged.
+
+``max_episode_steps`` / ``stall_speed`` + ``stall_steps`` put episode limits on
+the device (BatchSim.set_episode_limits): an env that did not terminate is
+truncated after ``max_episode_steps`` steps since its reset (code 1), or when
+its ego has been slower than ``stall_speed`` for ``stall_steps`` steps in a row
+(code 2); terminated wins over the time limit, the time limit over the stall.
+``step`` then returns the device's truncations, ``infos["truncation"]`` holds
+the u8 code, and a truncated env autoresets at its next step exactly as a
+terminated one does.  A trainer stores a truncated transition with ``done`` =
+0 (DDPGLearner.remember_env takes ``terminated``): it bootstraps from its real
+next_obs, which under NEXT_STEP autoreset is what the truncating step returns;
+the reset row that follows is skipped as after a termination.  With all limits
+off (the default) truncations stay zeros and the infos keys are unchanged.
+
+``episode_stats=True`` keeps per-env episode returns and lengths on the device
+(episode.EpisodeStats, one small kernel pair per step on that step's rewards):
+``infos["episode"]`` = {"r": last finished return, "l": its length, "finished":
+the envs that finished in this step}, ``episode_totals()`` the running totals.
 
 Multi-GPU: give each rank its block of envs (distributed.shard_range) and
 ``env_offset`` = the block's first global id; RNG streams are keyed by global
@@ -51,12 +70,15 @@ class F110VectorEnv:
                  spawn_poses: np.ndarray | None = None, noise_std: float = 0.01, env_offset: int = 0,
                  ego_idx: int = 0, as_numpy: bool = False, autoreset: bool = True, opponent: str | None = None,
                  opponent_idx: int = 1, reward_fn=None, infos: str = "full", options_dtype=np.float32,
-                 param_ranges=None, param_seed: int | None = None, **kwargs):
+                 param_ranges=None, param_seed: int | None = None, max_episode_steps: int | None = None,
+                 stall_speed: float = 0.0, stall_steps: int | None = None, episode_stats: bool = False, **kwargs):
         self.num_envs = int(num_envs)
         self.num_agents = int(num_agents)
         self.params = dict(params or DEFAULT_PARAMS)
         if param_ranges is not None:  # an unknown field: ValueError before anything is built
             param_range_rows(param_ranges, [{**DEFAULT_PARAMS, **self.params}] * self.num_agents)
+        # a bad episode limit: ValueError before anything is built
+        limits = BatchSim.check_episode_limits(max_episode_steps, stall_speed, stall_steps)
         self.timestep = timestep
         self.as_numpy = as_numpy
         self.track = load_map(map, map_ext)
@@ -71,6 +93,14 @@ class F110VectorEnv:
         # reset and device autoreset redraws the resetting cars' dynamics; sim.env_params() shows them
         if param_ranges is not None:
             self.sim.set_param_randomization(param_ranges, seed=param_seed)
+        # episode limits on the device (BatchSim.set_episode_limits), on before the first reset
+        self._limits = bool(limits[0] or limits[2])
+        if self._limits:
+            self.sim.set_episode_limits(max_episode_steps, stall_speed, stall_steps)
+        self._episode = None
+        if episode_stats:
+            from .episode import EpisodeStats
+            self._episode = EpisodeStats(self.num_envs, device=self.device)
         # F110Env.reset computes start_rot in the dtype of its options
         # (f110_env.py:448-451): autoresets and option-less resets follow
         # options_dtype (train_ddpg passes float32 poses); an explicit
@@ -117,12 +147,26 @@ class F110VectorEnv:
             gap_follow(out.scans[:, self.opponent_idx], out=self._act[:, self.opponent_idx])
 
     # ------------------------------------------------------------------
+    def _episode_infos(self, infos, out):
+        """The keys the episode limits / statistics add (none with both off)."""
+        if self._limits:
+            infos["truncation"] = out.truncated.clone()
+        if self._episode is not None:
+            ep = self._episode
+            infos["episode"] = {"r": ep.last_return.clone(), "l": ep.last_length.clone(),
+                                "finished": ep.finished.bool()}
+        return infos
+
+    def _to_numpy(self, infos):
+        return {k: self._to_numpy(v) if isinstance(v, dict) else v.cpu().numpy() for k, v in infos.items()}
+
     def _infos(self, out):
         if self.infos_mode == "minimal":
             infos = {"reset": out.was_reset.bool()}
             if self.opponent is not None:
                 infos["opponent_actions"] = self._act[:, self.opponent_idx]
-            return {k: v.cpu().numpy() for k, v in infos.items()} if self.as_numpy else infos
+            infos = self._episode_infos(infos, out)
+            return self._to_numpy(infos) if self.as_numpy else infos
         st = self.sim.agent_states()  # [E, A, 7]
         infos = {
             "poses_x": st[..., 0].float(), "poses_y": st[..., 1].float(), "poses_theta": st[..., 4].float(),
@@ -133,8 +177,9 @@ class F110VectorEnv:
         }
         if self.opponent is not None:
             infos["opponent_actions"] = self._act[:, self.opponent_idx].clone()
+        infos = self._episode_infos(infos, out)
         if self.as_numpy:
-            infos = {k: v.cpu().numpy() for k, v in infos.items()}
+            infos = self._to_numpy(infos)
         return infos
 
     def reset(self, seed=None, options=None):
@@ -151,6 +196,8 @@ class F110VectorEnv:
         self._opponent_next(out)
         if self.reward_fn is not None:
             self.reward_fn.reset()
+        if self._episode is not None:
+            self._episode.reset()
         obs = out.obs.clone()
         return (obs.cpu().numpy() if self.as_numpy else obs), self._infos(out)
 
@@ -173,7 +220,9 @@ class F110VectorEnv:
             rewards = torch.where(out.was_reset.bool(), torch.zeros((), dtype=torch.float64, device=self.device),
                                   torch.full((), self.timestep, dtype=torch.float64, device=self.device))
         term = out.terminated.bool()
-        trunc = torch.zeros_like(term)
+        trunc = out.truncated.bool() if self._limits else torch.zeros_like(term)
+        if self._episode is not None:
+            self._episode.update(rewards, out.terminated, out.truncated, out.was_reset)
         obs = out.obs.clone()
         if self.as_numpy:
             return (obs.cpu().numpy(), rewards.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy(),
@@ -195,7 +244,11 @@ class F110VectorEnv:
         rewards and flags are the simulator's / reward function's own buffers
         (no clone, no dtype conversion): valid until the next step.  obs_out:
         a preallocated [N, obs_dim] float32 tensor to copy next_obs into (a
-        captured step graph's fixed buffer) instead of a new one."""
+        captured step graph's fixed buffer) instead of a new one.
+        With episode limits on, ``self.truncated`` is this step's u8 flag buffer
+        (valid until the next step); the 4-tuple is unchanged, and a trainer keeps
+        storing ``terminated`` as done: a truncated transition bootstraps from its
+        next_obs, and the reset row after it is skipped like any other."""
         if self.as_numpy:
             raise ValueError("step_transition: device tensors only (as_numpy=False)")
         a = torch.as_tensor(actions, device=self.device)
@@ -214,7 +267,28 @@ class F110VectorEnv:
         else:
             rewards = torch.where(out.was_reset.bool(), torch.zeros((), dtype=torch.float64, device=self.device),
                                   torch.full((), self.timestep, dtype=torch.float64, device=self.device))
+        if self._episode is not None:
+            self._episode.update(rewards, out.terminated, out.truncated, out.was_reset)
         return (obs.clone() if obs_out is None else obs_out), rewards, out.terminated, out.was_reset
+
+    @property
+    def truncated(self):
+        """The simulator's u8 truncation flags of the last step (0, 1 time limit, 2 stall), or None
+        with the limits off."""
+        return self.sim.out.truncated
+
+    def episode_totals(self) -> dict:
+        """Totals over the episodes finished since the last reset_episode_totals (episode_stats=True):
+        episodes, terminated, truncated, length_sum, return_sum / min / max, return_mean, length_mean
+        as Python numbers.  Waits for the stream."""
+        if self._episode is None:
+            raise ValueError("episode_totals: build the env with episode_stats=True")
+        return self._episode.totals()
+
+    def reset_episode_totals(self):
+        if self._episode is None:
+            raise ValueError("reset_episode_totals: build the env with episode_stats=True")
+        self._episode.reset_totals()
 
     def close(self):
         if getattr(self, "sim", None) is not None:

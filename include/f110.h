@@ -215,6 +215,35 @@ F110_API int f110_get_env_params(f110_ctx *ctx, f110_params *out, void *stream);
 F110_API int f110_set_param_randomization(f110_ctx *ctx, const f110_params *lo, const f110_params *hi, uint64_t seed,
                                           void *stream);
 
+/* ---- episode limits (no reference counterpart: the reference steps one env
+ * from a Python loop that simply stops; gymnasium's TimeLimit wrapper is a host
+ * wrapper, and here the reset happens on the device) --------------------------
+ * Truncation in the step's epilogue.  Per env, n = steps since the env's last
+ * reset (0 after the reset's own zero-action step, +1 in every step that does
+ * not reset the env) and s = the stall counter: after a non-reset step, with v
+ * the ego's state[3] after the TTC response, s = |v| < stall_speed ? s + 1 : 0;
+ * 0 after a reset.  An env that did not terminate in the step gets
+ *   truncated = (max_steps && n >= max_steps) ? 1          (time limit)
+ *             : (stall_steps && s >= stall_steps) ? 2      (stall)
+ *             : 0
+ * so termination wins over truncation and the time limit over the stall; a
+ * reset step (f110_reset, or an autoreset) writes 0.  With cfg.autoreset a
+ * truncated env is reset at its next step exactly as a terminated one is (same
+ * spawn draw, same param draw, same episode count, was_reset set); without it
+ * the flag stays up while its condition holds and nothing else changes.  A
+ * masked f110_reset zeroes n and s of the masked envs only.
+ * max_steps 0 = no time limit, stall_steps 0 = no stall limit; with both 0 the
+ * context is back on the limit-free path and `truncated` is dropped, never
+ * written.  truncated: device [n_envs] u8 that every following f110_step /
+ * f110_step_n / f110_reset writes (a masked reset: the masked envs), or NULL
+ * (the limits still end episodes).  Turning the stall limit on (stall_steps
+ * from 0) starts every env's s at 0.  F110_E_INVALID, with the argument named in
+ * f110_last_error and before any device call, for a negative max_steps or
+ * stall_steps or a negative / non-finite stall_speed.  Ordered on `stream`,
+ * applied when the call returns. */
+F110_API int f110_set_episode_limits(f110_ctx *ctx, int64_t max_steps, double stall_speed, int32_t stall_steps,
+                                     uint8_t *truncated, void *stream);
+
 /* Scan-noise source of the following f110_step / f110_reset calls.
  * noise: device [n_envs][n_beams] f64, or NULL for the built-in stream.
  * The reference draws the noise as rng.normal(0, std_dev, num_beams) from a
@@ -366,6 +395,41 @@ F110_API void f110_default_reward_params(f110_reward_params *p);
 F110_API int f110_reward(const f110_track *track, const f110_reward_params *params, const float *obs, int64_t n_envs,
                          int32_t obs_len, int32_t n_beams, f110_reward_state *state, const uint8_t *reset_mask,
                          double *rewards, void *stream);
+
+/* ---- episode statistics (no reference counterpart: train_ddpg.py sums one
+ * env's rewards in its Python loop) ------------------------------------------------
+ * Per-env episode return and length of an autoresetting batch, and running
+ * totals over the finished episodes, from each step's rewards and flags.  No
+ * context; all pointers are device pointers; async on `stream`, no host
+ * synchronisation and no allocation (capturable in a HIP graph).
+ * Per env and call:
+ *   was_reset:  ret = 0, len = 0, closed = 0, finished = 0; the row's reward is
+ *               ignored (it is the reset observation of NEXT_STEP autoreset);
+ *   closed:     the env ended and was not reset since (autoreset off): the row
+ *               is ignored, finished = 0;
+ *   otherwise:  ret += reward, len += 1; if terminated || truncated: finished =
+ *               1, last_return = ret, last_length = len, closed = 1 and the env
+ *               enters the totals, as terminated if terminated, else truncated;
+ *               else finished = 0.
+ * last_return / last_length keep their values where the env does not finish.
+ * truncated, last_return, last_length and finished may be NULL.
+ * Totals accumulate over calls (zero bytes = fresh; return_min / return_max are
+ * meaningful only when episodes > 0).  The envs finishing in one call are
+ * reduced in a fixed order: blocks of 256 consecutive envs reduce their (sum,
+ * min, max, counts) in LDS as a binary tree over the env's position in the
+ * block (entry i += entry i + h for h = 128, 64, .. 1; envs that do not finish
+ * enter as +0.0), each block stores its partial to scratch, and a second
+ * launch adds the partials in ascending block order, then that sum to the
+ * totals.  No floating-point atomics: the same inputs give the same bits
+ * whatever the timing.  scratch: f110_episode_scratch_bytes(n_envs) bytes. */
+typedef struct f110_episode_state { double ret; int32_t len; int32_t closed; } f110_episode_state; /* zero bytes = fresh */
+typedef struct f110_episode_totals { int64_t episodes, terminated, truncated, length_sum;
+                                     double return_sum, return_min, return_max; } f110_episode_totals;
+F110_API int64_t f110_episode_scratch_bytes(int64_t n_envs);
+F110_API int f110_episode_stats(const double *rewards, const uint8_t *terminated, const uint8_t *truncated,
+                                const uint8_t *was_reset, int64_t n_envs, f110_episode_state *state,
+                                double *last_return, int32_t *last_length, uint8_t *finished,
+                                f110_episode_totals *totals, void *scratch, void *stream);
 
 /* ---- prioritized experience replay ---------------------------------------------
  * Replaces rl_training/DDPG/replay_buffer.py:PrioritizedExperienceReplayBuffer

@@ -254,6 +254,20 @@ F110_API int f110_host_check_param_ranges(const f110_params *lo, const f110_para
 F110_API int f110_host_param_draw(uint64_t seed, int64_t env, int32_t agent, uint64_t episode, const f110_params *lo,
                                   const f110_params *hi, f110_params *out);
 
+/* f110_set_episode_limits' validation without a context: F110_OK, or
+ * F110_E_INVALID with the argument named in f110_last_error (negative
+ * max_steps / stall_steps, negative or non-finite stall_speed).  Host test hook. */
+F110_API int f110_host_check_episode_limits(int64_t max_steps, double stall_speed, int32_t stall_steps);
+/* f110_episode_stats over HOST arrays (same arguments, no scratch, no stream):
+ * the device's per-env update and totals merge, run in ascending env order.
+ * The device differs only in the order return_sum is added up (f110.h).  Host
+ * test hook: the CPU suite and the GPU tests share one statement of the
+ * semantics. */
+F110_API int f110_host_episode_stats(const double *rewards, const uint8_t *terminated, const uint8_t *truncated,
+                                     const uint8_t *was_reset, int64_t n_envs, f110_episode_state *state,
+                                     double *last_return, int32_t *last_length, uint8_t *finished,
+                                     f110_episode_totals *totals);
+
 #ifdef __cplusplus
 }
 #endif

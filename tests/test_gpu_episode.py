@@ -1,0 +1,493 @@
+"""Episode limits (f110_set_episode_limits: truncation in the step epilogue of k_post_single /
+k_post_multi) and episode statistics (f110_episode_stats) on the GPU.
+
+Shapes: E = 70 with A = 1 (two 64-lane blocks, 58 padding lanes, k_post_single) and E = 33 with
+A = 2 (k_post_multi).  The runs are on straight_corridor, whose wall is 1.37 m to the left of the
+centre line: a car spawned at y = 1.2 (1.25) facing the wall and commanded 20 m/s has its TTC fire in
+its first (third) step -- an ordinary simulated collision --, one spawned at y = 1.0 in its 20th, one
+at y = 0.3 along the corridor never (checked on the CPU oracle).
+
+The stall runs use v_min = -5 (f110_gym's stock value): with this project's default v_min = 1e-8
+the reference's PID turns every braking command into full throttle, so a car commanded 0 m/s
+never stands; with a negative v_min it does what the command says."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(70, 1), (33, 2)]
+K = 7
+STALL = dict(stall_speed=0.1, stall_steps=5)
+
+
+def _sim(tracks, gpu, track="straight_corridor", **kw):
+    from f110_gymnasium_ros2_jazzy_amd.sim import BatchSim
+    kw.setdefault("noise_std", 0.0)
+    return BatchSim(tracks(track), device=gpu, **kw)
+
+
+def _table(A):
+    """Spawn rows [8, A, 3]: ego kinds (y, yaw) at 8 places along the corridor; the other cars drive
+    along it 5 m, 10 m, .. ahead on the centre side."""
+    kinds = [(1.2, np.pi / 2), (0.3, 0.0), (1.25, np.pi / 2), (0.3, 0.0), (1.0, np.pi / 2), (0.3, 0.0),
+             (1.2, np.pi / 2), (0.3, 0.0)]
+    rows = np.zeros((len(kinds), A, 3))
+    for i, (y, yaw) in enumerate(kinds):
+        rows[i, 0] = (10.0 + 9.0 * i, y, yaw)
+        for a in range(1, A):
+            rows[i, a] = (10.0 + 9.0 * i + 4.0 * a, -0.3, 0.0)
+    return rows
+
+
+def _const_actions(E, A, vel):
+    """[E, A, 2] float32: steer 0, velocity vel[e] for every car of env e."""
+    a = np.zeros((E, A, 2), np.float32)
+    a[:, :, 1] = np.asarray(vel, np.float32)[:, None]
+    return a
+
+
+def _flags(sim):
+    o = sim.out
+    return (o.terminated.cpu().numpy().copy(), o.truncated.cpu().numpy().copy(), o.was_reset.cpu().numpy().copy())
+
+
+def _ego_speed(sim):
+    st = sim.get_state()[0].cpu().numpy()  # [7, E*A]
+    return st[3].reshape(sim.E, sim.A)[:, sim.cfg.ego_idx]
+
+
+class LimitModel:
+    """The header's semantics per env, driven by the device's own terminated flags and ego speeds."""
+
+    def __init__(self, E, max_steps=0, stall_speed=0.0, stall_steps=0, autoreset=True):
+        self.n = np.zeros(E, np.int64)
+        self.s = np.zeros(E, np.int64)
+        self.pending = np.zeros(E, bool)
+        self.K, self.vs, self.ss, self.autoreset = max_steps, stall_speed, stall_steps, autoreset
+
+    def reset(self, mask=None):
+        m = np.ones(len(self.n), bool) if mask is None else np.asarray(mask, bool)
+        self.n[m] = 0
+        self.s[m] = 0
+        self.pending[m] = False
+
+    def step(self, term, v):
+        """(expected truncated codes, expected was_reset) of a step whose device outputs are term, v."""
+        was = self.pending.copy()
+        self.n = np.where(was, 0, self.n + 1)
+        self.s = np.where(was, 0, np.where(np.abs(v) < self.vs, self.s + 1, 0))
+        code = np.where(self.K and self.n >= self.K, 1, np.where(self.ss and self.s >= self.ss, 2, 0))
+        code = np.where(term.astype(bool) | was, 0, code).astype(np.uint8)
+        self.pending = (term.astype(bool) | (code != 0)) & self.autoreset
+        return code, was.astype(np.uint8)
+
+
+# ---- 1. off is untouched ---------------------------------------------------------------------------
+@pytest.mark.parametrize("E,A", SHAPES)
+def test_limits_off_is_untouched(tracks, gpu, E, A):
+    T = 40
+    rng = np.random.default_rng(10 * E + A)
+    tab = _table(A)
+    poses = tab[np.arange(E) % len(tab)]
+    acts = np.stack([rng.uniform(-0.05, 0.05, (T, E, A)), rng.uniform(15, 20, (T, E, A))], -1).astype(np.float32)
+    kw = dict(n_envs=E, n_agents=A, autoreset=True, spawn_poses=tab, seed=9, noise_std=0.01, keep_f64_scans=True)
+    never, far, cleared = (_sim(tracks, gpu, **kw) for _ in range(3))
+    far.set_episode_limits(max_steps=10 ** 6)
+    cleared.set_episode_limits(max_steps=3, **STALL)
+    assert cleared.out.truncated is not None
+    cleared.set_episode_limits()
+    assert cleared.out.truncated is None and never.out.truncated is None
+    sims = (never, far, cleared)
+    for s in sims:
+        s.reset(poses)
+    resets = 0
+    for t in range(T):
+        outs = []
+        for s in sims:
+            o = s.step(acts[t])
+            outs.append([x.cpu().numpy() for x in (o.obs, o.scans_f64, o.terminated, o.was_reset)])
+        for other in outs[1:]:
+            for a, b in zip(outs[0], other):
+                assert np.array_equal(a, b), t
+        assert not far.out.truncated.any()
+        resets += int(outs[0][3].sum())
+    assert resets >= E // 4  # the autoreset path ran inside the window
+    ref = [x.cpu().numpy() for x in never.get_state()]
+    for s in sims[1:]:
+        for a, b in zip(ref, [x.cpu().numpy() for x in s.get_state()]):
+            assert np.array_equal(a, b)
+    for s in sims:
+        s.close()
+
+
+# ---- 2. time limit -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("E,A", SHAPES)
+def test_time_limit(tracks, gpu, E, A):
+    T = 30
+    tab = _table(A)
+    poses = tab[np.arange(E) % len(tab)]
+    act = _const_actions(E, A, np.where(np.arange(E) % 3 == 0, 3.0, 20.0))
+    sim = _sim(tracks, gpu, n_envs=E, n_agents=A, autoreset=True, spawn_poses=tab, seed=4)
+    sim.set_episode_limits(max_steps=K)
+    sim.reset(poses)
+    term, trunc, was = _flags(sim)
+    assert not trunc.any() and was.all()  # a reset step writes 0
+    m = LimitModel(E, max_steps=K)
+    m.reset()
+    n_term = n_trunc = 0
+    for t in range(T):
+        sim.step(act)
+        term, trunc, was = _flags(sim)
+        code, exp_was = m.step(term, np.zeros(E))
+        assert np.array_equal(trunc, code), t
+        assert np.array_equal(was, exp_was), t
+        assert set(np.unique(trunc)) <= {0, 1}
+        n_term += int(term.sum())
+        n_trunc += int((trunc != 0).sum())
+    print(f"E={E} A={A}: {n_term} terminations, {n_trunc} truncations in {T} steps")
+    assert n_term > 0 and n_trunc > 0  # both kinds of episode end occurred
+    sim.close()
+
+
+# ---- 3. stall ------------------------------------------------------------------------------------------
+def test_stall_limit(tracks, gpu):
+    """E = 70, A = 1, autoreset off: kind 0 is commanded 0 m/s from the reset, kind 1 3 m/s, kind 2
+    3 m/s for 10 steps and then 0."""
+    E, A, T = 70, 1, 32
+    kind = np.arange(E) % 3
+    poses = np.tile([[[0.0, 0.3, 0.0]]], (E, 1, 1))
+    poses[:, 0, 0] = 10.0 + np.arange(E)
+    sim = _sim(tracks, gpu, n_envs=E, n_agents=A, params={"v_min": -5.0})
+    sim.set_episode_limits(**STALL)
+    sim.reset(poses)
+    m = LimitModel(E, autoreset=False, **STALL)
+    m.reset()
+    first = np.full(E, -1)
+    below = np.full(E, -1)  # kind 2: the first step after step 10 whose speed is below 0.1
+    for t in range(1, T + 1):
+        vel = np.where(kind == 0, 0.0, np.where((kind == 2) & (t > 10), 0.0, 3.0))
+        sim.step(_const_actions(E, A, vel))
+        term, trunc, was = _flags(sim)
+        v = _ego_speed(sim)
+        code, _ = m.step(term, v)
+        assert not term.any() and not was.any()
+        assert np.array_equal(trunc, code), t
+        first = np.where((first < 0) & (trunc != 0), t, first)
+        below = np.where((below < 0) & (t > 10) & (np.abs(v) < 0.1), t, below)
+        assert set(np.unique(trunc)) <= {0, 2}
+    assert (first[kind == 0] == 5).all()   # flagged 2 at their fifth step
+    assert (first[kind == 1] == -1).all()  # 3 m/s: never
+    assert (below[kind == 2] > 10).all() and (first[kind == 2] == below[kind == 2] + 4).all()
+    # autoreset off: the flag stays up while its condition holds
+    assert (trunc[kind == 0] == 2).all()
+    sim.close()
+
+
+def test_time_limit_wins_over_stall(tracks, gpu):
+    """E = 33, A = 2 (k_post_multi), both limits at 5 steps, autoreset on: the standing envs are
+    flagged 1, reset, and flagged again 5 steps after the reset's own step."""
+    E, A, T = 33, 2, 14
+    tab = _table(A)[1::2]  # the rows along the corridor
+    poses = tab[np.arange(E) % len(tab)]
+    act = _const_actions(E, A, np.where(np.arange(E) % 2 == 0, 0.0, 3.0))
+    sim = _sim(tracks, gpu, n_envs=E, n_agents=A, autoreset=True, spawn_poses=tab, params={"v_min": -5.0})
+    sim.set_episode_limits(max_steps=5, **STALL)
+    sim.reset(poses)
+    m = LimitModel(E, max_steps=5, **STALL)
+    m.reset()
+    for t in range(1, T + 1):
+        sim.step(act)
+        term, trunc, was = _flags(sim)
+        code, exp_was = m.step(term, _ego_speed(sim))
+        assert np.array_equal(trunc, code) and np.array_equal(was, exp_was), t
+        if t in (5, 11):
+            assert (trunc == 1).all()  # standing or not: the time limit, and it wins
+        else:
+            assert not trunc.any()
+    sim.close()
+
+
+# ---- 4. resets are the same resets ---------------------------------------------------------------
+def test_truncation_resets_are_shard_invariant(tracks, gpu):
+    from f110_gymnasium_ros2_jazzy_amd import _lib
+    from f110_gymnasium_ros2_jazzy_amd.streams import StreamShards
+    E, A, T = 70, 1, 60
+    tab = _table(A)
+    poses = tab[np.arange(E) % len(tab)]
+    act = _const_actions(E, A, np.where(np.arange(E) % 3 == 0, 0.0, 20.0))
+    ranges = {"mu": (0.6, 1.1), "a_max": (6.0, 11.0), "m": (3.0, 4.5)}
+    kw = dict(n_agents=A, autoreset=True, spawn_poses=tab, seed=3, params={"v_min": -5.0})
+    full = _sim(tracks, gpu, n_envs=E, **kw)
+    halves = [_sim(tracks, gpu, n_envs=E // 2, env_offset=35 * h, **kw) for h in range(2)]
+    shards = StreamShards(tracks("straight_corridor"), n_envs=E, n_streams=2, noise_std=0.0, device=gpu, **kw)
+    for s in [full, shards] + halves:
+        s.set_param_randomization(ranges, seed=11)
+        s.set_episode_limits(max_steps=K, **STALL)
+    full.reset(poses)
+    shards.reset(poses)
+    for h in range(2):
+        halves[h].reset(poses[35 * h:35 * h + 35])
+    seen = set()
+    for t in range(T):
+        full.step(act)
+        shards.step(act, minimal_outputs=False)
+        for h in range(2):
+            halves[h].step(act[35 * h:35 * h + 35])
+        f = _flags(full)
+        hf = [np.concatenate(x) for x in zip(*[_flags(h) for h in halves])]
+        for a, b in zip(f, hf):
+            assert np.array_equal(a, b), t
+        assert np.array_equal(shards.truncated.cpu().numpy(), f[1]), t
+        seen |= set(np.unique(f[1]).tolist()) | ({"term"} if f[0].any() else set())
+    assert seen == {0, 1, 2, "term"}  # every kind of episode end ran
+    sf = full.get_state()[0].cpu().numpy()
+    assert np.array_equal(sf, np.concatenate([h.get_state()[0].cpu().numpy() for h in halves], 1))
+    shards.join()
+    assert np.array_equal(sf, np.concatenate([sm.get_state()[0].cpu().numpy() for sm in shards.sims], 1))
+
+    def table(s):
+        p = s.env_params()
+        return np.stack([p[k] for k in _lib.PARAM_FIELDS], -1)
+    tf = table(full)
+    assert len(np.unique(tf[:, 0, 0])) > E // 2
+    assert np.array_equal(tf, np.concatenate([table(h) for h in halves]))
+    assert np.array_equal(tf, table(shards))
+    for s in [full, shards] + halves:
+        s.close()
+
+
+# ---- 5. masked reset --------------------------------------------------------------------------------
+def test_masked_reset_zeroes_only_its_counters(tracks, gpu):
+    E, A = 70, 1
+    poses = np.tile([[[0.0, 0.3, 0.0]]], (E, 1, 1))
+    poses[:, 0, 0] = 10.0 + np.arange(E)
+    mask = np.zeros(E, np.uint8)
+    mask[[0, 5, 63, 64, 69]] = 1
+    mb = mask.astype(bool)
+    # the time limit (n): 3 m/s, a masked reset after 4 steps
+    sim = _sim(tracks, gpu, n_envs=E, n_agents=A, autoreset=True, spawn_poses=poses[:8])
+    sim.set_episode_limits(max_steps=K)
+    sim.reset(poses)
+    act = _const_actions(E, A, np.full(E, 3.0))
+    for _ in range(4):
+        sim.step(act, minimal_outputs=True)  # the flags are written with minimal outputs alike
+    sim.reset(poses, env_mask=mask)
+    assert not _flags(sim)[1].any()
+    first = np.full(E, -1)
+    for t in range(5, 12):
+        sim.step(act, minimal_outputs=True)
+        trunc = _flags(sim)[1]
+        first = np.where((first < 0) & (trunc == 1), t, first)
+    assert (first[~mb] == K).all() and (first[mb] == 4 + K).all()
+    sim.close()
+    # the stall counter (s): standing cars, autoreset off, a masked reset after 3 steps
+    sim = _sim(tracks, gpu, n_envs=E, n_agents=A, params={"v_min": -5.0})
+    sim.set_episode_limits(**STALL)
+    sim.reset(poses)
+    act = _const_actions(E, A, np.zeros(E))
+    for _ in range(3):
+        sim.step(act)
+    sim.reset(poses, env_mask=mask)
+    first = np.full(E, -1)
+    for t in range(4, 10):
+        sim.step(act)
+        trunc = _flags(sim)[1]
+        first = np.where((first < 0) & (trunc == 2), t, first)
+    assert (first[~mb] == 5).all() and (first[mb] == 3 + 5).all()
+    sim.close()
+
+
+# ---- 6. step_n and a captured graph --------------------------------------------------------------
+@pytest.mark.parametrize("E,A", SHAPES)
+def test_step_n_and_graph_replay(tracks, gpu, E, A):
+    N = K + 3
+    tab = _table(A)
+    poses = tab[np.arange(E) % len(tab)]
+    act = torch.from_numpy(_const_actions(E, A, np.where(np.arange(E) % 3 == 0, 0.0, 20.0))).to(gpu)
+    sims = [_sim(tracks, gpu, n_envs=E, n_agents=A, autoreset=True, spawn_poses=tab, seed=13, noise_std=0.01,
+                 params={"v_min": -5.0}) for _ in range(3)]
+    for s in sims:
+        s.set_episode_limits(max_steps=K, **STALL)
+        s.reset(poses)
+    for _ in range(N):
+        sims[0].step(act)
+    sims[1].step_n(act.unsqueeze(0).repeat(N, 1, 1, 1))
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        sims[2].step(act)
+    for _ in range(N):
+        g.replay()
+    torch.cuda.synchronize()
+    ends = set()
+    for t in range(N + 1):  # the outputs after the N steps, then N more plain steps: the counters agree too
+        ref = _flags(sims[0])
+        ref_state = sims[0].get_state()[0].cpu().numpy()
+        ends |= set(np.unique(ref[1]).tolist()) | ({"term"} if ref[0].any() else set())
+        for s in sims[1:]:
+            for a, b in zip(ref, _flags(s)):
+                assert np.array_equal(a, b), t
+            assert np.array_equal(s.get_state()[0].cpu().numpy(), ref_state), t
+            assert np.array_equal(s.out.obs.cpu().numpy(), sims[0].out.obs.cpu().numpy()), t
+        for s in sims:
+            s.step(act)
+    assert {1, 2} <= ends  # truncations of both kinds inside the compared window
+    for s in sims:
+        s.close()
+
+
+# ---- 7. the statistics kernel against the host hook ------------------------------------------------
+@pytest.mark.parametrize("n", [1, 257, 1000])
+def test_episode_stats_kernel_matches_host(gpu, n):
+    from f110_gymnasium_ros2_jazzy_amd import _lib
+    from f110_gymnasium_ros2_jazzy_amd.episode import EpisodeStats, host_episode_stats
+    rng = np.random.default_rng(n)
+    calls = []
+    for _ in range(50):
+        r = rng.normal(0.0, 3.0, n)
+        term = (rng.random(n) < 0.08).astype(np.uint8)
+        trunc = (rng.random(n) < 0.08).astype(np.uint8)
+        both = rng.random(n) < 0.02
+        term[both] = trunc[both] = 1
+        wr = (rng.random(n) < 0.05).astype(np.uint8)
+        calls.append((r, term, trunc, wr))
+    dev = [EpisodeStats(n, device=gpu) for _ in range(2)]
+    state = np.zeros((n, 16), np.uint8)
+    last_r, last_l, fin = np.zeros(n), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    totals = _lib.F110EpisodeTotals()
+    abs_sum = 0.0
+    for r, term, trunc, wr in calls:
+        host_episode_stats(r, term, trunc, wr, state, last_r, last_l, fin, totals)
+        abs_sum += float(np.abs(r).sum())
+        for d in dev:
+            d.update(*(torch.from_numpy(x).to(gpu) for x in (r, term, trunc, wr)))
+        d = dev[0]
+        assert np.array_equal(d.state.cpu().numpy(), state)
+        assert np.array_equal(d.last_return.cpu().numpy(), last_r)
+        assert np.array_equal(d.last_length.cpu().numpy(), last_l)
+        assert np.array_equal(d.finished.cpu().numpy(), fin)
+    h = totals.as_dict()
+    t0, t1 = dev[0].totals(), dev[1].totals()
+    for k in ("episodes", "terminated", "truncated", "length_sum"):
+        assert t0[k] == h[k], k
+    if h["episodes"]:
+        assert t0["return_min"] == h["return_min"] and t0["return_max"] == h["return_max"]
+        print(f"n={n}: return_sum device - host = {t0['return_sum'] - h['return_sum']:+.3e}, bound {1e-12 * abs_sum:.3e}")
+        assert abs(t0["return_sum"] - h["return_sum"]) <= 1e-12 * abs_sum
+    assert np.float64(t0["return_sum"]).tobytes() == np.float64(t1["return_sum"]).tobytes()
+    assert t0 == t1
+    if n > 1:
+        assert h["episodes"] > 0 and h["terminated"] > 0 and h["truncated"] > 0
+    # NULL truncated and NULL optional outputs
+    L = _lib.load()
+    st = torch.zeros(n, 16, dtype=torch.uint8, device=gpu)
+    tot = torch.zeros(56, dtype=torch.uint8, device=gpu)
+    scratch = torch.zeros(int(L.f110_episode_scratch_bytes(n)), dtype=torch.uint8, device=gpu)
+    hstate, htot = np.zeros((n, 16), np.uint8), _lib.F110EpisodeTotals()
+    P = lambda x: ctypes.c_void_p(x.data_ptr())  # noqa: E731
+    for r, term, trunc, wr in calls[:10]:
+        dr, dt, dw = (torch.from_numpy(x).to(gpu) for x in (r, term, wr))
+        rc = L.f110_episode_stats(P(dr), P(dt), None, P(dw), n, P(st), None, None, None, P(tot), P(scratch),
+                                  ctypes.c_void_p(torch.cuda.current_stream(gpu).cuda_stream))
+        assert rc == 0
+        host_episode_stats(r, term, None, wr, hstate, totals=htot)
+    assert np.array_equal(st.cpu().numpy(), hstate)
+    got = _lib.F110EpisodeTotals.from_buffer_copy(tot.cpu().numpy().tobytes())
+    assert (got.episodes, got.terminated, got.truncated, got.length_sum) == \
+        (htot.episodes, htot.terminated, 0, htot.length_sum)
+
+
+# ---- 8. F110VectorEnv ------------------------------------------------------------------------------
+def test_vector_env_limits_and_stats(gpu):
+    from f110_gymnasium_ros2_jazzy_amd.vector_env import F110VectorEnv
+    N, T = 70, 30
+    tab = _table(1)
+    env = F110VectorEnv(N, map="straight_corridor", num_agents=1, spawn_poses=tab, noise_std=0.0, device=gpu,
+                        max_episode_steps=K, episode_stats=True)
+    try:
+        obs, infos = env.reset(seed=1)
+        keys = set(infos)
+        assert {"truncation", "episode"} <= keys
+        assert not infos["truncation"].any() and infos["truncation"].dtype == torch.uint8
+        ep = infos["episode"]
+        assert set(ep) == {"r", "l", "finished"} and not ep["r"].any() and not ep["l"].any() and not ep["finished"].any()
+        act = torch.tensor([0.0, 20.0], device=gpu).repeat(N, 1)
+        ret, ln = np.zeros(N), np.zeros(N, np.int64)
+        tally = dict(episodes=0, terminated=0, truncated=0, length_sum=0)
+        returns = []
+        for t in range(T):
+            obs, rew, term, trunc, infos = env.step(act)
+            assert set(infos) == keys
+            assert trunc.dtype == torch.bool and term.dtype == torch.bool
+            code = infos["truncation"].cpu().numpy()
+            rew, term, trunc, was = (x.cpu().numpy() for x in (rew, term, trunc, infos["reset"]))
+            assert np.array_equal(trunc, code != 0)
+            assert (rew[was] == 0).all() and (rew[~was] == env.timestep).all()
+            fin = infos["episode"]["finished"].cpu().numpy()
+            assert np.array_equal(fin, (term | trunc) & ~was)
+            ret = np.where(was, 0.0, ret + rew)
+            ln = np.where(was, 0, ln + 1)
+            assert (infos["episode"]["l"].cpu().numpy()[trunc & ~term] == K).all()
+            assert np.array_equal(infos["episode"]["l"].cpu().numpy()[fin], ln[fin])
+            assert np.array_equal(infos["episode"]["r"].cpu().numpy()[fin], ret[fin])
+            tally["episodes"] += int(fin.sum())
+            tally["terminated"] += int((fin & term).sum())
+            tally["truncated"] += int((fin & ~term).sum())
+            tally["length_sum"] += int(ln[fin].sum())
+            returns += ret[fin].tolist()
+        tot = env.episode_totals()
+        assert {k: tot[k] for k in tally} == tally
+        assert tally["terminated"] > 0 and tally["truncated"] > 0
+        rs = float(np.sum(returns))
+        assert abs(tot["return_sum"] - rs) <= 1e-12 * abs(rs)
+        assert tot["return_min"] == min(returns) and tot["return_max"] == max(returns)
+        assert tot["return_mean"] == tot["return_sum"] / tot["episodes"]
+        assert tot["length_mean"] == tot["length_sum"] / tot["episodes"]
+        env.reset_episode_totals()
+        assert env.episode_totals()["episodes"] == 0
+    finally:
+        env.close()
+    # all defaults: no truncation, today's key set
+    env = F110VectorEnv(N, map="straight_corridor", num_agents=1, spawn_poses=tab, noise_std=0.0, device=gpu)
+    try:
+        obs, infos = env.reset(seed=1)
+        assert set(infos) == keys - {"truncation", "episode"} and env.truncated is None
+        for t in range(K + 2):
+            out = env.step(act)
+            assert not out[3].any() and out[3].dtype == torch.bool and set(out[4]) == set(infos)
+        with pytest.raises(ValueError, match="episode_stats"):
+            env.episode_totals()
+    finally:
+        env.close()
+
+
+# ---- 9. the trainer ------------------------------------------------------------------------------------
+def test_trainer_truncates_and_stores_done_zero(gpu):
+    from f110_gymnasium_ros2_jazzy_amd.train import VectorTrainer, episode_report
+    N, CAP, T = 64, 4096, 80
+    tr = VectorTrainer(N, batch_size=64, memory_size=CAP, warmup_steps=8, graphs=True, max_episode_steps=20)
+    try:
+        done_rows = []  # the done flag of every stored row, in the ring's order (step-major, reset rows skipped)
+        n_trunc = 0
+        for _ in range(T):
+            rew, term = tr.step()
+            term = term.cpu().numpy().astype(bool)
+            was = tr.env.sim.out.was_reset.cpu().numpy().astype(bool)
+            n_trunc += int((tr.env.truncated.cpu().numpy() != 0).sum())
+            done_rows += term[~was].tolist()
+        assert tr._sg[0] is not None and tr._sg[1] is not None  # the graphed path was reached, both parities
+        tot = tr.env.episode_totals()
+        assert tot["episodes"] > 0 and tot["truncated"] > 0
+        assert tot["truncated"] == n_trunc and tot["episodes"] == tot["terminated"] + tot["truncated"]
+        n = len(tr.agent.memory)
+        assert n == min(len(done_rows), CAP)
+        stored = tr.agent.memory.arrays(("dones",))["dones"][:n].cpu().numpy()
+        assert stored.sum() == sum(done_rows[-CAP:])  # truncations are not stored as done
+        rep = episode_report(tr)
+        assert rep["episodes"] == tot["episodes"] and rep["episode_length_mean"] == tot["length_mean"]
+        assert tr.env.episode_totals()["episodes"] == 0
+    finally:
+        tr.close()
