@@ -118,6 +118,7 @@ EXPORTS = [
     "f110_ddpg_q_mean", "f110_ddpg_q_mean_bwd", "f110_ddpg_relu_bwd_scratch_floats", "f110_ddpg_relu_bwd",
     "f110_learner_gemm", "f110_learner_wgrad_scratch_floats", "f110_learner_wgrad", "f110_learner_wgrad_loss",
     "f110_ddpg_critic_step", "f110_ddpg_q_mean_step", "f110_ddpg_row_blocks",
+    "f110_ddpg_actor_explore_env", "f110_host_explore_rows",
 ]
 
 _lib = None
@@ -265,6 +266,11 @@ def load(build_if_missing: bool = True):
     L.f110_ddpg_actor_head.argtypes = [_P] * 5 + [i32] * 3 + [_P] * 3
     L.f110_ddpg_actor_explore.argtypes = [_P] * 5 + [i32] * 3 + [_P, _P, ctypes.c_double, ctypes.c_double, _P, _P,
                                                                   ctypes.c_uint64, _P, i64, _P]
+    f64 = ctypes.c_double
+    L.f110_ddpg_actor_explore_env.argtypes = L.f110_ddpg_actor_explore.argtypes[:-1] + [i32, _P, f64, f64, f64, _P, _P,
+                                                                                       _P, _P]
+    L.f110_host_explore_rows.argtypes = [_P, _P, i64, i32, i32, _P, f64, f64, f64, _P, _P, _P, _P, f64, f64, _P, _P,
+                                         _P]
     L.f110_ddpg_actor_head_bwd.argtypes = [_P] * 5 + [i32] * 3 + [_P] * 6
     L.f110_ddpg_td_target.argtypes = [_P] * 5 + [f32, i32, i32, _P, _P]
     L.f110_ddpg_critic_loss.argtypes = [_P] * 5 + [i32] * 2 + [_P] * 4

@@ -18,6 +18,7 @@
 // expression order (-ffp-contract=off keeps mul and add separate there).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <string>
 #include <type_traits>
 
@@ -35,7 +36,7 @@ constexpr int kWRows = 64;    // rows per block of the weight-gradient pass
 constexpr int kMaxOut = 4;    // head outputs (act_dim <= 4)
 constexpr int kMaxK = 255;    // hidden width (the weight pass keeps >= 3 row lanes of column quads)
 
-enum HeadMode { kActor = 0, kTarget = 1, kLoss = 2, kMean = 3, kExplore = 4 };
+enum HeadMode { kActor = 0, kTarget = 1, kLoss = 2, kMean = 3, kExplore = 4, kExploreEnv = 5 };
 
 struct HeadArgs {
     const float *h, *W, *b;
@@ -58,6 +59,14 @@ struct HeadArgs {
     double decay, sigma_min;
     int64_t out_stride;
     uint64_t seed;
+    // kExploreEnv (kExplore's fields, plus): the noise kind, the per-row OU state [B][nout], the OU
+    // constants (sqdt = sqrt(dt)), the per-row reset / eval flags and the caller's draws [B][nout]
+    // (each may be null)
+    double *ou_x;
+    double theta, mu, dt, sqdt;
+    const uint8_t *reset, *eval_mask;
+    const float *normals_ext;
+    int32_t kind;
 };
 
 // choose_action's exploration noise (agent.py:350-370, GaussianActionNoise
@@ -185,6 +194,34 @@ __global__ void __launch_bounds__(kHB) k_head_fwd(HeadArgs a) {
                         a.out0[row * a.out_stride + j + q] = v;
                     }
                 }
+            } else if (MODE == kExploreEnv) {  // per row: reset, eval or explore (explore_one, f110_device.h)
+                const double sigma = a.nstate_in[0];
+                const uint64_t step = (uint64_t)a.nstate_in[1];
+                const bool ev = a.eval_mask && a.eval_mask[row] != 0;
+                const bool rs = a.reset && a.reset[row] != 0;
+                const bool ou = a.kind == kExploreOU;
+#pragma unroll
+                for (int j = 0; j < NOUT; j += 2) {
+                    float2 nz = make_float2(0.0f, 0.0f);
+                    if (!ev) {  // an eval row uses no draw (keys are by row: the others' draws stay)
+                        if (a.normals_ext) {
+                            nz.x = a.normals_ext[row * NOUT + j];
+                            if (j + 1 < NOUT) nz.y = a.normals_ext[row * NOUT + j + 1];
+                        } else {
+                            nz = explore_normals(a.seed, step, row, j >> 1);
+                        }
+                    }
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        if (j + q >= NOUT) break;
+                        const float act = a.aux0[j + q] * tanhf(z[j + q]) + a.aux1[j + q];
+                        double x = ou && !rs ? a.ou_x[row * NOUT + j + q] : 0.0;
+                        a.out0[row * a.out_stride + j + q] =
+                            explore_one(a.kind, act, q == 0 ? nz.x : nz.y, sigma, a.theta, a.mu, a.dt, a.sqdt, rs, ev,
+                                        a.lo[j + q], a.hi[j + q], x);
+                        if (ou && (rs || !ev)) a.ou_x[row * NOUT + j + q] = x;
+                    }
+                }
             } else if (MODE == kTarget) {  // r + gamma * (1.0 - d) * q_next (agent.py:306)
                 const float gd = a.gamma * (1.0f - a.aux1[row]);
                 a.out0[row] = a.aux0[row] + gd * z[0];
@@ -201,7 +238,8 @@ __global__ void __launch_bounds__(kHB) k_head_fwd(HeadArgs a) {
         const float s = block_sum(v);
         if (threadIdx.x == 0) a.part[blockIdx.x] = s;
     }
-    if (MODE == kExplore && blockIdx.x == 0 && threadIdx.x == 0) {  // GaussianActionNoise.__call__'s decay
+    // GaussianActionNoise.__call__'s decay (OUActionNoise's is the same line)
+    if ((MODE == kExplore || MODE == kExploreEnv) && blockIdx.x == 0 && threadIdx.x == 0) {
         const double sg = a.nstate_in[0] * a.decay;
         a.nstate_out[0] = sg > a.sigma_min ? sg : a.sigma_min;  // max(sigma * decay, sigma_min)
         a.nstate_out[1] = a.nstate_in[1] + 1.0;
@@ -556,6 +594,60 @@ extern "C" int f110_ddpg_actor_explore(const float *h, const float *W, const flo
         return hipGetLastError();
     });
     return e == hipSuccess ? 0 : fail_hip("f110_ddpg_actor_explore", e);
+}
+
+extern "C" int f110_ddpg_actor_explore_env(const float *h, const float *W, const float *b, const float *scale,
+                                           const float *shift, int32_t B, int32_t K, int32_t nout,
+                                           const double *state_in, double *state_out, double decay, double sigma_min,
+                                           const float *low, const float *high, uint64_t seed, float *out,
+                                           int64_t out_stride, int32_t kind, double *ou_x, double theta, double mu,
+                                           double dt, const uint8_t *reset, const uint8_t *eval_mask,
+                                           const float *normals_ext, void *stream) {
+    if (bad_shape(B, K, nout) || !h || !W || !b || !scale || !shift || !state_in || !state_out ||
+        state_in == state_out || !low || !high || !out || out_stride < nout ||
+        (kind != kExploreGaussian && kind != kExploreOU) || (kind == kExploreOU && !ou_x) || !std::isfinite(theta) ||
+        !std::isfinite(mu) || !std::isfinite(dt) || dt < 0.0)
+        return fail_arg("f110_ddpg_actor_explore_env");
+    HeadArgs a{};
+    a.h = h, a.W = W, a.b = b, a.aux0 = scale, a.aux1 = shift, a.out0 = out;
+    a.lo = low, a.hi = high, a.nstate_in = state_in, a.nstate_out = state_out, a.decay = decay;
+    a.sigma_min = sigma_min, a.out_stride = out_stride, a.seed = seed;
+    a.kind = kind, a.ou_x = ou_x, a.theta = theta, a.mu = mu, a.dt = dt, a.sqdt = std::sqrt(dt);
+    a.reset = reset, a.eval_mask = eval_mask, a.normals_ext = normals_ext;
+    a.B = B, a.K = K, a.nout = nout;
+    hipError_t e = with_nout(nout, [&](auto N) {
+        hipLaunchKernelGGL((k_head_fwd<kExploreEnv, decltype(N)::value>), dim3(row_blocks(B)), dim3(kHB), 0,
+                           (hipStream_t)stream, a);
+        return hipGetLastError();
+    });
+    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_actor_explore_env", e);
+}
+
+extern "C" int f110_host_explore_rows(const float *act, const float *normals, int64_t n_rows, int32_t nout,
+                                      int32_t kind, double *ou_x, double theta, double mu, double dt,
+                                      const uint8_t *reset, const uint8_t *eval_mask, const double *state_in,
+                                      double *state_out, double decay, double sigma_min, const float *low,
+                                      const float *high, float *out) {
+    if (n_rows <= 0 || nout <= 0 || nout > kMaxOut || !act || !normals || !state_in || state_in == state_out || !low ||
+        !high || !out || (kind != kExploreGaussian && kind != kExploreOU) || (kind == kExploreOU && !ou_x) ||
+        !std::isfinite(theta) || !std::isfinite(mu) || !std::isfinite(dt) || dt < 0.0)
+        return fail_arg("f110_host_explore_rows");
+    const double sigma = state_in[0], sqdt = std::sqrt(dt);
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const bool ev = eval_mask && eval_mask[r] != 0, rs = reset && reset[r] != 0;
+        for (int j = 0; j < nout; ++j) {
+            const int64_t i = r * nout + j;
+            double x = kind == kExploreOU && !rs ? ou_x[i] : 0.0;
+            out[i] = explore_one(kind, act[i], normals[i], sigma, theta, mu, dt, sqdt, rs, ev, low[j], high[j], x);
+            if (kind == kExploreOU && (rs || !ev)) ou_x[i] = x;
+        }
+    }
+    if (state_out) {
+        const double sg = state_in[0] * decay;
+        state_out[0] = sg > sigma_min ? sg : sigma_min;  // max(sigma * decay, sigma_min)
+        state_out[1] = state_in[1] + 1.0;
+    }
+    return 0;
 }
 
 extern "C" int f110_ddpg_actor_head_bwd(const float *h, const float *W, const float *t, const float *scale,

@@ -1376,4 +1376,32 @@ F110_HD void episode_totals_add(f110_episode_totals &t, const EpisodePart &b) {
     t.return_max = a.mx;
 }
 
+// ---------------------------------------------------- exploration head rows --
+// One output of one row of f110_ddpg_actor_explore_env (include/f110.h; k_head_fwd's kExploreEnv
+// epilogue and f110_host_explore_rows both call it): act the deterministic action, n the N(0,1) draw,
+// x the OU state of (row, output) (kind 1; unused for kind 0).  sqdt = sqrt(dt), taken on the host
+// once (np.sqrt(self.dt)).  Returns the action.
+//   reset  zeroes x first, on every row;
+//   eval   the action is act, no draw used, x untouched (agent.py `if not training: return action`);
+//   kind 0 GaussianActionNoise.__call__ (agent.py:520-539) in f32, kExplore's operations;
+//   kind 1 OUActionNoise.__call__ (agent.py:490-505) in f64, left to right, no FMA: the state is
+//          float64 after its first call, the draw a float32 (mu = 0: the first call's float32 drift
+//          is an exact 0 either way).
+constexpr int kExploreGaussian = 0, kExploreOU = 1;
+
+F110_HD float explore_one(int kind, float act, float n, double sigma, double theta, double mu, double dt, double sqdt,
+                          bool reset, bool eval, float lo, float hi, double &x) {
+    if (reset) x = 0.0;
+    if (eval) return act;
+    if (kind == kExploreGaussian) {
+        float v = act + (float)sigma * n;
+        v = v < lo ? lo : v;
+        v = v > hi ? hi : v;
+        return v;
+    }
+    const double dx = theta * (mu - x) * dt + (sigma * sqdt) * (double)n;
+    x = x + dx;
+    return (float)clip((double)act + x, (double)lo, (double)hi);
+}
+
 }  // namespace f110

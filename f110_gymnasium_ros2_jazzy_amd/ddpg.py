@@ -22,6 +22,7 @@ collectives.  Ranks start from rank 0's weights and stay identical.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Sequence
 
@@ -321,7 +322,8 @@ class DDPGLearner:
                  alpha: float = 0.6, beta: float = 0.4, priority_epsilon: float = 1e-5,
                  noise_sigma_start: float = 0.2, noise_sigma_min: float = 0.05, noise_decay: float = 0.999,
                  seed: int = 42, device="cuda:0", replay="device", process_group=None, max_add: int | None = None,
-                 check_finite: bool = False, path: str | None = None, graphs: bool = False):
+                 check_finite: bool = False, path: str | None = None, graphs: bool = False,
+                 noise_type: str = "gaussian", ou_theta: float = 0.15, ou_mu: float = 0.0, ou_dt: float = 1.0):
         self.device = torch.device(device)
         self.tuned_gemms = enable_tuned_gemms(self.device)
         self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
@@ -408,6 +410,16 @@ class DDPGLearner:
         self._noise_state = torch.tensor([[self.sigma, 0.0]] * 2, dtype=torch.float64, device=self.device)
         self._noise_slot = 0
         self._noise_dev = (self.sigma, 0)  # what the current slot holds
+        # noise_type "ou": OUActionNoise (agent.py:469-505, its defaults :474) with one float64 state
+        # row per env, on the device so a captured step graph carries it from step to step
+        if noise_type not in ("gaussian", "ou"):
+            raise ValueError(f"noise_type must be 'gaussian' or 'ou'; got {noise_type!r}")
+        self.noise_type = noise_type
+        self.ou_theta, self.ou_mu, self.ou_dt = float(ou_theta), float(ou_mu), float(ou_dt)
+        if not all(math.isfinite(v) for v in (self.ou_theta, self.ou_mu, self.ou_dt)) or self.ou_dt < 0:
+            raise ValueError("ou_theta, ou_mu and ou_dt must be finite and ou_dt >= 0")
+        self.ou_x = torch.zeros(int(max_add or 0), self.act_dim, dtype=torch.float64, device=self.device) \
+            if noise_type == "ou" else None  # (without max_add: the first training call's rows)
         self._ready = False
         self.global_step = 0
 
@@ -589,23 +601,62 @@ class DDPGLearner:
         self.global_step += 1
         return self._graph_out
 
-    def choose_action(self, obs, training: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
+    def _row_mask(self, m, n, what):
+        """eval_mask / reset as a contiguous uint8 [n] device tensor (as it is when it already is one:
+        a captured step graph reads the caller's buffer)."""
+        if m is None:
+            return None
+        m = torch.as_tensor(m, device=self.device)
+        if m.dtype == torch.bool and m.is_contiguous():
+            m = m.view(torch.uint8)
+        elif m.dtype != torch.uint8 or not m.is_contiguous():
+            m = m.to(torch.uint8).contiguous()
+        if m.shape != (n,):
+            raise ValueError(f"choose_action: {what} must have {n} entries; got {tuple(m.shape)}")
+        return m
+
+    def _ou_state(self, n):
+        """The OU state's first n rows (allocated once: max_add rows, or the first call's)."""
+        if self.ou_x is None or self.ou_x.shape[0] == 0:
+            self.ou_x = torch.zeros(n, self.act_dim, dtype=torch.float64, device=self.device)
+        if n > self.ou_x.shape[0]:
+            raise ValueError(f"choose_action: {n} rows, but the OU state has {self.ou_x.shape[0]} (max_add)")
+        return self.ou_x
+
+    def choose_action(self, obs, training: bool = True, out: torch.Tensor | None = None, eval_mask=None,
+                      reset=None) -> torch.Tensor:
         """agent.py:350-370 for obs [N, obs_dim] (or [obs_dim]): actor output,
-        plus N(0, sigma^2) noise clipped to [low, high] when training; sigma
-        decays once per call (GaussianActionNoise.__call__, :520-539).  On the
+        plus noise clipped to [low, high] when training; sigma decays once per
+        call.  noise_type "gaussian": N(0, sigma^2) (GaussianActionNoise.__call__,
+        :520-539); "ou": each row's own Ornstein-Uhlenbeck state (OUActionNoise.__call__,
+        :490-505; self.ou_x, float64 [rows, act_dim]).  On the
         explicit path a training call is one launch after the hidden layers
         (the head draws the noise and clips) and may write into out, a
-        [N, act_dim] float32 view with unit column stride (e.g. the env's action rows)."""
+        [N, act_dim] float32 view with unit column stride (e.g. the env's action rows).
+        eval_mask (u8 / bool [N]): rows that get the actor's action as it is in a
+        training call -- no noise, no clip, their OU state untouched (`training=False`
+        for those rows).  reset (u8 / bool [N]): rows whose OU state starts from 0
+        in this call (OUActionNoise.reset), eval rows included."""
         with torch.no_grad(), TunedGemms(self.tuned_gemms):
             o = torch.as_tensor(obs, device=self.device, dtype=torch.float32)
+            per_row = training and (self.noise_type == "ou" or eval_mask is not None or reset is not None)
+            if per_row:
+                N = o.shape[0] if o.dim() == 2 else 1
+                eval_mask = self._row_mask(eval_mask, N, "eval_mask")
+                reset = self._row_mask(reset, N, "reset")
             if self.explicit is not None and training and o.dim() == 2:
                 s = self._noise_slot
                 if self._noise_dev != (self.sigma, self._noise_calls):  # the host changed sigma: upload it
                     self._noise_state[s, 0] = self.sigma
                     self._noise_state[s, 1] = float(self._noise_calls)
+                rows = None
+                if per_row:  # f110_ddpg_actor_explore_env; Gaussian without masks stays on f110_ddpg_actor_explore
+                    ou = self.noise_type == "ou"
+                    rows = (1 if ou else 0, self._ou_state(N) if ou else None, self.ou_theta, self.ou_mu, self.ou_dt,
+                            reset, eval_mask)
                 a = self.explicit.policy(self.actor, o, explore=(
                     self._noise_state[s], self._noise_state[1 - s], self.noise_decay, self.sigma_min, self._low32,
-                    self._high32, self._noise_key, out))
+                    self._high32, self._noise_key, out), rows=rows)
                 self.noise_advance()
                 return a
             if self.explicit is not None:
@@ -614,9 +665,25 @@ class DDPGLearner:
                     a = a.squeeze(0)
             else:
                 a = self.actor(o)
-            if training:
+            if training and not per_row:
                 noise = torch.randn(a.shape, generator=self._noise_gen, device=self.device) * self.sigma
                 a = torch.clamp(a + noise, self._low, self._high)
+                self.sigma = max(self.sigma * self.noise_decay, self.sigma_min)
+            elif training:  # the per-row head's semantics (include/f110.h) in torch
+                a2 = a if a.dim() == 2 else a.unsqueeze(0)
+                n = torch.randn(a2.shape, generator=self._noise_gen, device=self.device)
+                if self.noise_type == "ou":
+                    x = self._ou_state(N)[:N]
+                    if reset is not None:
+                        x[reset.bool()] = 0.0
+                    drift = self.ou_theta * (self.ou_mu - x) * self.ou_dt
+                    xn = x + (drift + (self.sigma * math.sqrt(self.ou_dt)) * n.double())
+                    noisy = torch.clamp(a2.double() + xn, self._low.double(), self._high.double()).to(a2.dtype)
+                    x.copy_(xn if eval_mask is None else torch.where(eval_mask.bool()[:, None], x, xn))
+                else:
+                    noisy = torch.clamp(a2 + n * self.sigma, self._low, self._high)
+                a2 = noisy if eval_mask is None else torch.where(eval_mask.bool()[:, None], a2, noisy)
+                a = a2 if a.dim() == 2 else a2.squeeze(0)
                 self.sigma = max(self.sigma * self.noise_decay, self.sigma_min)
         if out is not None:
             out.copy_(a)
@@ -646,7 +713,7 @@ class DDPGLearner:
             "actor_optim": self.actor_optim.state_dict(), "critic_optim": self.critic_optim.state_dict(),
             "action_low": self.action_low.tolist(), "action_high": self.action_high.tolist(),
             "gamma": self.gamma, "tau": self.tau, "obs_dim": self.obs_dim, "act_dim": self.act_dim,
-            "global_step": self.global_step, "torch_version": torch.__version__,
+            "global_step": self.global_step, "torch_version": str(torch.__version__),  # (a plain str: load_model's weights_only loader)
         }, os.path.join(self.path, filename))
 
     def load_model(self, filename: str = "ddpg_checkpoint.pt") -> bool:

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -183,3 +184,58 @@ def relu_bwd(gy, y, need_db: bool = True):
     _lib.check(L.f110_ddpg_relu_bwd(_p(gy), _p(y), B, K, _p(gz), _p(db), _p(scratch), _stream(y)),
                "f110_ddpg_relu_bwd")
     return gz, db
+
+
+def actor_explore_env(h, W, b, scale, shift, state_in, state_out, decay, sigma_min, low, high, seed, out, kind=0,
+                      ou_x=None, theta=0.15, mu=0.0, dt=1.0, reset=None, eval_mask=None, normals_ext=None):
+    """f110_ddpg_actor_explore_env (include/f110.h) on device tensors: the actor's last layer with
+    per-row exploration -- Gaussian (kind 0) or OU (kind 1, ou_x float64 [B, nout] read and written)
+    noise, reset / eval_mask uint8 [B] or None, normals_ext float32 [B, nout] or None -- written
+    into out ([B, nout] float32, rows may be strided).  No autograd (choose_action)."""
+    _check(h, W, b)
+    B, K = h.shape
+    n = W.shape[0]
+    if out.shape != (B, n) or out.stride(1) != 1 or out.dtype != torch.float32:
+        raise _lib.F110Error("actor_explore_env: out must be [B, nout] float32 with unit column stride")
+    for name, t, dt_, shape in (("ou_x", ou_x, torch.float64, (B, n)), ("reset", reset, torch.uint8, (B,)),
+                                ("eval_mask", eval_mask, torch.uint8, (B,)),
+                                ("normals_ext", normals_ext, torch.float32, (B, n))):
+        if t is not None and (t.dtype != dt_ or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+            raise _lib.F110Error(f"actor_explore_env: {name} must be a contiguous device {dt_} tensor {shape}")
+    h, W = h.contiguous(), W.contiguous()
+    _lib.check(_lib.load().f110_ddpg_actor_explore_env(
+        _p(h), _p(W), _p(b), _p(scale), _p(shift), B, K, n, _p(state_in), _p(state_out),
+        float(decay), float(sigma_min), _p(low), _p(high), int(seed), _p(out), out.stride(0), int(kind), _p(ou_x),
+        float(theta), float(mu), float(dt), _p(reset), _p(eval_mask), _p(normals_ext), _stream(h)),
+        "f110_ddpg_actor_explore_env")
+    return out
+
+
+def host_explore_rows(act, normals, kind, ou_x, sigma, low, high, theta=0.15, mu=0.0, dt=1.0, reset=None,
+                      eval_mask=None, decay=1.0, sigma_min=0.0, call=0):
+    """f110_host_explore_rows over NumPy arrays: the per-row epilogue of f110_ddpg_actor_explore_env
+    on the CPU, on given actions act [n, nout] float32 and draws normals [n, nout] float32; ou_x
+    (float64 [n, nout], kind 1) is updated in place.  Returns (out [n, nout] float32, the decayed
+    (sigma, call index) pair)."""
+    act = np.ascontiguousarray(act, np.float32)
+    n, nout = act.shape
+    normals = np.ascontiguousarray(normals, np.float32)
+    low, high = np.ascontiguousarray(low, np.float32), np.ascontiguousarray(high, np.float32)
+    if normals.shape != act.shape or low.shape != (nout,) or high.shape != (nout,):
+        raise ValueError("host_explore_rows: normals must match act, low / high must have nout entries")
+    if ou_x is not None and (ou_x.dtype != np.float64 or ou_x.shape != act.shape or not ou_x.flags.c_contiguous):
+        raise ValueError("host_explore_rows: ou_x must be a C-contiguous float64 array shaped like act")
+    masks = []
+    for m in (reset, eval_mask):
+        m = None if m is None else np.ascontiguousarray(m, np.uint8)
+        if m is not None and m.shape != (n,):
+            raise ValueError("host_explore_rows: reset / eval_mask must have one entry per row")
+        masks.append(m)
+    st_in, st_out = np.array([sigma, float(call)], np.float64), np.zeros(2, np.float64)
+    out = np.empty_like(act)
+    P = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    _lib.check(_lib.load().f110_host_explore_rows(P(act), P(normals), n, nout, int(kind), P(ou_x), float(theta),
+                                                  float(mu), float(dt), P(masks[0]), P(masks[1]), P(st_in), P(st_out),
+                                                  float(decay), float(sigma_min), P(low), P(high), P(out)),
+               "f110_host_explore_rows")
+    return out, (float(st_out[0]), float(st_out[1]))

@@ -154,14 +154,19 @@ class ExplicitUpdate:
                  M, dev, loss=(part, -1.0, loss))
         return loss
 
-    def policy(self, actor, obs, explore=None):
+    def policy(self, actor, obs, explore=None, rows=None):
         """Actor.forward without autograd (choose_action): fc1, fc2, head.
         explore = (state_in, state_out, decay, sigma_min, low, high, seed, out):
         the head adds sigma * N(0, 1) and clips to [low, high]
         (f110_ddpg_actor_explore; sigma and the call index from the f64 device
         pair state_in, the decayed pair written to state_out), writing the
         actions into out (rows may be strided; None: a new tensor), which is
-        returned."""
+        returned.
+        rows = (kind, ou_x, theta, mu, dt, reset, eval_mask): the per-row head
+        instead (f110_ddpg_actor_explore_env): Gaussian (0) or OU (1) noise
+        with the f64 state ou_x [>= M, act_dim], rows with reset != 0 start
+        from x = 0, rows with eval_mask != 0 get the actor's action as it is
+        (reset, eval_mask: u8 [M] or None)."""
         obs = obs.contiguous()
         M = obs.shape[0]
         h1, h2 = self._e(M), self._e(M)
@@ -177,6 +182,21 @@ class ExplicitUpdate:
             out = self._e(M, n)
         if out.shape != (M, n) or out.stride(1) != 1 or out.dtype != torch.float32:
             raise ValueError("policy: out must be [M, act_dim] float32 with unit column stride")
+        if rows is not None:
+            kind, ou_x, theta, mu, dt, reset, eval_mask = rows
+            for name, m in (("reset", reset), ("eval_mask", eval_mask)):
+                if m is not None and (m.dtype != torch.uint8 or m.shape != (M,) or not m.is_contiguous()):
+                    raise ValueError(f"policy: {name} must be a contiguous uint8 [M] tensor")
+            if kind == 1 and (ou_x is None or ou_x.dtype != torch.float64 or ou_x.dim() != 2 or ou_x.shape[0] < M
+                              or ou_x.shape[1] != n or not ou_x.is_contiguous()):
+                raise ValueError("policy: ou_x must be a contiguous float64 [>= M, act_dim] tensor")
+            P = lambda t: None if t is None else _p(t)  # noqa: E731
+            _lib.check(self.L.f110_ddpg_actor_explore_env(
+                _p(h2), _p(W), _p(b), _p(scale), _p(shift), M, h2.shape[1], n, _p(st_in), _p(st_out), float(decay),
+                float(sigma_min), _p(low), _p(high), int(seed), _p(out), out.stride(0), int(kind), P(ou_x),
+                float(theta), float(mu), float(dt), P(reset), P(eval_mask), None, _stream(h2)),
+                "f110_ddpg_actor_explore_env")
+            return out
         _lib.check(self.L.f110_ddpg_actor_explore(_p(h2), _p(W), _p(b), _p(scale), _p(shift), M, h2.shape[1], n,
                                                   _p(st_in), _p(st_out), float(decay), float(sigma_min), _p(low),
                                                   _p(high), int(seed), _p(out), out.stride(0), _stream(h2)),

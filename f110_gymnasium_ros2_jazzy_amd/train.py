@@ -3,7 +3,8 @@
 
 Per vector step, everything on the device:
   ego action    random U(low, high) during warm-up (:162-163), else the actor
-                + Gaussian noise (:165)
+                + Gaussian or OU noise (:165); the last `eval_envs` envs are
+                evaluation envs (:158-165): the actor's action, noise-free, from step 0
   opponent      gap_follow_action on its previous scan (:168), inside F110VectorEnv
   env.step      (:174) with device autoreset (gymnasium NEXT_STEP)
   reward        CenterlineSafetyProgressReward (:127-146, :179) on the device
@@ -40,30 +41,44 @@ class VectorTrainer:
     def __init__(self, envs_per_rank: int, map_name: str = "Spielberg_map", batch_size: int = 4096,
                  memory_size: int = 1 << 20, warmup_steps: int = 1000, updates_per_step: int = 1, seed: int = 42,
                  device=None, env_offset: int = 0, rank_seed: int = 0, graphs: bool = True,
-                 max_episode_steps: int | None = None, stall_speed: float = 0.0, stall_steps: int | None = None):
+                 max_episode_steps: int | None = None, stall_speed: float = 0.0, stall_steps: int | None = None,
+                 noise_type: str = "gaussian", eval_envs: int = 0, ou_reset: bool = False):
         from .ddpg import DDPGLearner
         from .maps import MAP_DIR
         from .reward import BatchedCenterlineReward, CenterlineTrack
         from .vector_env import F110VectorEnv
         self.device = torch.device(device or f"cuda:{torch.cuda.current_device()}")
         self.N = int(envs_per_rank)
+        self.eval_envs = int(eval_envs)
+        if not 0 <= self.eval_envs < self.N:
+            raise ValueError(f"eval_envs must be in [0, {self.N}); got {eval_envs}")
+        self.ou_reset = bool(ou_reset)
         cl = np.load(os.path.join(MAP_DIR, map_name.replace("_map", "") + "_centerline.npz"))
         self.track = CenterlineTrack(cl["xy"], cl["w_right"], cl["w_left"], device=self.device.index or 0)
         self.reward_fn = BatchedCenterlineReward(self.N, dt=0.01, progress=self.track, device=self.device,
                                                  **REWARD_KW)
         # episode limits (device truncation): with any of them on the env also keeps the episode
         # statistics on the device (one kernel pair per step, inside the step graphs)
-        self.episode_stats = bool(max_episode_steps or stall_steps)
+        # With evaluation envs the trainer keeps the statistics itself, one EpisodeStats over the
+        # training rows and one over the eval rows (contiguous row ranges of the step's buffers)
+        self.episode_stats = bool(max_episode_steps or stall_steps or self.eval_envs)
         self.env = F110VectorEnv(self.N, map=map_name, num_agents=2, seed=seed, device=self.device,
                                  env_offset=env_offset, opponent="gap_follow", reward_fn=self.reward_fn,
                                  infos="minimal", max_episode_steps=max_episode_steps, stall_speed=stall_speed,
-                                 stall_steps=stall_steps, episode_stats=self.episode_stats)
+                                 stall_steps=stall_steps, episode_stats=self.episode_stats and not self.eval_envs)
+        self.train_stats = self.eval_stats = self._eval_mask = None
+        if self.eval_envs:
+            from .episode import EpisodeStats
+            self.train_stats = EpisodeStats(self.N - self.eval_envs, device=self.device)
+            self.eval_stats = EpisodeStats(self.eval_envs, device=self.device)
+            self._eval_mask = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
+            self._eval_mask[self.N - self.eval_envs:] = 1
         self.agent = DDPGLearner(obs_dim=self.env.single_observation_space.shape[0], act_dim=2,
                                  action_low=ACTION_LOW, action_high=ACTION_HIGH, gamma=0.99, tau=0.005,
                                  actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size,
                                  alpha=0.6, beta=0.4, priority_epsilon=1e-5, noise_sigma_start=0.20,
                                  noise_sigma_min=0.02, noise_decay=0.9995, seed=seed, device=self.device,
-                                 max_add=self.N, graphs=graphs)
+                                 max_add=self.N, graphs=graphs, noise_type=noise_type)
         self.warmup = int(warmup_steps)
         self.updates_per_step = int(updates_per_step)
         # HIP graphs per vector step once the learner's eager warm-up updates are done (explicit
@@ -89,15 +104,14 @@ class VectorTrainer:
         if self.global_step < self.warmup:  # :162-163
             u = torch.rand(self.N, 2, generator=self._gen, device=self.device)
             act = self._low + u * (self._high - self._low)
+            if self.eval_envs:  # an eval episode bypasses the warm-up's random actions (:160-165)
+                k = self.N - self.eval_envs
+                act[k:] = self.agent.choose_action(self.obs, training=False)[k:]
         elif self._graph_ready():
             return self._step_graphed()
         else:  # the actions land in the env's action rows (no copy in the step)
-            act = self.agent.choose_action(self.obs, training=True, out=self.env.agent_actions())
-        next_obs, rew, term, was_reset = self.env.step_transition(act)
-        # NEXT_STEP autoreset: a reset row's obs is the previous episode's last
-        # observation and its next_obs the new episode's first -- not a transition
-        # (remember_env skips the rows with was_reset != 0)
-        self.agent.remember_env(self.obs, act, rew, next_obs, term, was_reset)
+            act = self._explore(self.obs)
+        next_obs, rew, term, was_reset = self._transition(self.obs, act, None)
         if self.global_step >= self.warmup:
             for _ in range(self.updates_per_step):
                 self.last = self.agent.replay()
@@ -110,14 +124,36 @@ class VectorTrainer:
         return (self.step_graphs and ag.explicit is not None and ag.graphs and self.updates_per_step == 1 and
                 ag._ready and ag._eager_left == 0 and ag._graphs is None and self.env.agent_actions() is not None)
 
+    def _explore(self, obs):
+        """The step's actions into the env's action rows: the eval rows noise-free, the others with
+        the learner's noise; with ou_reset the rows the previous step reset start from x = 0 (the
+        simulator's was_reset buffer, which this step's env.step rewrites only afterwards)."""
+        reset = self.env.sim.out.was_reset if self.ou_reset else None
+        return self.agent.choose_action(obs, training=True, out=self.env.agent_actions(), eval_mask=self._eval_mask,
+                                        reset=reset)
+
+    def _transition(self, obs_in, act, obs_out):
+        """env.step, the episode statistics of the two row ranges (eval_envs > 0) and remember."""
+        nxt, rew, term, was_reset = self.env.step_transition(act, obs_out=obs_out)
+        if self.eval_envs:
+            k = self.N - self.eval_envs
+            trunc = self.env.truncated
+            self.train_stats.update(rew[:k], term[:k], None if trunc is None else trunc[:k], was_reset[:k])
+            self.eval_stats.update(rew[k:], term[k:], None if trunc is None else trunc[k:], was_reset[k:])
+        # NEXT_STEP autoreset: a reset row's obs is the previous episode's last
+        # observation and its next_obs the new episode's first -- not a transition
+        # (remember_env skips the rows with was_reset != 0); eval transitions are stored like any
+        # other (train_ddpg.py:184 remembers unconditionally)
+        self.agent.remember_env(obs_in, act, rew, nxt, term, was_reset)
+        return nxt, rew, term, was_reset
+
     def _head(self, obs_in, obs_out, phase_a):
         """A vector step after the warm-up up to the first all-reduce, as captured:
         choose_action (noise in the head launch), env step + reward, replay add,
         the learner update's first phase (sample, critic loss and gradients)."""
         ag = self.agent
-        act = ag.choose_action(obs_in, training=True, out=self.env.agent_actions())
-        nxt, rew, term, was_reset = self.env.step_transition(act, obs_out=obs_out)
-        ag.remember_env(obs_in, act, rew, nxt, term, was_reset)
+        act = self._explore(obs_in)
+        _, rew, term, _ = self._transition(obs_in, act, obs_out)
         phase_a()
         return rew, term
 
@@ -193,10 +229,18 @@ class VectorTrainer:
 
 def episode_report(tr: VectorTrainer, world: int = 1) -> dict:
     """The episodes finished since the last report, summed over ranks on the host (print time only),
-    then cleared: episodes, episode_return_mean, episode_length_mean."""
-    t = tr.env.episode_totals()
-    tr.env.reset_episode_totals()
+    then cleared: episodes, episode_return_mean, episode_length_mean.  With evaluation envs these
+    three cover the training rows, and eval_episodes, eval_return_mean, eval_length_mean the eval rows."""
+    if tr.eval_envs:
+        t, te = tr.train_stats.totals(), tr.eval_stats.totals()
+        tr.train_stats.reset_totals()
+        tr.eval_stats.reset_totals()
+    else:
+        t, te = tr.env.episode_totals(), None
+        tr.env.reset_episode_totals()
     v = [float(t["episodes"]), float(t["return_sum"]), float(t["length_sum"])]
+    if te is not None:
+        v += [float(te["episodes"]), float(te["return_sum"]), float(te["length_sum"])]
     if world > 1:
         import torch.distributed as dist
         w = torch.tensor(v, dtype=torch.float64)
@@ -205,8 +249,13 @@ def episode_report(tr: VectorTrainer, world: int = 1) -> dict:
         dist.all_reduce(w)
         v = w.tolist()
     n = int(v[0])
-    return {"episodes": n, "episode_return_mean": v[1] / n if n else None,
-            "episode_length_mean": v[2] / n if n else None}
+    rep = {"episodes": n, "episode_return_mean": v[1] / n if n else None,
+           "episode_length_mean": v[2] / n if n else None}
+    if te is not None:
+        m = int(v[3])
+        rep.update(eval_episodes=m, eval_return_mean=v[4] / m if m else None,
+                   eval_length_mean=v[5] / m if m else None)
+    return rep
 
 
 def main():
@@ -221,6 +270,10 @@ def main():
     ap.add_argument("--max-episode-steps", type=int, default=0, help="time limit per episode in steps (0: none)")
     ap.add_argument("--stall-speed", type=float, default=0.0, help="ego speed below which a step counts as standing")
     ap.add_argument("--stall-steps", type=int, default=0, help="standing steps in a row that truncate (0: none)")
+    ap.add_argument("--noise", choices=("gaussian", "ou"), default="gaussian", help="exploration noise")
+    ap.add_argument("--eval-envs", type=int, default=0, help="noise-free evaluation envs per GPU (the last K)")
+    ap.add_argument("--ou-reset", action="store_true", help="zero an env's OU state when its episode resets")
+    ap.add_argument("--save-dir", default=None, help="rank 0 saves best.pt here when eval_return_mean improves")
     args = ap.parse_args()
     rank, world, local = D.init()
     torch.cuda.set_device(D.local_device_index(local))
@@ -228,7 +281,9 @@ def main():
     tr = VectorTrainer(shard.count, batch_size=args.batch, memory_size=args.memory, warmup_steps=args.warmup,
                        updates_per_step=args.updates_per_step, seed=args.seed, env_offset=shard.offset,
                        rank_seed=rank, max_episode_steps=args.max_episode_steps, stall_speed=args.stall_speed,
-                       stall_steps=args.stall_steps)
+                       stall_steps=args.stall_steps, noise_type=args.noise, eval_envs=args.eval_envs,
+                       ou_reset=args.ou_reset)
+    best = -float("inf")
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)
     for k in range(args.steps):
@@ -236,6 +291,11 @@ def main():
         ret += rew
         if (k + 1) % 500 == 0:
             ep = episode_report(tr, world) if tr.episode_stats else {}  # (every rank: a host all-reduce)
+            ev = ep.get("eval_return_mean")
+            if rank == 0 and args.save_dir and ev is not None and ev > best:  # train_ddpg.py:213-216, batched
+                best = ev
+                tr.agent.path = args.save_dir
+                tr.agent.save_model("best.pt")
             if rank == 0:
                 st = tr.last or {}
                 print(json.dumps({"step": k + 1,

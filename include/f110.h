@@ -543,6 +543,34 @@ F110_API int f110_ddpg_actor_explore(const float *h, const float *W, const float
                                      const float *shift, int32_t B, int32_t K, int32_t nout, const double *state_in,
                                      double *state_out, double decay, double sigma_min, const float *low,
                                      const float *high, uint64_t seed, float *out, int64_t out_stride, void *stream);
+/* f110_ddpg_actor_explore per row: a batch whose rows are envs, some exploring and some evaluating,
+ * with GaussianActionNoise (kind 0) or OUActionNoise (kind 1, agent.py:469-505).  The leading
+ * arguments, the (sigma, call index) pair and its decay are f110_ddpg_actor_explore's; act below is
+ * scale[j] * tanh(z) + shift[j], f110_ddpg_actor_head's value bit for bit.  Per row r, output j:
+ *  - reset[r] != 0 (reset: [B] u8 or NULL) zeroes the row's ou_x first -- on every row, eval rows too;
+ *  - eval_mask[r] != 0 ([B] u8 or NULL): out = act, unclipped, no draw used, ou_x untouched
+ *    (`if not training: return action`);
+ *  - the draw n = normals_ext[r * nout + j] (normals_ext: [B][nout] f32 caller-supplied N(0,1), or
+ *    NULL), else f110_ddpg_actor_explore's own draw for (seed, call index, r, j): keys are by row, so
+ *    eval rows do not shift the other rows' draws;
+ *  - kind 0: out = clip(act + (float)sigma * n, low[j], high[j]) in f32, f110_ddpg_actor_explore's
+ *    operations (with reset, eval_mask and normals_ext NULL the two entry points agree bit for bit);
+ *  - kind 1: in f64, left to right, no FMA, with x = ou_x[r][j] (ou_x: [B][nout] f64, read and
+ *    written; required):  dx = theta * (mu - x) * dt + (sigma * sqrt(dt)) * (double)n;  x' = x + dx,
+ *    stored back;  out = (float)clip((double)act + x', (double)low[j], (double)high[j]).  This is
+ *    OUActionNoise.__call__ as NumPy evaluates it (a float64 state after the first call, a float32
+ *    draw) for mu = 0, the only value the reference constructs.
+ * NaN stays NaN.  state_out is written once per launch whatever the masks hold: a caller with no
+ * exploring row uses f110_ddpg_actor_head.  F110_E_INVALID before any device call for kind outside
+ * {0, 1}, kind 1 without ou_x, dt < 0, a non-finite theta / mu / dt, state_in == state_out, or a bad
+ * shape (K <= 255, nout <= 4, B > 0). */
+F110_API int f110_ddpg_actor_explore_env(const float *h, const float *W, const float *b, const float *scale,
+                                         const float *shift, int32_t B, int32_t K, int32_t nout,
+                                         const double *state_in, double *state_out, double decay, double sigma_min,
+                                         const float *low, const float *high, uint64_t seed, float *out,
+                                         int64_t out_stride, int32_t kind, double *ou_x, double theta, double mu,
+                                         double dt, const uint8_t *reset, const uint8_t *eval_mask,
+                                         const float *normals_ext, void *stream);
 /* The critic update's head in one launch: y = r + gamma (1 - d) (ht Wt^T + bt) (the target critic),
  * td = y - (h W^T + b), part[blk] = block sums of w td^2 (f110_ddpg_row_blocks(B) floats; the loss
  * is sum(part) / B: f110_learner_wgrad_loss), dq = -((g / B) w) (2 td) (may be null), dh = dq W where

@@ -268,6 +268,19 @@ F110_API int f110_host_episode_stats(const double *rewards, const uint8_t *termi
                                      double *last_return, int32_t *last_length, uint8_t *finished,
                                      f110_episode_totals *totals);
 
+/* f110_ddpg_actor_explore_env's per-row epilogue over HOST arrays: the same function the kernel runs
+ * (explore_one, csrc/f110_device.h), on given actions act [n_rows][nout] f32 (f110_ddpg_actor_head's
+ * act) and given draws normals [n_rows][nout] f32.  ou_x, reset, eval_mask, kind, theta / mu / dt,
+ * low / high, the {sigma, call index} pair state_in and decay / sigma_min as there; writes out
+ * [n_rows][nout] (packed), updates ou_x and, when state_out is not NULL, writes the decayed pair.
+ * Same validation (F110_E_INVALID).  Host test hook: the CPU suite and the GPU tests share one
+ * statement of the semantics. */
+F110_API int f110_host_explore_rows(const float *act, const float *normals, int64_t n_rows, int32_t nout,
+                                    int32_t kind, double *ou_x, double theta, double mu, double dt,
+                                    const uint8_t *reset, const uint8_t *eval_mask, const double *state_in,
+                                    double *state_out, double decay, double sigma_min, const float *low,
+                                    const float *high, float *out);
+
 #ifdef __cplusplus
 }
 #endif
