@@ -119,6 +119,8 @@ EXPORTS = [
     "f110_learner_gemm", "f110_learner_wgrad_scratch_floats", "f110_learner_wgrad", "f110_learner_wgrad_loss",
     "f110_ddpg_critic_step", "f110_ddpg_q_mean_step", "f110_ddpg_row_blocks",
     "f110_ddpg_actor_explore_env", "f110_host_explore_rows",
+    "f110_nstep_create", "f110_nstep_destroy", "f110_nstep_push", "f110_nstep_reset", "f110_nstep_arrays",
+    "f110_host_nstep",
 ]
 
 _lib = None
@@ -271,6 +273,12 @@ def load(build_if_missing: bool = True):
                                                                                        _P, _P]
     L.f110_host_explore_rows.argtypes = [_P, _P, i64, i32, i32, _P, f64, f64, f64, _P, _P, _P, _P, f64, f64, _P, _P,
                                          _P]
+    L.f110_nstep_create.argtypes = [ctypes.POINTER(_P), i32, i64, i32, f64, i32, i32]
+    L.f110_nstep_destroy.argtypes = [_P]
+    L.f110_nstep_push.argtypes = [_P, _P, _P, i64, _P, i64, _P, _P, i64, _P, _P, _P, _P]
+    L.f110_nstep_reset.argtypes = [_P, _P, _P]
+    L.f110_nstep_arrays.argtypes = [_P] + [ctypes.POINTER(_P)] * 6
+    L.f110_host_nstep.argtypes = [i64, i32, f64, i32, i32, i64] + [_P] * 18 + [ctypes.POINTER(i64)]
     L.f110_ddpg_actor_head_bwd.argtypes = [_P] * 5 + [i32] * 3 + [_P] * 6
     L.f110_ddpg_td_target.argtypes = [_P] * 5 + [f32, i32, i32, _P, _P]
     L.f110_ddpg_critic_loss.argtypes = [_P] * 5 + [i32] * 2 + [_P] * 4

@@ -1404,4 +1404,61 @@ F110_HD float explore_one(int kind, float act, float n, double sigma, double the
     return (float)clip((double)act + x, (double)lo, (double)hi);
 }
 
+// ------------------------------------------------------- n-step returns --
+// One env's push into its n-step window (the semantics of include/f110.h, "n-step returns";
+// k_nstep_update and f110_host_nstep both call it).  The window is a ring of n slots: its len
+// pending entries sit at slots (head + i) % n, oldest first, each with a running return ret (f64)
+// and a reward count k; pw[i] = gamma^i as sequential products (pw[0] = 1).  r is this step's
+// reward.  Returns the number of emitted rows (0..n), oldest first; for row j
+//   e_slot[j]   the window slot that holds its (obs, act), or -1: this push's own (s, a);
+//   e_reward[j] (float)ret;  e_done[j] the effective done, 1 - gamma^(k-1) (1 - done).
+// store = the slot this push's (s, a) is to be written to, or -1 when it does not stay pending
+// (a reset row, or emitted by this very push).  A slot that is emitted is never the slot stored
+// to in the same push: the caller may move the rows of one push in any order.
+F110_HD int nstep_update(int n, const double *pw, double r, int term, int trunc, int was_reset, int32_t &len,
+                         int32_t &head, double *ret, int32_t *k, int32_t *e_slot, float *e_reward, float *e_done,
+                         int32_t &store) {
+    store = -1;
+    if (was_reset) {  // not a transition: whatever is pending belongs to an episode that is over
+        len = 0;
+        head = 0;
+        return 0;
+    }
+    int s = head;
+    for (int i = 0; i < len; ++i) {
+        const double p = pw[k[s]] * r;  // (product and sum kept apart: no FMA)
+        ret[s] = ret[s] + p;
+        k[s] += 1;
+        s = s + 1 == n ? 0 : s + 1;
+    }
+    const int ns = s;  // (head + len) % n: len < n before a push
+    ret[ns] = r;       // assigned, not 0.0 + r: -0.0 survives
+    k[ns] = 1;
+    len += 1;
+    if (term || trunc) {  // the episode ends: every pending entry leaves, with what it has
+        const int cnt = len;
+        s = head;
+        for (int j = 0; j < cnt; ++j) {
+            e_slot[j] = s == ns ? -1 : s;
+            e_reward[j] = (float)ret[s];
+            e_done[j] = term ? 1.0f : (float)(1.0 - pw[k[s] - 1]);
+            s = s + 1 == n ? 0 : s + 1;
+        }
+        len = 0;
+        head = 0;
+        return cnt;
+    }
+    if (len == n) {  // the oldest entry has its n rewards
+        e_slot[0] = head == ns ? -1 : head;
+        e_reward[0] = (float)ret[head];
+        e_done[0] = (float)(1.0 - pw[n - 1]);
+        if (head != ns) store = ns;  // (n == 1: the new entry itself left)
+        head = head + 1 == n ? 0 : head + 1;
+        len -= 1;
+        return 1;
+    }
+    store = ns;
+    return 0;
+}
+
 }  // namespace f110

@@ -383,6 +383,35 @@ hipError_t launch_replay_update(const ReplayView &v, const int64_t *idx, const f
 hipError_t prepare_replay(int32_t max_batch);
 int replay_grid(int64_t capacity);
 
+// ---- n-step accumulator in front of the ring (f110_replay.hip) -------------
+constexpr int kNstepMax = 16;
+struct NstepView {       // one f110_nstep (device)
+    int64_t n_envs;
+    int32_t n, obs_dim, act_dim;
+    const double *pw;    // [n + 1] gamma^i, sequential products
+    int32_t *len, *head; // [N] pending entries, slot of the oldest
+    double *ret;         // [N][n] running returns
+    int32_t *k;          // [N][n] rewards in ret
+    float *obs, *act;    // [N][n][D], [N][n][A] the pending entries' rows
+    // one push's scratch
+    int32_t *cnt;        // [N] rows the env emits
+    int32_t *store;      // [N] window slot this push's (s, a) goes to, or -1
+    int64_t *base;       // [N] ring slot of the env's first emitted row
+    int32_t *e_slot;     // [N][n] window slot of emitted row j (-1: this push's own row)
+    float *e_reward, *e_done;  // [N][n]
+};
+
+struct NstepRows {       // one push: n_envs raw step outputs (device)
+    const float *obs, *act, *next_obs;
+    const double *reward;
+    const uint8_t *terminated, *truncated, *was_reset;  // truncated may be null
+    int64_t obs_stride, act_stride, next_stride;
+    int32_t vec4;        // every row moved is 16-B aligned and obs_dim % 4 == 0
+};
+
+hipError_t launch_nstep_push(const ReplayView &v, const NstepView &w, const NstepRows &in, hipStream_t s);
+hipError_t launch_nstep_reset(const NstepView &w, const uint8_t *env_mask, hipStream_t s);
+
 // ---- flat Adam (f110_adam.hip) --------------------------------------------
 struct AdamArgs {
     float *param, *exp_avg, *exp_avg_sq;

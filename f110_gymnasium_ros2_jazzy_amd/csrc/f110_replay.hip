@@ -9,6 +9,9 @@
 //   add     (replay_buffer.py:48-71)   k_prio_max (per-block max priority)
 //           -> k_add_scan (one workgroup: the max, ring slots of the masked
 //           rows, their priority) -> k_add_copy (one block per row).
+//   n-step  (no reference counterpart)  f110_nstep_push: a per-env window of
+//           pending (s, a, running return) entries in front of the ring; a
+//           push emits 0..n rows per env, placed by a scan over the counts.
 //   sample  (replay_buffer.py:76-116)  Sampling WITHOUT replacement from
 //           p_i = (prio_i + eps)^alpha / sum_j (...) by the exponential race
 //           (Efraimidis-Spirakis): key_i = E_i / w_i with E_i ~ Exp(1); the B
@@ -228,6 +231,153 @@ __global__ void __launch_bounds__(kRB) k_add_copy(ReplayView v, ReplayRows in, i
         v.reward[slot] = in.reward64 ? (float)in.reward64[i] : in.reward[i];
         v.done[slot] = in.done ? (in.done[i] ? 1.0f : 0.0f) : 0.0f;
     }
+}
+
+// ------------------------------------------------------- n-step push -------
+// f110_nstep_push: k_nstep_update (one thread per env: nstep_update, f110_device.h) ->
+// k_prio_max -> k_nstep_scan (k_add_scan with a count per env in place of a 0/1 mask) ->
+// k_nstep_copy (one block per (env, emitted row), one more job per env for the window).
+__global__ void __launch_bounds__(kRB) k_nstep_update(NstepView w, NstepRows in) {
+    const int64_t e = (int64_t)blockIdx.x * kRB + threadIdx.x;
+    if (e >= w.n_envs) return;
+    const int n = w.n;
+    int32_t len = w.len[e], head = w.head[e], store;
+    const int cnt = nstep_update(n, w.pw, in.reward[e], in.terminated[e], in.truncated ? in.truncated[e] : 0,
+                                 in.was_reset[e], len, head, w.ret + e * n, w.k + e * n, w.e_slot + e * n,
+                                 w.e_reward + e * n, w.e_done + e * n, store);
+    w.len[e] = len;
+    w.head[e] = head;
+    w.cnt[e] = cnt;
+    w.store[e] = store;
+}
+
+// Ring slots of the emitted rows, by env ascending and oldest first within an env, as that many
+// add(priority=None) calls in this order would fill them: base[e] is the env's first slot, its
+// rows take consecutive ones (mod capacity).  Total rows <= n_envs * n <= capacity: no slot twice.
+__global__ void __launch_bounds__(kOneBlock) k_nstep_scan(ReplayView v, NstepView w, int n_part) {
+    __shared__ int64_t part[kOneBlock];
+    __shared__ uint32_t wmx[kOneBlock / 64];
+    __shared__ uint32_t mx;
+    const int t = threadIdx.x;
+    {  // the max priority from k_prio_max's partials (as k_add_scan)
+        uint32_t m = 0;
+        for (int k = t; k < n_part; k += kOneBlock) m = max(m, v.part[k]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+        if ((t & 63) == 0) wmx[t >> 6] = m;
+        __syncthreads();
+        if (t == 0) {
+            uint32_t b = wmx[0];
+            for (int q = 1; q < kOneBlock / 64; ++q) b = max(b, wmx[q]);
+            mx = b;
+        }
+    }
+    const int64_t N = w.n_envs;
+    const int64_t chunk = (N + kOneBlock - 1) / kOneBlock;
+    const int64_t r0 = min((int64_t)t * chunk, N), r1 = min(r0 + chunk, N);
+    int64_t cnt = 0;
+    for (int64_t e = r0; e < r1; ++e) cnt += w.cnt[e];
+    part[t] = cnt;
+    __syncthreads();
+    for (int o = 1; o < kOneBlock; o <<= 1) {  // inclusive scan of the chunks' row counts
+        const int64_t add = t >= o ? part[t - o] : 0;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    const int64_t total = part[kOneBlock - 1];
+    const int64_t rank = part[t] - cnt;
+    const int64_t cap = v.capacity, next = v.hdr->next;
+    const float p0 = add_priority(v.hdr->length, mx);
+    const double w0 = prio_weight(p0, v.eps, v.alpha);
+    int64_t slot = (next + rank) % cap;
+    for (int64_t e = r0; e < r1; ++e) {
+        w.base[e] = slot;
+        const int c = w.cnt[e];
+        for (int j = 0; j < c; ++j) {
+            v.prio[slot] = p0;
+            v.wt[slot] = w0;
+            slot = slot + 1 == cap ? 0 : slot + 1;
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        const int64_t len = v.hdr->length + total;
+        v.hdr->length = len < cap ? len : cap;
+        v.hdr->next = (next + total) % cap;
+    }
+}
+
+// Two rows of D floats, a -> da and b -> db (b == nullptr: one row): pairs of float4 per thread
+// with every load issued before the stores, as k_add_copy.
+__device__ __forceinline__ void copy_rows(const float *a, float *da, const float *b, float *db, int D, int vec4) {
+    if (vec4) {
+        const int D4 = D >> 2;
+        for (int k0 = threadIdx.x; k0 < D4; k0 += 2 * kRB) {
+            const int k1 = k0 + kRB;
+            const float4 a0 = reinterpret_cast<const float4 *>(a)[k0];
+            float4 b0, a1, b1;
+            if (b) b0 = reinterpret_cast<const float4 *>(b)[k0];
+            if (k1 < D4) {
+                a1 = reinterpret_cast<const float4 *>(a)[k1];
+                if (b) b1 = reinterpret_cast<const float4 *>(b)[k1];
+            }
+            reinterpret_cast<float4 *>(da)[k0] = a0;
+            if (b) reinterpret_cast<float4 *>(db)[k0] = b0;
+            if (k1 < D4) {
+                reinterpret_cast<float4 *>(da)[k1] = a1;
+                if (b) reinterpret_cast<float4 *>(db)[k1] = b1;
+            }
+        }
+    } else {
+        for (int k = threadIdx.x; k < D; k += kRB) {
+            const float x = a[k];
+            float y = 0.0f;
+            if (b) y = b[k];
+            da[k] = x;
+            if (b) db[k] = y;
+        }
+    }
+}
+
+// Block (e, j), j < n: emitted row j of env e into its ring slot -- obs / act from the window (or
+// from this push's own row), next_obs from the caller's row e, whichever row of the env it is.
+// Block (e, n - 1) also writes this push's (s, a) into the window where it stays pending; no
+// emitted row of the same push reads that slot (nstep_update), so the blocks need no order.
+__global__ void __launch_bounds__(kRB) k_nstep_copy(ReplayView v, NstepView w, NstepRows in) {
+    const int n = w.n;
+    const int64_t e = blockIdx.x / (unsigned)n;
+    const int j = (int)(blockIdx.x - (unsigned)(e * n));
+    if (e >= w.n_envs) return;
+    const int D = w.obs_dim, A = w.act_dim;
+    const float *s_in = in.obs + e * in.obs_stride, *a_in = in.act + e * in.act_stride;
+    if (j < w.cnt[e]) {
+        int64_t slot = w.base[e] + j;
+        slot = slot >= v.capacity ? slot - v.capacity : slot;
+        const int ws = w.e_slot[e * n + j];
+        const float *so = ws < 0 ? s_in : w.obs + (e * n + ws) * D;
+        const float *sa = ws < 0 ? a_in : w.act + (e * n + ws) * A;
+        copy_rows(so, v.obs + slot * D, in.next_obs + e * in.next_stride, v.next_obs + slot * D, D, in.vec4);
+        if ((int)threadIdx.x < A) v.act[slot * A + threadIdx.x] = sa[threadIdx.x];
+        if (threadIdx.x == 0) {
+            v.reward[slot] = w.e_reward[e * n + j];
+            v.done[slot] = w.e_done[e * n + j];
+        }
+    }
+    if (j == n - 1) {
+        const int st = w.store[e];
+        if (st >= 0) {
+            copy_rows(s_in, w.obs + (e * n + st) * D, nullptr, nullptr, D, in.vec4);
+            if ((int)threadIdx.x < A) w.act[(e * n + st) * A + threadIdx.x] = a_in[threadIdx.x];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kRB) k_nstep_reset(NstepView w, const uint8_t *env_mask) {
+    const int64_t e = (int64_t)blockIdx.x * kRB + threadIdx.x;
+    if (e >= w.n_envs || (env_mask && !env_mask[e])) return;
+    w.len[e] = 0;
+    w.head[e] = 0;
 }
 
 // ------------------------------------------------------------- sample ------
@@ -651,6 +801,22 @@ hipError_t launch_replay_add_index(const ReplayView &v, const uint8_t *mask, int
 hipError_t launch_replay_add_copy(const ReplayView &v, const ReplayRows &in, int64_t n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_add_copy, dim3((unsigned)n), dim3(kRB), 0, s, v, in, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_nstep_push(const ReplayView &v, const NstepView &w, const NstepRows &in, hipStream_t s) {
+    const int grid = replay_grid(v.capacity);
+    const unsigned eb = (unsigned)((w.n_envs + kRB - 1) / kRB);
+    hipLaunchKernelGGL(k_nstep_update, dim3(eb), dim3(kRB), 0, s, w, in);
+    hipLaunchKernelGGL(k_prio_max, dim3(grid), dim3(kRB), 0, s, v);
+    hipLaunchKernelGGL(k_nstep_scan, dim3(1), dim3(kOneBlock), 0, s, v, w, grid);
+    hipLaunchKernelGGL(k_nstep_copy, dim3((unsigned)(w.n_envs * w.n)), dim3(kRB), 0, s, v, w, in);
+    return hipGetLastError();
+}
+
+hipError_t launch_nstep_reset(const NstepView &w, const uint8_t *env_mask, hipStream_t s) {
+    const unsigned eb = (unsigned)((w.n_envs + kRB - 1) / kRB);
+    hipLaunchKernelGGL(k_nstep_reset, dim3(eb), dim3(kRB), 0, s, w, env_mask);
     return hipGetLastError();
 }
 

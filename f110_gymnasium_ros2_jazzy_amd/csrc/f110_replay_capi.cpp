@@ -1,9 +1,12 @@
 // f110_replay_capi.cpp — host side of the learner's device components
-// (include/f110.h, "prioritized experience replay" and "learner
-// optimizer"): argument checks, the device allocation at create, and the
-// launches of f110_replay.hip / f110_adam.hip.
+// (include/f110.h, "prioritized experience replay", "n-step returns" and
+// "learner optimizer"): argument checks, the device allocation at create, the
+// launches of f110_replay.hip / f110_adam.hip, and the host hook
+// f110_host_nstep (include/f110_debug.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -206,6 +209,195 @@ extern "C" int f110_replay_arrays(f110_replay *rb, float **priority, float **obs
     if (reward) *reward = rb->v.reward;
     if (next_obs) *next_obs = rb->v.next_obs;
     if (done) *done = rb->v.done;
+    return F110_OK;
+}
+
+// ---- n-step accumulator -------------------------------------------------------
+struct f110_nstep {
+    int device = 0;
+    NstepView w{};
+    std::vector<void *> allocs;
+
+    template <class T>
+    hipError_t alloc(T **p, size_t n) {
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, n * sizeof(T) + 16);
+        if (e == hipSuccess) e = hipMemset(q, 0, n * sizeof(T) + 16);
+        if (e == hipSuccess || q) allocs.push_back(q);
+        if (e == hipSuccess) *p = static_cast<T *>(q);
+        return e;
+    }
+};
+
+namespace {
+int check_nstep_args(const char *fn, int64_t n_envs, int32_t n_step, double gamma, int32_t obs_dim, int32_t act_dim) {
+    if (n_step < 1 || n_step > kNstepMax) return fail(F110_E_INVALID, std::string(fn) + ": n_step must be in [1, 16]");
+    if (!std::isfinite(gamma) || gamma < 0.0 || gamma > 1.0)
+        return fail(F110_E_INVALID, std::string(fn) + ": gamma must be finite and in [0, 1]");
+    if (n_envs <= 0 || n_envs * n_step >= (int64_t)1 << 31)
+        return fail(F110_E_INVALID, std::string(fn) + ": n_envs must be positive (n_envs * n_step < 2^31)");
+    if (obs_dim <= 0 || act_dim <= 0 || act_dim > 256)
+        return fail(F110_E_INVALID, std::string(fn) + ": obs_dim > 0 and 0 < act_dim <= 256");
+    return F110_OK;
+}
+
+int check_nstep_capacity(const char *fn, int64_t n_envs, int32_t n_step, int64_t capacity) {
+    if (n_envs * n_step > capacity)
+        return fail(F110_E_INVALID, std::string(fn) + ": n_envs * n_step must not exceed the replay's capacity");
+    return F110_OK;
+}
+
+void nstep_powers(double gamma, int n, double *pw) {  // sequential products
+    pw[0] = 1.0;
+    for (int i = 1; i <= n; ++i) pw[i] = pw[i - 1] * gamma;
+}
+}  // namespace
+
+extern "C" int f110_nstep_create(f110_nstep **out, int32_t device, int64_t n_envs, int32_t n_step, double gamma,
+                                 int32_t obs_dim, int32_t act_dim) {
+    if (!out) return fail(F110_E_INVALID, "f110_nstep_create: null out");
+    const int rc = check_nstep_args("f110_nstep_create", n_envs, n_step, gamma, obs_dim, act_dim);
+    if (rc != F110_OK) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
+        return fail(F110_E_NODEVICE, "f110_nstep_create: no such HIP device");
+    if (hipSetDevice(device) != hipSuccess) return fail(F110_E_NODEVICE, "f110_nstep_create: hipSetDevice");
+    auto *ns = new f110_nstep();
+    ns->device = device;
+    NstepView &w = ns->w;
+    w.n_envs = n_envs;
+    w.n = n_step;
+    w.obs_dim = obs_dim;
+    w.act_dim = act_dim;
+    const size_t N = (size_t)n_envs, W = N * (size_t)n_step;
+    double pw[kNstepMax + 1];
+    nstep_powers(gamma, n_step, pw);
+    double *dpw = nullptr;
+    hipError_t e = ns->alloc(&dpw, (size_t)n_step + 1);
+    w.pw = dpw;
+    if (e == hipSuccess) e = ns->alloc(&w.len, N);
+    if (e == hipSuccess) e = ns->alloc(&w.head, N);
+    if (e == hipSuccess) e = ns->alloc(&w.ret, W);
+    if (e == hipSuccess) e = ns->alloc(&w.k, W);
+    if (e == hipSuccess) e = ns->alloc(&w.obs, W * obs_dim);
+    if (e == hipSuccess) e = ns->alloc(&w.act, W * act_dim);
+    if (e == hipSuccess) e = ns->alloc(&w.cnt, N);
+    if (e == hipSuccess) e = ns->alloc(&w.store, N);
+    if (e == hipSuccess) e = ns->alloc(&w.base, N);
+    if (e == hipSuccess) e = ns->alloc(&w.e_slot, W);
+    if (e == hipSuccess) e = ns->alloc(&w.e_reward, W);
+    if (e == hipSuccess) e = ns->alloc(&w.e_done, W);
+    if (e == hipSuccess) e = hipMemcpy(dpw, pw, ((size_t)n_step + 1) * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        for (void *q : ns->allocs) (void)hipFree(q);
+        delete ns;
+        return fail(F110_E_ALLOC, std::string("f110_nstep_create: ") + hipGetErrorString(e));
+    }
+    *out = ns;
+    return F110_OK;
+}
+
+extern "C" int f110_nstep_destroy(f110_nstep *ns) {
+    if (!ns) return F110_OK;
+    (void)hipSetDevice(ns->device);
+    for (void *q : ns->allocs) (void)hipFree(q);
+    delete ns;
+    return F110_OK;
+}
+
+extern "C" int f110_nstep_push(f110_nstep *ns, f110_replay *rb, const float *obs, int64_t obs_stride, const float *act,
+                               int64_t act_stride, const double *reward, const float *next_obs, int64_t next_stride,
+                               const uint8_t *terminated, const uint8_t *truncated, const uint8_t *was_reset,
+                               void *stream) {
+    if (!ns || !rb) return fail(F110_E_INVALID, "f110_nstep_push: null accumulator or buffer");
+    const NstepView &w = ns->w;
+    const ReplayView &v = rb->v;
+    if (ns->device != rb->device) return fail(F110_E_INVALID, "f110_nstep_push: accumulator and buffer on different devices");
+    if (w.obs_dim != v.obs_dim || w.act_dim != v.act_dim)
+        return fail(F110_E_INVALID, "f110_nstep_push: obs_dim / act_dim differ from the replay's");
+    const int rc = check_nstep_capacity("f110_nstep_push", w.n_envs, w.n, v.capacity);
+    if (rc != F110_OK) return rc;
+    if (!obs || !act || !reward || !next_obs || !terminated || !was_reset || obs_stride < v.obs_dim ||
+        next_stride < v.obs_dim || act_stride < v.act_dim)
+        return fail(F110_E_INVALID, "f110_nstep_push: null row pointer or stride below the row length");
+    if (hipSetDevice(ns->device) != hipSuccess) return fail(F110_E_HIP, "f110_nstep_push: hipSetDevice");
+    NstepRows in{};
+    in.obs = obs;
+    in.act = act;
+    in.next_obs = next_obs;
+    in.reward = reward;
+    in.terminated = terminated;
+    in.truncated = truncated;
+    in.was_reset = was_reset;
+    in.obs_stride = obs_stride;
+    in.act_stride = act_stride;
+    in.next_stride = next_stride;
+    // (the window's and the ring's rows start 16-B aligned whenever obs_dim % 4 == 0)
+    in.vec4 = (v.obs_dim % 4 == 0 && obs_stride % 4 == 0 && next_stride % 4 == 0 && aligned16(obs) &&
+               aligned16(next_obs)) ? 1 : 0;
+    hipError_t e = launch_nstep_push(v, w, in, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(F110_E_HIP, std::string("f110_nstep_push: ") + hipGetErrorString(e));
+    return F110_OK;
+}
+
+extern "C" int f110_nstep_reset(f110_nstep *ns, const uint8_t *env_mask, void *stream) {
+    if (!ns) return fail(F110_E_INVALID, "f110_nstep_reset: null accumulator");
+    if (hipSetDevice(ns->device) != hipSuccess) return fail(F110_E_HIP, "f110_nstep_reset: hipSetDevice");
+    hipError_t e = launch_nstep_reset(ns->w, env_mask, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(F110_E_HIP, std::string("f110_nstep_reset: ") + hipGetErrorString(e));
+    return F110_OK;
+}
+
+extern "C" int f110_nstep_arrays(f110_nstep *ns, int32_t **len, int32_t **head, double **ret, int32_t **k, float **obs,
+                                 float **act) {
+    if (!ns) return fail(F110_E_INVALID, "f110_nstep_arrays: null accumulator");
+    if (len) *len = ns->w.len;
+    if (head) *head = ns->w.head;
+    if (ret) *ret = ns->w.ret;
+    if (k) *k = ns->w.k;
+    if (obs) *obs = ns->w.obs;
+    if (act) *act = ns->w.act;
+    return F110_OK;
+}
+
+extern "C" int f110_host_nstep(int64_t n_envs, int32_t n_step, double gamma, int32_t obs_dim, int32_t act_dim,
+                               int64_t capacity, int32_t *len, int32_t *head, double *ret, int32_t *k, float *win_obs,
+                               float *win_act, const float *obs, const float *act, const double *reward,
+                               const float *next_obs, const uint8_t *terminated, const uint8_t *truncated,
+                               const uint8_t *was_reset, float *out_obs, float *out_act, float *out_reward,
+                               float *out_next_obs, float *out_done, int64_t *out_count) {
+    int rc = check_nstep_args("f110_host_nstep", n_envs, n_step, gamma, obs_dim, act_dim);
+    if (rc == F110_OK && capacity > 0) rc = check_nstep_capacity("f110_host_nstep", n_envs, n_step, capacity);
+    if (rc != F110_OK) return rc;
+    if (!len || !head || !ret || !k || !win_obs || !win_act || !obs || !act || !reward || !next_obs || !terminated ||
+        !was_reset || !out_obs || !out_act || !out_reward || !out_next_obs || !out_done || !out_count)
+        return fail(F110_E_INVALID, "f110_host_nstep: null argument");
+    const int n = n_step;
+    const size_t D = (size_t)obs_dim, A = (size_t)act_dim;
+    double pw[kNstepMax + 1];
+    nstep_powers(gamma, n, pw);
+    int64_t row = 0;
+    for (int64_t e = 0; e < n_envs; ++e) {
+        int32_t e_slot[kNstepMax], store;
+        float e_reward[kNstepMax], e_done[kNstepMax];
+        const int cnt = nstep_update(n, pw, reward[e], terminated[e], truncated ? truncated[e] : 0, was_reset[e], len[e],
+                                     head[e], ret + e * n, k + e * n, e_slot, e_reward, e_done, store);
+        for (int j = 0; j < cnt; ++j, ++row) {
+            const float *so = e_slot[j] < 0 ? obs + e * D : win_obs + ((size_t)e * n + e_slot[j]) * D;
+            const float *sa = e_slot[j] < 0 ? act + e * A : win_act + ((size_t)e * n + e_slot[j]) * A;
+            std::copy(so, so + D, out_obs + row * D);
+            std::copy(sa, sa + A, out_act + row * A);
+            std::copy(next_obs + e * D, next_obs + (e + 1) * D, out_next_obs + row * D);
+            out_reward[row] = e_reward[j];
+            out_done[row] = e_done[j];
+        }
+        if (store >= 0) {
+            std::copy(obs + e * D, obs + (e + 1) * D, win_obs + ((size_t)e * n + store) * D);
+            std::copy(act + e * A, act + (e + 1) * A, win_act + ((size_t)e * n + store) * A);
+        }
+    }
+    *out_count = row;
     return F110_OK;
 }
 

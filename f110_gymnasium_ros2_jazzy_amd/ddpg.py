@@ -323,7 +323,8 @@ class DDPGLearner:
                  noise_sigma_start: float = 0.2, noise_sigma_min: float = 0.05, noise_decay: float = 0.999,
                  seed: int = 42, device="cuda:0", replay="device", process_group=None, max_add: int | None = None,
                  check_finite: bool = False, path: str | None = None, graphs: bool = False,
-                 noise_type: str = "gaussian", ou_theta: float = 0.15, ou_mu: float = 0.0, ou_dt: float = 1.0):
+                 noise_type: str = "gaussian", ou_theta: float = 0.15, ou_mu: float = 0.0, ou_dt: float = 1.0,
+                 n_step: int = 1):
         self.device = torch.device(device)
         self.tuned_gemms = enable_tuned_gemms(self.device)
         self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
@@ -391,6 +392,19 @@ class DDPGLearner:
                                              max_add=max_add)
         elif replay is not None:
             self.memory = replay
+        # n_step > 1: remember_env goes through a device window per env (replay.NStepAccumulator) that
+        # stores n-step returns with an effective done column; self.gamma stays the one-step gamma
+        # and the update kernels are the one-step ones
+        self.n_step = int(n_step)
+        if self.n_step < 1:
+            raise ValueError(f"n_step must be at least 1; got {n_step}")
+        self.nstep = None
+        if self.n_step > 1:
+            from .replay import DeviceReplayBuffer, NStepAccumulator
+            if not isinstance(self.memory, DeviceReplayBuffer):
+                raise ValueError("n_step > 1 needs the device replay buffer")
+            self.nstep = NStepAccumulator(self.memory.max_add, self.n_step, self.gamma, obs_dim=self.obs_dim,
+                                          act_dim=self.act_dim, device=self.device)
         # GaussianActionNoise (agent.py:507-539) on the device
         self.sigma = float(noise_sigma_start)
         self.sigma_min, self.noise_decay = float(noise_sigma_min), float(noise_decay)
@@ -428,11 +442,16 @@ class DDPGLearner:
         """agent.py:223-237 for a batch of transitions (rows with mask == 0 skipped)."""
         self.memory.add(state, action, reward, next_state, done, mask=mask)
 
-    def remember_env(self, state, action, reward, next_state, terminated, was_reset):
+    def remember_env(self, state, action, reward, next_state, terminated, was_reset, truncated=None):
         """remember() of a vector env's raw outputs (float64 rewards, uint8
         terminated / was_reset flags; reset rows skipped) without torch-side
-        conversions (DeviceReplayBuffer.add_env)."""
-        self.memory.add_env(state, action, reward, next_state, terminated, was_reset)
+        conversions (DeviceReplayBuffer.add_env).  With n_step > 1 the step goes
+        into the n-step windows instead, which also end at ``truncated`` rows
+        (uint8 or None); with n_step == 1 truncated is not used."""
+        if self.nstep is None:
+            self.memory.add_env(state, action, reward, next_state, terminated, was_reset)
+        else:
+            self.nstep.push(self.memory, state, action, reward, next_state, terminated, truncated, was_reset)
 
     def _finite(self, name, x):  # agent.py:291-296 (host sync; only with check_finite)
         if self.check_finite and not bool(torch.isfinite(x).all()):

@@ -205,6 +205,137 @@ class DeviceReplayBuffer:
             pass
 
 
+class NStepAccumulator:
+    """N-step returns in front of a DeviceReplayBuffer (include/f110.h, "n-step returns"): per env a
+    device window of at most ``n_step`` pending (s, a, running return) entries.  ``push`` takes a
+    vector env's raw step outputs as ``add_env`` does and appends what leaves the windows to the
+    ring: an entry with its n rewards, or every entry of an env whose episode ends.  A stored row's
+    done column is the effective done 1 - gamma^(k-1) (1 - done), so the one-step learner
+    bootstraps it with gamma^k.  All on the current torch stream; nothing goes through the host."""
+
+    def __init__(self, n_envs: int, n_step: int, gamma: float, obs_dim: int = 1088, act_dim: int = 2, device=0):
+        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        self.L = _lib.load()
+        self.n_envs, self.n_step, self.gamma = int(n_envs), int(n_step), float(gamma)
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        self.handle = None
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise _lib.F110Error("NStepAccumulator runs on a HIP device only (no CPU path)")
+        self.device = dev
+        h = ctypes.c_void_p()
+        _lib.check(self.L.f110_nstep_create(ctypes.byref(h), dev.index or 0, self.n_envs, self.n_step, self.gamma,
+                                            self.obs_dim, self.act_dim), "f110_nstep_create")
+        self.handle = h
+        self._keep = None
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def push(self, memory: DeviceReplayBuffer, states, actions, rewards, next_states, terminated, truncated,
+             was_reset):
+        """One vector step into the windows; the emitted rows into ``memory``.  rewards float64,
+        terminated / truncated / was_reset uint8 device tensors as the simulator writes them
+        (truncated may be None: no episode limits); ``n_envs`` rows each."""
+        s = memory._rows(states, self.obs_dim)
+        ns = memory._rows(next_states, self.obs_dim)
+        a = memory._rows(actions, self.act_dim)
+        r, d, m = rewards.reshape(-1), terminated.reshape(-1), was_reset.reshape(-1)
+        t = None if truncated is None else truncated.reshape(-1)
+        if r.dtype != torch.float64 or d.dtype != torch.uint8 or m.dtype != torch.uint8 or \
+                (t is not None and t.dtype != torch.uint8):
+            raise TypeError("push: rewards float64, terminated, truncated and was_reset uint8")
+        if not (r.is_contiguous() and d.is_contiguous() and m.is_contiguous() and (t is None or t.is_contiguous())):
+            raise ValueError("push: contiguous rewards / flags")
+        n = self.n_envs
+        if any(x.shape[0] != n for x in (s, ns, a, r, d, m)) or (t is not None and t.shape[0] != n):
+            raise ValueError(f"push: every input needs n_envs = {n} rows")
+        self._keep = (s, ns, a, r, d, t, m)  # alive until the stream has consumed them
+        _lib.check(self.L.f110_nstep_push(self.handle, memory.handle, _p(s), s.stride(0), _p(a), a.stride(0), _p(r),
+                                          _p(ns), ns.stride(0), _p(d), _p(t), _p(m), self._stream()),
+                   "f110_nstep_push")
+        memory._added += n  # an upper bound: emitted rows never outnumber pushed rows in total
+
+    def reset(self, env_mask=None):
+        """Drop the windows of the envs with env_mask != 0 (None: all); nothing is emitted."""
+        m = None if env_mask is None else _as_u8(torch.as_tensor(env_mask, device=self.device))
+        if m is not None and m.shape[0] != self.n_envs:
+            raise ValueError("reset: env_mask needs n_envs entries")
+        self._keep_m = m
+        _lib.check(self.L.f110_nstep_reset(self.handle, _p(m), self._stream()), "f110_nstep_reset")
+
+    def arrays(self):
+        """Device copies of the windows (tests): len, head [N] int32, ret [N, n] float64, k [N, n]
+        int32, obs [N, n, D], act [N, n, A]; entry i of env e sits in slot (head + i) % n."""
+        ptrs = [ctypes.c_void_p() for _ in range(6)]
+        _lib.check(self.L.f110_nstep_arrays(self.handle, *[ctypes.byref(p) for p in ptrs]), "f110_nstep_arrays")
+        N, n = self.n_envs, self.n_step
+        spec = [("len", (N,), torch.int32), ("head", (N,), torch.int32), ("ret", (N, n), torch.float64),
+                ("k", (N, n), torch.int32), ("obs", (N, n, self.obs_dim), torch.float32),
+                ("act", (N, n, self.act_dim), torch.float32)]
+        out = {}
+        for (name, shape, dt), p in zip(spec, ptrs):
+            t = torch.empty(shape, dtype=dt, device=self.device)
+            _d2d(t, p.value, self._stream())
+            out[name] = t
+        return out
+
+    def pending(self) -> torch.Tensor:
+        """[n_envs] int32 copy of the window lengths."""
+        p = ctypes.c_void_p()
+        _lib.check(self.L.f110_nstep_arrays(self.handle, ctypes.byref(p), None, None, None, None, None),
+                   "f110_nstep_arrays")
+        t = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        _d2d(t, p.value, self._stream())
+        return t
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize(self.device)
+            self.L.f110_nstep_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def host_nstep(state: dict, gamma, obs, act, reward, next_obs, terminated, truncated, was_reset, capacity: int = 0):
+    """One push on the host (f110_host_nstep) over NumPy arrays.  ``state``: the windows, as
+    ``host_nstep_state`` makes them, updated in place.  Returns the emitted rows
+    (obs, act, reward, next_obs, done) in the order the device appends them."""
+    import numpy as np
+    L = _lib.load()
+    N, n = state["ret"].shape
+    D, A = state["obs"].shape[2], state["act"].shape[2]
+    obs, next_obs = (np.ascontiguousarray(x, np.float32).reshape(N, D) for x in (obs, next_obs))
+    act = np.ascontiguousarray(act, np.float32).reshape(N, A)
+    reward = np.ascontiguousarray(reward, np.float64).reshape(N)
+    flags = [None if f is None else np.ascontiguousarray(f, np.uint8).reshape(N)
+             for f in (terminated, truncated, was_reset)]
+    out = [np.empty((N * n, D), np.float32), np.empty((N * n, A), np.float32), np.empty(N * n, np.float32),
+           np.empty((N * n, D), np.float32), np.empty(N * n, np.float32)]
+    cnt = ctypes.c_int64()
+
+    def ptr(x):
+        return None if x is None else ctypes.c_void_p(x.ctypes.data)
+    _lib.check(L.f110_host_nstep(N, n, float(gamma), D, A, int(capacity),
+                                 *[ptr(state[q]) for q in ("len", "head", "ret", "k", "obs", "act")],
+                                 ptr(obs), ptr(act), ptr(reward), ptr(next_obs), *[ptr(f) for f in flags],
+                                 *[ptr(x) for x in out], ctypes.byref(cnt)), "f110_host_nstep")
+    return tuple(x[:cnt.value] for x in out)
+
+
+def host_nstep_state(n_envs: int, n_step: int, obs_dim: int, act_dim: int) -> dict:
+    """Fresh host windows in f110_nstep_arrays' layout."""
+    import numpy as np
+    N, n = int(n_envs), int(n_step)
+    return {"len": np.zeros(N, np.int32), "head": np.zeros(N, np.int32), "ret": np.zeros((N, n), np.float64),
+            "k": np.zeros((N, n), np.int32), "obs": np.zeros((N, n, obs_dim), np.float32),
+            "act": np.zeros((N, n, act_dim), np.float32)}
+
+
 _hip = None
 
 

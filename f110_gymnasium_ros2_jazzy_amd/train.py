@@ -8,7 +8,8 @@ Per vector step, everything on the device:
   opponent      gap_follow_action on its previous scan (:168), inside F110VectorEnv
   env.step      (:174) with device autoreset (gymnasium NEXT_STEP)
   reward        CenterlineSafetyProgressReward (:127-146, :179) on the device
-  remember      (:184) every transition except the reset rows of autoreset steps
+  remember      (:184) every transition except the reset rows of autoreset steps;
+                with --n-step N as N-step returns (device windows in front of the ring)
   replay        (:187-188) `updates_per_step` learner updates after warm-up,
                 gradients averaged over ranks by RCCL
 
@@ -42,7 +43,7 @@ class VectorTrainer:
                  memory_size: int = 1 << 20, warmup_steps: int = 1000, updates_per_step: int = 1, seed: int = 42,
                  device=None, env_offset: int = 0, rank_seed: int = 0, graphs: bool = True,
                  max_episode_steps: int | None = None, stall_speed: float = 0.0, stall_steps: int | None = None,
-                 noise_type: str = "gaussian", eval_envs: int = 0, ou_reset: bool = False):
+                 noise_type: str = "gaussian", eval_envs: int = 0, ou_reset: bool = False, n_step: int = 1):
         from .ddpg import DDPGLearner
         from .maps import MAP_DIR
         from .reward import BatchedCenterlineReward, CenterlineTrack
@@ -78,7 +79,7 @@ class VectorTrainer:
                                  actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size,
                                  alpha=0.6, beta=0.4, priority_epsilon=1e-5, noise_sigma_start=0.20,
                                  noise_sigma_min=0.02, noise_decay=0.9995, seed=seed, device=self.device,
-                                 max_add=self.N, graphs=graphs, noise_type=noise_type)
+                                 max_add=self.N, graphs=graphs, noise_type=noise_type, n_step=n_step)
         self.warmup = int(warmup_steps)
         self.updates_per_step = int(updates_per_step)
         # HIP graphs per vector step once the learner's eager warm-up updates are done (explicit
@@ -143,8 +144,9 @@ class VectorTrainer:
         # NEXT_STEP autoreset: a reset row's obs is the previous episode's last
         # observation and its next_obs the new episode's first -- not a transition
         # (remember_env skips the rows with was_reset != 0); eval transitions are stored like any
-        # other (train_ddpg.py:184 remembers unconditionally)
-        self.agent.remember_env(obs_in, act, rew, nxt, term, was_reset)
+        # other (train_ddpg.py:184 remembers unconditionally).  n_step > 1: the step goes into the
+        # learner's n-step windows, which also end at this step's truncated rows
+        self.agent.remember_env(obs_in, act, rew, nxt, term, was_reset, truncated=self.env.truncated)
         return nxt, rew, term, was_reset
 
     def _head(self, obs_in, obs_out, phase_a):
@@ -273,6 +275,7 @@ def main():
     ap.add_argument("--noise", choices=("gaussian", "ou"), default="gaussian", help="exploration noise")
     ap.add_argument("--eval-envs", type=int, default=0, help="noise-free evaluation envs per GPU (the last K)")
     ap.add_argument("--ou-reset", action="store_true", help="zero an env's OU state when its episode resets")
+    ap.add_argument("--n-step", type=int, default=1, help="n-step returns in the replay (1: one-step targets)")
     ap.add_argument("--save-dir", default=None, help="rank 0 saves best.pt here when eval_return_mean improves")
     args = ap.parse_args()
     rank, world, local = D.init()
@@ -282,7 +285,7 @@ def main():
                        updates_per_step=args.updates_per_step, seed=args.seed, env_offset=shard.offset,
                        rank_seed=rank, max_episode_steps=args.max_episode_steps, stall_speed=args.stall_speed,
                        stall_steps=args.stall_steps, noise_type=args.noise, eval_envs=args.eval_envs,
-                       ou_reset=args.ou_reset)
+                       ou_reset=args.ou_reset, n_step=args.n_step)
     best = -float("inf")
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)

@@ -502,6 +502,51 @@ F110_API int f110_replay_length(f110_replay *rb, int64_t *length, int64_t *next_
 F110_API int f110_replay_arrays(f110_replay *rb, float **priority, float **obs, float **act, float **reward,
                                 float **next_obs, float **done);
 
+/* ---- n-step returns (no reference counterpart: agent.replay's targets are one-step) --
+ * An accumulator in front of the replay ring: per env a window of at most n_step
+ * pending entries (obs, act, a running return ret in f64, a reward count k),
+ * oldest first, and a power table pw[i] = gamma^i (f64, sequential products,
+ * pw[0] = 1).  One f110_nstep_push takes n_envs raw step outputs, as
+ * f110_replay_add_env does.  Per env:
+ *   was_reset != 0:  the window is dropped, nothing is emitted (a NEXT_STEP reset
+ *                    row; after an ending step the window is already empty);
+ *   otherwise:       every pending entry, oldest first: ret = ret + pw[k] * r,
+ *                    k += 1 (product and sum rounded separately); then
+ *                    (s, a, ret = r, k = 1) is appended;
+ *     terminated || truncated:  every entry is emitted, oldest first, with done =
+ *                    1.0f if terminated, else (float)(1.0 - pw[k - 1]); the window
+ *                    is empty afterwards;
+ *     else, n_step entries pending:  the oldest is emitted with done =
+ *                    (float)(1.0 - pw[n_step - 1]).
+ * An emitted row is (obs, act of the entry, (float)ret, this push's next_obs,
+ * done).  The done column is the effective done d_eff = 1 - gamma^(k-1) (1 - done):
+ * every TD target here is r + gamma * (1 - d) * q with d in float32, so the stored
+ * row bootstraps with gamma^k (1 - done) through the one-step kernels.  With
+ * n_step = 1 a push stores exactly f110_replay_add_env's rows.
+ * The emitted rows of one push are appended by env ascending, oldest first within
+ * an env, each with the ring's current max priority: what that many
+ * f110_replay_add rows (priority NULL) in this order would store.  Async on
+ * `stream`, no host read and no allocation after create (capturable in a HIP
+ * graph).  1 <= n_step <= 16, gamma finite in [0, 1]; at push obs_dim / act_dim
+ * must equal the replay's and n_envs * n_step must not exceed its capacity (its
+ * max_add does not apply).  truncated may be NULL (all 0).  The windows take
+ * n_step * n_envs * (obs_dim + act_dim) * 4 bytes. */
+typedef struct f110_nstep f110_nstep;
+F110_API int f110_nstep_create(f110_nstep **out, int32_t device, int64_t n_envs, int32_t n_step, double gamma,
+                               int32_t obs_dim, int32_t act_dim);
+F110_API int f110_nstep_destroy(f110_nstep *ns);
+F110_API int f110_nstep_push(f110_nstep *ns, f110_replay *rb, const float *obs, int64_t obs_stride, const float *act,
+                             int64_t act_stride, const double *reward, const float *next_obs, int64_t next_stride,
+                             const uint8_t *terminated, const uint8_t *truncated, const uint8_t *was_reset,
+                             void *stream);
+/* Drops the windows of the envs with env_mask != 0 (NULL = all); emits nothing. */
+F110_API int f110_nstep_reset(f110_nstep *ns, const uint8_t *env_mask /* NULL = all */, void *stream);
+/* Device views for tests: len / head [n_envs] (entry i of env e sits in slot
+ * (head + i) % n_step), ret / k [n_envs][n_step], obs [n_envs][n_step][obs_dim],
+ * act [n_envs][n_step][act_dim].  Any out pointer may be NULL. */
+F110_API int f110_nstep_arrays(f110_nstep *ns, int32_t **len, int32_t **head, double **ret, int32_t **k,
+                               float **obs, float **act);
+
 /* ---- learner optimizer ----------------------------------------------------------
  * One torch.optim.Adam step (agent.py:187-188: Adam(params, lr), betas
  * (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad) over a network whose

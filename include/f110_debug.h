@@ -281,6 +281,22 @@ F110_API int f110_host_explore_rows(const float *act, const float *normals, int6
                                     double *state_out, double decay, double sigma_min, const float *low,
                                     const float *high, float *out);
 
+/* One f110_nstep_push over HOST arrays: the same per-env function the kernel runs (nstep_update,
+ * csrc/f110_device.h), envs in ascending order.  len / head [n_envs], ret / k [n_envs][n_step],
+ * win_obs [n_envs][n_step][obs_dim] and win_act [n_envs][n_step][act_dim] are the windows
+ * (f110_nstep_arrays' layout; zero = fresh), updated in place; obs / act / next_obs are packed
+ * rows.  Writes the emitted rows, in the order the device appends them, to out_obs / out_next_obs
+ * [.][obs_dim], out_act [.][act_dim], out_reward / out_done [.] (room for n_envs * n_step rows)
+ * and their number to out_count.  Same validation (F110_E_INVALID); capacity > 0 also checks
+ * n_envs * n_step <= capacity as a push into such a ring would.  Host test hook: the CPU suite
+ * and the GPU tests share one statement of the semantics. */
+F110_API int f110_host_nstep(int64_t n_envs, int32_t n_step, double gamma, int32_t obs_dim, int32_t act_dim,
+                             int64_t capacity, int32_t *len, int32_t *head, double *ret, int32_t *k, float *win_obs,
+                             float *win_act, const float *obs, const float *act, const double *reward,
+                             const float *next_obs, const uint8_t *terminated, const uint8_t *truncated,
+                             const uint8_t *was_reset, float *out_obs, float *out_act, float *out_reward,
+                             float *out_next_obs, float *out_done, int64_t *out_count);
+
 #ifdef __cplusplus
 }
 #endif
