@@ -14,9 +14,9 @@ REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libf110.so")
 SOURCES = ["f110_kernels.hip", "f110_opponent.hip", "f110_reward.hip", "f110_episode.hip", "f110_replay.hip", "f110_adam.hip", "f110_ddpg.hip", "f110_gemm.hip",
-           "f110_capi.cpp",
+           "f110_host.cpp", "f110_ctx.cpp", "f110_ctx_debug.cpp", "f110_task_capi.cpp",
            "f110_replay_capi.cpp"]
-HEADERS = ["f110_device.h", "f110_internal.h", "f110_sincos_table.h"]
+HEADERS = ["f110_device.h", "f110_internal.h", "f110_sincos_table.h", "f110_host_util.h", "f110_host.h", "f110_ctx.h"]
 ARCH = os.environ.get("F110_OFFLOAD_ARCH", "gfx950")
 
 # -ffp-contract=off: the reference (Python/Numba) never fuses a*b+c; hipcc

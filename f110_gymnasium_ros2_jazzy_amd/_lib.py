@@ -98,30 +98,124 @@ F64 = 1
 INTEGRATOR_RK4 = 1
 INTEGRATOR_EULER = 2
 
-EXPORTS = [
-    "f110_abi_version", "f110_last_error", "f110_default_params", "f110_default_config", "f110_edt_k",
-    "f110_create", "f110_destroy", "f110_reset", "f110_step", "f110_get_state", "f110_set_state",
-    "f110_scan_batch", "f110_dynamics_batch", "f110_read_counters", "f110_reset_counters", "f110_debug_read_simt", "f110_debug_set_simt", "f110_debug_set_handoff_check", "f110_debug_profile_stamps", "f110_host_beam_runs_agree", "f110_host_sincos_fast", "f110_host_tan_cos_fast",
-    "f110_profile_begin", "f110_profile_end", "f110_host_tables", "f110_host_beam_indices",
-    "f110_set_scan_noise", "f110_set_params", "f110_host_cell_index", "f110_gap_follow",
-    "f110_host_window_ranges", "f110_track_create", "f110_track_destroy", "f110_track_arrays",
-    "f110_default_reward_params", "f110_reward", "f110_replay_create", "f110_replay_destroy", "f110_replay_add", "f110_replay_add_env",
-    "f110_replay_sample", "f110_replay_update_priorities", "f110_replay_length", "f110_replay_arrays",
-    "f110_debug_wave_trace", "f110_debug_set_ray_gate", "f110_debug_disable_heavy_first", "f110_debug_ray_kernel", "f110_debug_ray_lanes", "f110_debug_ray_refill", "f110_debug_set_ray_refill", "f110_debug_read_counter", "f110_step_n", "f110_debug_set_ray_lanes", "f110_set_reset_dtype", "f110_set_device_share", "f110_host_np_sincosf", "f110_host_sincos", "f110_host_sincos_series", "f110_host_map_table", "f110_get_lap_state",
-    "f110_host_ray_plan", "f110_host_ray_rules",
-    "f110_set_env_params", "f110_get_env_params", "f110_set_param_randomization",
-    "f110_host_check_param_ranges", "f110_host_param_draw",
-    "f110_set_episode_limits", "f110_host_check_episode_limits",
-    "f110_episode_scratch_bytes", "f110_episode_stats", "f110_host_episode_stats",
-    "f110_dynamics_ks_batch", "f110_collision_batch", "f110_collision_multiple", "f110_adam_step", "f110_ddpg_scratch_floats", "f110_ddpg_actor_head", "f110_ddpg_actor_explore",
-    "f110_ddpg_actor_head_bwd", "f110_ddpg_td_target", "f110_ddpg_critic_loss", "f110_ddpg_critic_loss_bwd",
-    "f110_ddpg_q_mean", "f110_ddpg_q_mean_bwd", "f110_ddpg_relu_bwd_scratch_floats", "f110_ddpg_relu_bwd",
-    "f110_learner_gemm", "f110_learner_wgrad_scratch_floats", "f110_learner_wgrad", "f110_learner_wgrad_loss",
-    "f110_ddpg_critic_step", "f110_ddpg_q_mean_step", "f110_ddpg_row_blocks",
-    "f110_ddpg_actor_explore_env", "f110_host_explore_rows",
-    "f110_nstep_create", "f110_nstep_destroy", "f110_nstep_push", "f110_nstep_reset", "f110_nstep_arrays",
-    "f110_host_nstep",
-]
+_i, _i32, _i64, _u64 = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
+_f32, _f64 = ctypes.c_float, ctypes.c_double
+_PP = ctypes.POINTER(F110Params)
+_OUT = ctypes.POINTER(F110Outputs)
+_PTRS6 = [ctypes.POINTER(_P)] * 6
+_EXPLORE = [_P] * 5 + [_i32] * 3 + [_P, _P, _f64, _f64, _P, _P, _u64, _P, _i64]  # f110_ddpg_actor_explore less its stream
+
+# The C ABI, one line per entry point of include/f110.h and include/f110_debug.h:
+# name -> (restype, argtypes); restype None is void.  tests/test_host_lib.py checks every line
+# against the headers' prototypes.
+_API = {
+    "f110_abi_version": (_i, []),
+    "f110_last_error": (ctypes.c_char_p, []),
+    "f110_default_params": (None, [_PP]),
+    "f110_default_config": (None, [ctypes.POINTER(F110Config)]),
+    "f110_edt_k": (_i, [_P, _i32, _i32, _P]),
+    "f110_create": (_i, [ctypes.POINTER(_P), _i32, ctypes.POINTER(F110Config), _PP, _P, _i32, _i32, _f64, _D, _P,
+                         _i32]),
+    "f110_destroy": (_i, [_P]),
+    "f110_reset": (_i, [_P, _P, _P, _OUT, _P]),
+    "f110_step": (_i, [_P, _P, _i32, _OUT, _P]),
+    "f110_get_state": (_i, [_P, _P, _P, _P, _P]),
+    "f110_set_state": (_i, [_P, _P, _P, _P, _P]),
+    "f110_scan_batch": (_i, [_P, _P, _i64, _P, _P, _P, _P]),
+    "f110_dynamics_batch": (_i, [_P, _P, _P, _P, _i64, _P]),
+    "f110_read_counters": (_i, [_P, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _P]),
+    "f110_reset_counters": (_i, [_P, _P]),
+    "f110_debug_read_simt": (_i, [_P, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _P]),
+    "f110_debug_set_simt": (_i, [_P, _i32]),
+    "f110_debug_set_handoff_check": (_i, [_P, _i32]),
+    "f110_debug_profile_stamps": (_i, [_P, _P, _P, _i32, ctypes.POINTER(_i32)]),
+    "f110_host_beam_runs_agree": (_i, [_f64, _f64, _i32, _i32]),
+    "f110_host_sincos_fast": (None, [_P, _i64, _P, _P, _P]),
+    "f110_host_tan_cos_fast": (None, [_P, _i64, _P, _P, _P, _P]),
+    "f110_profile_begin": (_i, [_P, _i32]),
+    "f110_profile_end": (_i, [_P, _D, ctypes.POINTER(_i32)]),
+    "f110_host_tables": (None, [_i32, _i32, _f64, _PP, _P, _P, _P, _P, _P]),
+    "f110_host_beam_indices": (_i, [_f64, _f64, _i32, _i32, _P]),
+    "f110_set_scan_noise": (_i, [_P, _P]),
+    "f110_set_params": (_i, [_P, _PP, _i32, _P]),
+    "f110_host_cell_index": (_i, [_i32, _i32, _f64, _D, _P, _i64, _P]),
+    "f110_gap_follow": (_i, [_P, _i64, _i64, _i32, _f64, _f64, _P, _i64, _P, _P]),
+    "f110_host_window_ranges": (None, [_f64, _f64, _i32, _f64, _f64, _P]),
+    "f110_track_create": (_i, [ctypes.POINTER(_P), _i32, _P, _P, _P, _i32, _i32]),
+    "f110_track_destroy": (_i, [_P]),
+    "f110_track_arrays": (_f64, [_P, _P, _P, _P, _P]),
+    "f110_default_reward_params": (None, [ctypes.POINTER(F110RewardParams)]),
+    "f110_reward": (_i, [_P, ctypes.POINTER(F110RewardParams), _P, _i64, _i32, _i32, _P, _P, _P, _P]),
+    "f110_replay_create": (_i, [ctypes.POINTER(_P), _i32, _i64, _i32, _i32, _i32, _i64, _f64, _f64, _u64]),
+    "f110_replay_destroy": (_i, [_P]),
+    "f110_replay_add": (_i, [_P, _P, _i64, _P, _i64, _P, _P, _i64, _P, _P, _P, _i64, _P]),
+    "f110_replay_add_env": (_i, [_P, _P, _i64, _P, _i64, _P, _P, _i64, _P, _P, _i64, _P]),
+    "f110_replay_sample": (_i, [_P, _i32, _f64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f110_replay_update_priorities": (_i, [_P, _P, _P, _i64, _i32, _f32, _P]),
+    "f110_replay_length": (_i, [_P, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _P]),
+    "f110_replay_arrays": (_i, [_P] + _PTRS6),
+    "f110_debug_wave_trace": (_i, [_P, _i32, _P, _i64, ctypes.POINTER(_i64), _P]),
+    "f110_debug_set_ray_gate": (_i, [_P, _P, _P]),
+    "f110_debug_disable_heavy_first": (_i, [_P]),
+    "f110_debug_ray_kernel": (_i, [_P]),
+    "f110_debug_ray_lanes": (_i, [_P]),
+    "f110_debug_ray_refill": (_i, [_P]),
+    "f110_debug_set_ray_refill": (_i, [_P, _i32]),
+    "f110_debug_read_counter": (_i, [_P, _i32, ctypes.POINTER(_u64), _P]),
+    "f110_step_n": (_i, [_P, _P, _i32, _i32, _i64, _P, _P]),
+    "f110_debug_set_ray_lanes": (_i, [_P, _i32]),
+    "f110_set_reset_dtype": (_i, [_P, _i32]),
+    "f110_set_device_share": (_i, [_P, _i64, _i32]),
+    "f110_host_np_sincosf": (None, [_P, _i64, _i32, _P]),
+    "f110_host_sincos": (None, [_P, _i64, _P, _P]),
+    "f110_host_sincos_series": (None, [_P, _i64, _P, _P]),
+    "f110_host_map_table": (_i64, [_P, _i32, _i32, _f64, _i32, _i32, _P, _i64, _P]),
+    "f110_get_lap_state": (_i, [_P, _P, _P, _P]),
+    "f110_host_ray_plan": (_i, [ctypes.POINTER(F110RayKnobs), _i32, ctypes.POINTER(F110RayPlan)]),
+    "f110_host_ray_rules": (_i, [_i64, _i64, _i32, _i32, _i32, ctypes.POINTER(_i32)]),
+    "f110_set_env_params": (_i, [_P, _PP, _P]),
+    "f110_get_env_params": (_i, [_P, _PP, _P]),
+    "f110_set_param_randomization": (_i, [_P, _PP, _PP, _u64, _P]),
+    "f110_host_check_param_ranges": (_i, [_PP, _PP, _PP, _i32]),
+    "f110_host_param_draw": (_i, [_u64, _i64, _i32, _u64, _PP, _PP, _PP]),
+    "f110_set_episode_limits": (_i, [_P, _i64, _f64, _i32, _P, _P]),
+    "f110_host_check_episode_limits": (_i, [_i64, _f64, _i32]),
+    "f110_episode_scratch_bytes": (_i64, [_i64]),
+    "f110_episode_stats": (_i, [_P, _P, _P, _P, _i64, _P, _P, _P, _P, _P, _P, _P]),
+    "f110_host_episode_stats": (_i, [_P, _P, _P, _P, _i64, _P, _P, _P, _P, _P]),
+    "f110_dynamics_ks_batch": (_i, [_P, _P, _P, _P, _i64, _P]),
+    "f110_collision_batch": (_i, [_P, _P, _i64, _P, _P]),
+    "f110_collision_multiple": (_i, [_P, _i64, _i32, _P, _P, _P]),
+    "f110_adam_step": (_i, [_P, _P, _P, _P, _i64, _f64, _f64, _f64, _f64, _P, _P, _f64, _P]),
+    "f110_ddpg_scratch_floats": (_i64, [_i32, _i32, _i32]),
+    "f110_ddpg_actor_head": (_i, [_P] * 5 + [_i32] * 3 + [_P] * 3),
+    "f110_ddpg_actor_explore": (_i, _EXPLORE + [_P]),
+    "f110_ddpg_actor_head_bwd": (_i, [_P] * 5 + [_i32] * 3 + [_P] * 6),
+    "f110_ddpg_td_target": (_i, [_P] * 5 + [_f32, _i32, _i32, _P, _P]),
+    "f110_ddpg_critic_loss": (_i, [_P] * 5 + [_i32] * 2 + [_P] * 4),
+    "f110_ddpg_critic_loss_bwd": (_i, [_P] * 5 + [_i32] * 2 + [_P] * 6),
+    "f110_ddpg_q_mean": (_i, [_P] * 3 + [_f32, _i32, _i32] + [_P] * 3),
+    "f110_ddpg_q_mean_bwd": (_i, [_P] * 3 + [_f32, _i32, _i32] + [_P] * 6),
+    "f110_ddpg_relu_bwd_scratch_floats": (_i64, [_i32, _i32]),
+    "f110_ddpg_relu_bwd": (_i, [_P, _P, _i32, _i32, _P, _P, _P, _P]),
+    "f110_learner_gemm": (_i, [ctypes.POINTER(F110GemmOp), _i32, _i32, _P]),
+    "f110_learner_wgrad_scratch_floats": (_i64, [ctypes.POINTER(F110WgradOp), _i32, _i32]),
+    "f110_learner_wgrad": (_i, [ctypes.POINTER(F110WgradOp), _i32, _i32, _P, _P]),
+    "f110_learner_wgrad_loss": (_i, [ctypes.POINTER(F110WgradOp), _i32, _i32, _P, _P, _i32, _f32, _P, _P]),
+    "f110_ddpg_critic_step": (_i, [_P] * 5 + [_f32] + [_P] * 5 + [_i32, _i32] + [_P] * 6),
+    "f110_ddpg_q_mean_step": (_i, [_P] * 4 + [_f32, _i32, _i32] + [_P] * 4),
+    "f110_ddpg_row_blocks": (_i32, [_i32]),
+    "f110_ddpg_actor_explore_env": (_i, _EXPLORE + [_i32, _P, _f64, _f64, _f64, _P, _P, _P, _P]),
+    "f110_host_explore_rows": (_i, [_P, _P, _i64, _i32, _i32, _P, _f64, _f64, _f64, _P, _P, _P, _P, _f64, _f64, _P,
+                                    _P, _P]),
+    "f110_nstep_create": (_i, [ctypes.POINTER(_P), _i32, _i64, _i32, _f64, _i32, _i32]),
+    "f110_nstep_destroy": (_i, [_P]),
+    "f110_nstep_push": (_i, [_P, _P, _P, _i64, _P, _i64, _P, _P, _i64, _P, _P, _P, _P]),
+    "f110_nstep_reset": (_i, [_P, _P, _P]),
+    "f110_nstep_arrays": (_i, [_P] + _PTRS6),
+    "f110_host_nstep": (_i, [_i64, _i32, _f64, _i32, _i32, _i64] + [_P] * 18 + [ctypes.POINTER(_i64)]),
+}
+EXPORTS = list(_API)
 
 _lib = None
 
@@ -164,151 +258,15 @@ def load(build_if_missing: bool = True):
         pass
     L = ctypes.CDLL(path)
     alternate = path != _build.LIB
-    if alternate:  # an older build for A/B (ABI 2): its diagnostics under their pre-f110_debug_ names
-        for name in EXPORTS:
-            old = name.replace("f110_debug_", "f110_")
-            if name.startswith("f110_debug_") and not hasattr(L, name) and hasattr(L, old):
-                setattr(L, name, getattr(L, old))
-            elif not hasattr(L, name):  # newer than that build: fails when called
-                setattr(L, name, _Missing(name))
-    i32, i64, u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
-    L.f110_abi_version.restype = ctypes.c_int
-    L.f110_last_error.restype = ctypes.c_char_p
-    L.f110_default_params.argtypes = [ctypes.POINTER(F110Params)]
-    L.f110_default_config.argtypes = [ctypes.POINTER(F110Config)]
-    L.f110_edt_k.argtypes = [_P, i32, i32, _P]
-    L.f110_create.argtypes = [ctypes.POINTER(_P), i32, ctypes.POINTER(F110Config), ctypes.POINTER(F110Params),
-                              _P, i32, i32, ctypes.c_double, _D, _P, i32]
-    L.f110_destroy.argtypes = [_P]
-    L.f110_reset.argtypes = [_P, _P, _P, ctypes.POINTER(F110Outputs), _P]
-    L.f110_step.argtypes = [_P, _P, i32, ctypes.POINTER(F110Outputs), _P]
-    L.f110_get_state.argtypes = [_P, _P, _P, _P, _P]
-    L.f110_set_state.argtypes = [_P, _P, _P, _P, _P]
-    L.f110_scan_batch.argtypes = [_P, _P, i64, _P, _P, _P, _P]
-    L.f110_dynamics_batch.argtypes = [_P, _P, _P, _P, i64, _P]
-    L.f110_dynamics_ks_batch.argtypes = [_P, _P, _P, _P, i64, _P]
-    L.f110_collision_batch.argtypes = [_P, _P, i64, _P, _P]
-    L.f110_collision_multiple.argtypes = [_P, i64, ctypes.c_int32, _P, _P, _P]
-    L.f110_read_counters.argtypes = [_P, ctypes.POINTER(u64), ctypes.POINTER(u64), _P]
-    L.f110_reset_counters.argtypes = [_P, _P]
-    L.f110_debug_read_simt.argtypes = [_P, ctypes.POINTER(u64), ctypes.POINTER(u64), _P]
-    L.f110_debug_set_simt.argtypes = [_P, ctypes.c_int32]
-    L.f110_debug_set_handoff_check.argtypes = [_P, ctypes.c_int32]
-    L.f110_host_beam_runs_agree.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32]
-    L.f110_host_sincos_fast.argtypes = [_P, i64, _P, _P, _P]
-    L.f110_host_tan_cos_fast.argtypes = [_P, i64, _P, _P, _P, _P]
-    L.f110_debug_profile_stamps.argtypes = [_P, _P, _P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
-    L.f110_set_scan_noise.argtypes = [_P, _P]
-    L.f110_host_window_ranges.argtypes = [ctypes.c_double, ctypes.c_double, i32, ctypes.c_double, ctypes.c_double,
-                                          _P]
-    L.f110_host_window_ranges.restype = None
-    L.f110_track_create.argtypes = [ctypes.POINTER(_P), i32, _P, _P, _P, i32, i32]
-    L.f110_track_destroy.argtypes = [_P]
-    L.f110_track_arrays.argtypes = [_P, _P, _P, _P, _P]
-    L.f110_track_arrays.restype = ctypes.c_double
-    L.f110_default_reward_params.argtypes = [ctypes.POINTER(F110RewardParams)]
-    L.f110_default_reward_params.restype = None
-    L.f110_reward.argtypes = [_P, ctypes.POINTER(F110RewardParams), _P, i64, i32, i32, _P, _P, _P, _P]
-    L.f110_gap_follow.argtypes = [_P, i64, i64, i32, ctypes.c_double, ctypes.c_double, _P, i64, _P, _P]
-    L.f110_host_cell_index.argtypes = [i32, i32, ctypes.c_double, _D, _P, i64, _P]
-    L.f110_set_params.argtypes = [_P, ctypes.POINTER(F110Params), i32, _P]
-    L.f110_profile_begin.argtypes = [_P, i32]
-    L.f110_profile_end.argtypes = [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32)]
-    L.f110_host_tables.argtypes = [i32, i32, ctypes.c_double, ctypes.POINTER(F110Params), _P, _P, _P, _P, _P]
-    L.f110_host_beam_indices.argtypes = [ctypes.c_double, ctypes.c_double, i32, i32, _P]
-    L.f110_host_beam_indices.restype = ctypes.c_int
-    L.f110_replay_create.argtypes = [ctypes.POINTER(_P), i32, i64, i32, i32, i32, i64, ctypes.c_double,
-                                     ctypes.c_double, u64]
-    L.f110_replay_destroy.argtypes = [_P]
-    L.f110_replay_add.argtypes = [_P, _P, i64, _P, i64, _P, _P, i64, _P, _P, _P, i64, _P]
-    L.f110_replay_add_env.argtypes = [_P, _P, i64, _P, i64, _P, _P, i64, _P, _P, i64, _P]
-    L.f110_replay_sample.argtypes = [_P, i32, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P]
-    L.f110_replay_update_priorities.argtypes = [_P, _P, _P, i64, i32, ctypes.c_float, _P]
-    L.f110_replay_length.argtypes = [_P, ctypes.POINTER(i64), ctypes.POINTER(i64), _P]
-    L.f110_replay_arrays.argtypes = [_P] + [ctypes.POINTER(_P)] * 6
-    L.f110_debug_wave_trace.argtypes = [_P, i32, _P, i64, ctypes.POINTER(i64), _P]
-    L.f110_debug_set_ray_gate.argtypes = [_P, _P, _P]
-    L.f110_debug_disable_heavy_first.argtypes = [_P]
-    L.f110_debug_ray_kernel.argtypes = [_P]
-    L.f110_debug_ray_lanes.argtypes = [_P]
-    L.f110_debug_ray_refill.argtypes = [_P]
-    L.f110_debug_set_ray_refill.argtypes = [_P, ctypes.c_int32]
-    L.f110_step_n.argtypes = [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _P, _P]
-    L.f110_debug_read_counter.argtypes = [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), _P]
-    L.f110_debug_set_ray_lanes.argtypes = [_P, ctypes.c_int32]
-    if hasattr(L, "f110_set_device_share") or not alternate:
-        L.f110_set_device_share.argtypes = [_P, i64, i32]
-    L.f110_set_reset_dtype.argtypes = [_P, ctypes.c_int32]
-    L.f110_get_lap_state.argtypes = [_P, _P, _P, _P]
-    L.f110_host_np_sincosf.argtypes = [_P, i64, ctypes.c_int32, _P]
-    L.f110_host_np_sincosf.restype = None
-    L.f110_host_sincos.argtypes = [_P, i64, _P, _P]
-    L.f110_host_sincos.restype = None
-    L.f110_host_sincos_series.argtypes = [_P, i64, _P, _P]
-    L.f110_host_sincos_series.restype = None
-    L.f110_host_map_table.argtypes = [_P, i32, i32, ctypes.c_double, i32, i32, _P, i64, _P]
-    L.f110_host_map_table.restype = ctypes.c_int64
-    L.f110_host_ray_plan.argtypes = [ctypes.POINTER(F110RayKnobs), i32, ctypes.POINTER(F110RayPlan)]
-    L.f110_host_ray_rules.argtypes = [i64, i64, i32, i32, i32, ctypes.POINTER(i32)]
-    PP = ctypes.POINTER(F110Params)
-    L.f110_set_env_params.argtypes = [_P, PP, _P]
-    L.f110_get_env_params.argtypes = [_P, PP, _P]
-    L.f110_set_param_randomization.argtypes = [_P, PP, PP, u64, _P]
-    L.f110_host_check_param_ranges.argtypes = [PP, PP, PP, i32]
-    L.f110_host_param_draw.argtypes = [u64, i64, i32, u64, PP, PP, PP]
-    L.f110_set_episode_limits.argtypes = [_P, i64, ctypes.c_double, i32, _P, _P]
-    L.f110_host_check_episode_limits.argtypes = [i64, ctypes.c_double, i32]
-    L.f110_episode_scratch_bytes.argtypes = [i64]
-    L.f110_episode_stats.argtypes = [_P, _P, _P, _P, i64, _P, _P, _P, _P, _P, _P, _P]
-    L.f110_host_episode_stats.argtypes = [_P, _P, _P, _P, i64, _P, _P, _P, _P, _P]
-    L.f110_adam_step.argtypes = [_P, _P, _P, _P, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                 ctypes.c_double, _P, _P, ctypes.c_double, _P]
-    f32 = ctypes.c_float
-    L.f110_ddpg_scratch_floats.argtypes = [i32, i32, i32]
-    L.f110_ddpg_actor_head.argtypes = [_P] * 5 + [i32] * 3 + [_P] * 3
-    L.f110_ddpg_actor_explore.argtypes = [_P] * 5 + [i32] * 3 + [_P, _P, ctypes.c_double, ctypes.c_double, _P, _P,
-                                                                  ctypes.c_uint64, _P, i64, _P]
-    f64 = ctypes.c_double
-    L.f110_ddpg_actor_explore_env.argtypes = L.f110_ddpg_actor_explore.argtypes[:-1] + [i32, _P, f64, f64, f64, _P, _P,
-                                                                                       _P, _P]
-    L.f110_host_explore_rows.argtypes = [_P, _P, i64, i32, i32, _P, f64, f64, f64, _P, _P, _P, _P, f64, f64, _P, _P,
-                                         _P]
-    L.f110_nstep_create.argtypes = [ctypes.POINTER(_P), i32, i64, i32, f64, i32, i32]
-    L.f110_nstep_destroy.argtypes = [_P]
-    L.f110_nstep_push.argtypes = [_P, _P, _P, i64, _P, i64, _P, _P, i64, _P, _P, _P, _P]
-    L.f110_nstep_reset.argtypes = [_P, _P, _P]
-    L.f110_nstep_arrays.argtypes = [_P] + [ctypes.POINTER(_P)] * 6
-    L.f110_host_nstep.argtypes = [i64, i32, f64, i32, i32, i64] + [_P] * 18 + [ctypes.POINTER(i64)]
-    L.f110_ddpg_actor_head_bwd.argtypes = [_P] * 5 + [i32] * 3 + [_P] * 6
-    L.f110_ddpg_td_target.argtypes = [_P] * 5 + [f32, i32, i32, _P, _P]
-    L.f110_ddpg_critic_loss.argtypes = [_P] * 5 + [i32] * 2 + [_P] * 4
-    L.f110_ddpg_critic_loss_bwd.argtypes = [_P] * 5 + [i32] * 2 + [_P] * 6
-    L.f110_ddpg_q_mean.argtypes = [_P] * 3 + [f32, i32, i32] + [_P] * 3
-    L.f110_ddpg_q_mean_bwd.argtypes = [_P] * 3 + [f32, i32, i32] + [_P] * 6
-    L.f110_ddpg_relu_bwd_scratch_floats.argtypes = [i32, i32]
-    L.f110_ddpg_relu_bwd.argtypes = [_P, _P, i32, i32, _P, _P, _P, _P]
-    L.f110_learner_gemm.argtypes = [ctypes.POINTER(F110GemmOp), i32, i32, _P]
-    L.f110_learner_wgrad_scratch_floats.argtypes = [ctypes.POINTER(F110WgradOp), i32, i32]
-    L.f110_learner_wgrad.argtypes = [ctypes.POINTER(F110WgradOp), i32, i32, _P, _P]
-    L.f110_learner_wgrad_loss.argtypes = [ctypes.POINTER(F110WgradOp), i32, i32, _P, _P, i32, f32, _P, _P]
-    L.f110_ddpg_critic_step.argtypes = [_P] * 5 + [f32] + [_P] * 5 + [i32, i32] + [_P] * 6
-    L.f110_ddpg_q_mean_step.argtypes = [_P] * 4 + [f32, i32, i32] + [_P] * 4
-    L.f110_ddpg_row_blocks.argtypes = [i32]
-    L.f110_ddpg_row_blocks.restype = i32
-    for name in EXPORTS:
-        if alternate and not hasattr(L, name):
-            continue
-        if name not in ("f110_abi_version", "f110_last_error", "f110_default_params", "f110_default_config",
-                        "f110_host_np_sincosf", "f110_host_sincos", "f110_host_sincos_series",
-                        "f110_host_tables", "f110_host_window_ranges", "f110_track_arrays",
-                        "f110_default_reward_params", "f110_ddpg_scratch_floats",
-                        "f110_ddpg_relu_bwd_scratch_floats", "f110_learner_wgrad_scratch_floats",
-                        "f110_episode_scratch_bytes"):
-            getattr(L, name).restype = ctypes.c_int
-    L.f110_ddpg_scratch_floats.restype = i64
-    L.f110_ddpg_relu_bwd_scratch_floats.restype = i64
-    L.f110_learner_wgrad_scratch_floats.restype = i64
-    L.f110_episode_scratch_bytes.restype = i64
+    for name, (restype, argtypes) in _API.items():
+        fn = getattr(L, name, None) if alternate else getattr(L, name)
+        if fn is None and name.startswith("f110_debug_"):
+            # an older build for A/B (ABI 2): its diagnostics under their pre-f110_debug_ names
+            fn = getattr(L, name.replace("f110_debug_", "f110_"), None)
+        if fn is None:  # newer than that build: fails when called
+            fn = _Missing(name)
+        setattr(L, name, fn)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.f110_abi_version() != ABI_VERSION and not (alternate and L.f110_abi_version() == 2):
         raise F110Error(f"libf110.so ABI version mismatch ({L.f110_abi_version()} != {ABI_VERSION})")
     _lib = L

@@ -22,9 +22,8 @@
 #include <string>
 #include <type_traits>
 
+#include "f110_host_util.h"
 #include "f110_internal.h"
-
-int f110_set_error(int code, const std::string &msg);  // f110_capi.cpp
 
 namespace f110 {
 namespace {
@@ -519,10 +518,6 @@ hipError_t wgrad(HeadArgs a, hipStream_t s) {
 
 bool bad_shape(int32_t B, int32_t K, int32_t nout) { return B <= 0 || K <= 0 || K > kMaxK || nout <= 0 || nout > kMaxOut; }
 
-int fail_hip(const char *fn, hipError_t e) {
-    return f110_set_error(F110_E_HIP, std::string(fn) + ": " + hipGetErrorString(e));
-}
-
 int fail_arg(const char *fn) { return f110_set_error(F110_E_INVALID, std::string(fn) + ": bad arguments"); }
 
 }  // namespace
@@ -557,7 +552,7 @@ extern "C" int f110_ddpg_relu_bwd(const float *gy, const float *y, int32_t B, in
                            scratch, nblk, K, db);
         e = hipGetLastError();
     }
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_relu_bwd", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_relu_bwd", e);
 }
 
 extern "C" int f110_ddpg_actor_head(const float *h, const float *W, const float *b, const float *scale,
@@ -572,7 +567,7 @@ extern "C" int f110_ddpg_actor_head(const float *h, const float *W, const float 
                            (hipStream_t)stream, a);
         return hipGetLastError();
     });
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_actor_head", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_actor_head", e);
 }
 
 extern "C" int f110_ddpg_actor_explore(const float *h, const float *W, const float *b, const float *scale,
@@ -593,7 +588,7 @@ extern "C" int f110_ddpg_actor_explore(const float *h, const float *W, const flo
                            (hipStream_t)stream, a);
         return hipGetLastError();
     });
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_actor_explore", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_actor_explore", e);
 }
 
 extern "C" int f110_ddpg_actor_explore_env(const float *h, const float *W, const float *b, const float *scale,
@@ -620,7 +615,7 @@ extern "C" int f110_ddpg_actor_explore_env(const float *h, const float *W, const
                            (hipStream_t)stream, a);
         return hipGetLastError();
     });
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_actor_explore_env", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_actor_explore_env", e);
 }
 
 extern "C" int f110_host_explore_rows(const float *act, const float *normals, int64_t n_rows, int32_t nout,
@@ -665,7 +660,7 @@ extern "C" int f110_ddpg_actor_head_bwd(const float *h, const float *W, const fl
         return hipGetLastError();
     });
     if (e == hipSuccess) e = wgrad(a, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_actor_head_bwd", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_actor_head_bwd", e);
 }
 
 extern "C" int f110_ddpg_td_target(const float *h, const float *W, const float *b, const float *r, const float *d,
@@ -676,7 +671,7 @@ extern "C" int f110_ddpg_td_target(const float *h, const float *W, const float *
     a.B = B, a.K = K, a.nout = 1;
     hipLaunchKernelGGL((k_head_fwd<kTarget, 1>), dim3(row_blocks(B)), dim3(kHB), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_td_target", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_td_target", e);
 }
 
 extern "C" int f110_ddpg_critic_loss(const float *h, const float *W, const float *b, const float *y, const float *w,
@@ -693,7 +688,7 @@ extern "C" int f110_ddpg_critic_loss(const float *h, const float *W, const float
         hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(kHB), 0, (hipStream_t)stream, a);
         e = hipGetLastError();
     }
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_critic_loss", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_critic_loss", e);
 }
 
 extern "C" int f110_ddpg_critic_loss_bwd(const float *h, const float *W, const float *td, const float *w,
@@ -708,7 +703,7 @@ extern "C" int f110_ddpg_critic_loss_bwd(const float *h, const float *W, const f
     hipLaunchKernelGGL((k_head_bwd_rows<kLoss, 1>), dim3(row_blocks(B)), dim3(kHB), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = wgrad(a, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_critic_loss_bwd", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_critic_loss_bwd", e);
 }
 
 extern "C" int f110_ddpg_q_mean(const float *h, const float *W, const float *b, float sign, int32_t B, int32_t K,
@@ -723,7 +718,7 @@ extern "C" int f110_ddpg_q_mean(const float *h, const float *W, const float *b, 
         hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(kHB), 0, (hipStream_t)stream, a);
         e = hipGetLastError();
     }
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_q_mean", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_q_mean", e);
 }
 
 extern "C" int f110_ddpg_q_mean_bwd(const float *h, const float *W, const float *g, float sign, int32_t B, int32_t K,
@@ -737,7 +732,7 @@ extern "C" int f110_ddpg_q_mean_bwd(const float *h, const float *W, const float 
     hipLaunchKernelGGL((k_head_bwd_rows<kMean, 1>), dim3(row_blocks(B)), dim3(kHB), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = wgrad(a, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_q_mean_bwd", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_q_mean_bwd", e);
 }
 
 extern "C" int f110_ddpg_critic_step(const float *ht, const float *Wt, const float *bt, const float *r, const float *d,
@@ -753,7 +748,7 @@ extern "C" int f110_ddpg_critic_step(const float *ht, const float *Wt, const flo
     a.B = B, a.K = K, a.nout = 1;
     hipLaunchKernelGGL(k_critic_step, dim3(row_blocks(B)), dim3(kHB), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_critic_step", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_critic_step", e);
 }
 
 extern "C" int f110_ddpg_q_mean_step(const float *h, const float *W, const float *b, const float *g, float sign,
@@ -765,7 +760,7 @@ extern "C" int f110_ddpg_q_mean_step(const float *h, const float *W, const float
     a.B = B, a.K = K, a.nout = 1;
     hipLaunchKernelGGL(k_q_mean_step, dim3(row_blocks(B)), dim3(kHB), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("f110_ddpg_q_mean_step", e);
+    return e == hipSuccess ? 0 : hip_fail("f110_ddpg_q_mean_step", e);
 }
 
 extern "C" int32_t f110_ddpg_row_blocks(int32_t B) { return B > 0 ? (int32_t)row_blocks(B) : -1; }

@@ -29,9 +29,8 @@
 #include <algorithm>
 #include <string>
 
+#include "f110_host_util.h"
 #include "f110_internal.h"
-
-int f110_set_error(int code, const std::string &msg);  // f110_capi.cpp
 
 namespace f110 {
 namespace {
@@ -624,7 +623,7 @@ extern "C" int f110_learner_gemm(const f110_gemm_op *ops, int32_t nops, int32_t 
     void *args[] = {&L};
     hipError_t e = hipLaunchKernel(k, dim3((unsigned)blk), dim3(kGB), args, 0, (hipStream_t)stream);
     if (e == hipSuccess) e = hipGetLastError();
-    return e == hipSuccess ? 0 : f110_set_error(F110_E_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+    return e == hipSuccess ? 0 : hip_fail(fn, e);
 }
 
 extern "C" int64_t f110_learner_wgrad_scratch_floats(const f110_wgrad_op *ops, int32_t nops, int32_t M) {
@@ -674,7 +673,7 @@ static int learner_wgrad(const char *fn, const f110_wgrad_op *ops, int32_t nops,
     void *args[] = {&L};
     {
         hipError_t e = hipLaunchKernel(kf[L.S == 1][gm], dim3((unsigned)blk), dim3(kGB), args, 0, s);
-        if (e != hipSuccess) return f110_set_error(F110_E_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+        if (e != hipSuccess) return hip_fail(fn, e);
     }
     if (L.S > 1 || loss) {  // the partials added (S > 1) and / or the loss (one more block)
         const int64_t outs = L.S > 1 ? total : 0;
@@ -682,7 +681,7 @@ static int learner_wgrad(const char *fn, const f110_wgrad_op *ops, int32_t nops,
                            s, L, outs);
     }
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : f110_set_error(F110_E_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+    return e == hipSuccess ? 0 : hip_fail(fn, e);
 }
 
 extern "C" int f110_learner_wgrad(const f110_wgrad_op *ops, int32_t nops, int32_t M, float *scratch, void *stream) {

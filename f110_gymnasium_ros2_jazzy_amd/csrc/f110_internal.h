@@ -1,5 +1,8 @@
-// f110_internal.h — context layout and kernel launchers shared by
-// f110_kernels.hip (device) and f110_capi.cpp (host API).
+// f110_internal.h — kernel argument blocks and launchers shared by the .hip
+// files (device) and the host files of the C ABI: f110_host.cpp (pure host
+// code), f110_ctx.cpp / f110_ctx_debug.cpp (the context), f110_task_capi.cpp
+// and f110_replay_capi.cpp (the other handles).  Host-only helpers are in
+// f110_host_util.h (errors, DeviceArena) and f110_host.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -218,8 +221,8 @@ constexpr int kFxsLdsTheta = 2048;   // theta table entries the block's LDS copy
 
 // The ray launch of one f110_step / f110_reset, decided in one place: RayKnobs is the context state
 // the decision reads (plain values, include/f110_debug.h), RayPlan the kernel family, its template
-// flags, the launch shape and the EDT table.  plan_ray_launch is pure host code: no HIP call, no
-// context, no environment (tests/test_host_lib.py checks it on the CPU through f110_host_ray_plan).
+// flags, the launch shape and the EDT table.  plan_ray_launch (f110_host.cpp) is pure host code: no HIP
+// call, no context, no environment (tests/test_host_lib.py checks it on the CPU through f110_host_ray_plan).
 using RayKnobs = f110_ray_knobs;
 using RayPlan = f110_ray_plan;
 RayPlan plan_ray_launch(const RayKnobs &k, bool masked);

@@ -2116,52 +2116,6 @@ __global__ void __launch_bounds__(kMultiBlock, 6) k_post_multi(StepArgs a) {
 #endif
 }
 
-// The ray launch of a context, the one place that decides it:
-//   kernel 1:  k_rays_tiled in flat ray order, kBlock rays per block;
-//   kernel 2:  k_rays_tiled chunked: HB heavy-first blocks (steps of a context that keeps a list),
-//              then a block per (chunk, wpb cars); also kernel 3 on a rotated map;
-//   kernel 3:  the fixed-point kernels (f110_create checked their preconditions: axis-aligned map,
-//              one-wave blocks, W, H < 2^21, |origin / res| < 2^20, EDT entries 0 or > eps):
-//              k_rays_fx (1 ray per lane, clamped table), k_rays_fxn<2> (2 rays per lane, a block
-//              per chunk group, on the padded table where it exists) or, for unmasked launches
-//              of a context with refill waves, fxs_ok and no heavy-first, k_rays_fxs.
-RayPlan plan_ray_launch(const RayKnobs &k, bool masked) {
-    const int EA = k.E * k.A, chunks = (k.B + 63) / 64;
-    const bool single = k.A == 1, fx = k.kernel == 3 && !k.rotated && k.ray_wpb == 1 && k.has_rm;
-    const bool pair = fx && k.lanes == 2, pad = pair && k.has_rmp;  // k_rays_fxn<2>; on the padded table
-    RayPlan p{};
-    p.rot = k.rotated != 0;
-    p.mask = masked;
-    p.handoff = !single;  // HANDOFF for A >= 2
-    p.family = F110_RAY_TILED_FLAT;
-    p.table = pad ? F110_TABLE_PADDED : fx ? F110_TABLE_ROWMAJOR : F110_TABLE_TILED;
-    p.grid = (uint32_t)(((int64_t)EA * k.B + kBlock - 1) / kBlock);
-    p.block = (uint32_t)kBlock;
-    if (k.kernel < 2) return p;
-    p.family = pad ? F110_RAY_FXN_PADDED : pair ? F110_RAY_FXN_CLAMPED : fx ? F110_RAY_FX : F110_RAY_TILED_CHUNKED;
-    p.wpb = k.ray_wpb;
-    p.G4 = (EA + p.wpb - 1) / p.wpb;
-    p.nch = pair ? (chunks + 1) / 2 : chunks;  // k_rays_fxn: chunk groups per car (heavy list / wcost units)
-    p.wcost = k.heavy_list && k.heavy_on;  // the cost bytes feed the next step's heavy-first list only
-    if (k.heavy_use && !masked) p.HB = (k.heavy_cap + p.wpb - 1) / p.wpb;
-    p.trace = k.wtrace && !fx && !k.rotated && !masked;  // f110_debug_wave_trace
-    p.grid = (uint32_t)(p.HB + p.G4 * p.nch);
-    p.block = 64u * (uint32_t)p.wpb;
-    if (pad && k.refill > 0 && k.fxs_ok && !masked && p.HB == 0 && !p.wcost) {
-        // k_rays_fxs: one or a few waves per car, two chunk slots with refill (no heavy-first)
-        p.family = F110_RAY_FXS;
-        p.lds = single && k.fxs_lds && k.theta_dis <= kFxsLdsTheta;
-        p.count = k.count_slots != 0;  // f110_debug_set_simt: the variant that counts lookups, rays, lane slots
-        p.G4 = std::min(k.refill, chunks);  // waves per car
-        p.geo_ready = !single && k.has_geo;  // leading geometry items (a multiple of 8: XCD mapping kept)
-        p.geo_blocks = p.geo_ready ? ((EA * (k.A - 1) + 63) / 64 + 7) / 8 * 8 : 0;
-        const int wpb = p.lds ? kFxsWaves : 1;  // k_rays_fxs's work items per block
-        p.grid = (uint32_t)((p.geo_blocks + EA * p.G4 + wpb - 1) / wpb);
-        p.block = 64u * (uint32_t)wpb;
-    }
-    return p;
-}
-
 // The kernel of a plan: every ray kernel the library instantiates is named here.
 #define RAY_FN(...) reinterpret_cast<const void *>(&__VA_ARGS__)
 static const void *ray_kernel_fn(const RayPlan &p) {

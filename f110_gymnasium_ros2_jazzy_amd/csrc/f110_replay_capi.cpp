@@ -1,42 +1,27 @@
 // f110_replay_capi.cpp — host side of the learner's device components
 // (include/f110.h, "prioritized experience replay", "n-step returns" and
 // "learner optimizer"): argument checks, the device allocation at create, the
-// launches of f110_replay.hip / f110_adam.hip, and the host hook
-// f110_host_nstep (include/f110_debug.h).
+// launches of f110_replay.hip / f110_adam.hip.  (The n-step host model,
+// f110_host_nstep, and the argument checks it shares are in f110_host.cpp.)
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
 #include <string>
-#include <vector>
 
-#include "f110_internal.h"
+#include "f110_host.h"
 
 using namespace f110;
 
-int f110_set_error(int code, const std::string &msg);  // f110_capi.cpp
-
-namespace {
-int fail(int code, const std::string &msg) { return f110_set_error(code, msg); }
-}  // namespace
-
 struct f110_replay {
-    int device = 0;
+    DeviceArena arena;
     int64_t max_add = 0;
     int32_t max_batch = 0;
     int64_t known_len = 0;  // a lower bound of the device length seen by f110_replay_length (never shrinks)
     ReplayView v{};
-    std::vector<void *> allocs;
 
+    // n elements and 16 bytes of slack (the vectorised row copies), not cleared
     template <class T>
     hipError_t alloc(T **p, size_t n) {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, n * sizeof(T) + 16);
-        if (e == hipSuccess) {
-            allocs.push_back(q);
-            *p = static_cast<T *>(q);
-        }
-        return e;
+        return arena.alloc(p, n, /*zero=*/false, 16);
     }
 };
 
@@ -53,7 +38,7 @@ extern "C" int f110_replay_create(f110_replay **out, int32_t device, int64_t cap
         return fail(F110_E_NODEVICE, "f110_replay_create: no such HIP device");
     if (hipSetDevice(device) != hipSuccess) return fail(F110_E_NODEVICE, "f110_replay_create: hipSetDevice");
     auto *rb = new f110_replay();
-    rb->device = device;
+    rb->arena.device = device;
     rb->max_add = max_add;
     rb->max_batch = max_batch;
     ReplayView &v = rb->v;
@@ -86,18 +71,14 @@ extern "C" int f110_replay_create(f110_replay **out, int32_t device, int64_t cap
     if (e == hipSuccess) e = prepare_replay(max_batch);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
-        for (void *q : rb->allocs) (void)hipFree(q);
-        delete rb;
-        return fail(F110_E_ALLOC, std::string("f110_replay_create: ") + hipGetErrorString(e));
+        delete rb;  // (the arena frees what was allocated)
+        return hip_fail("f110_replay_create", e, F110_E_ALLOC);
     }
     *out = rb;
     return F110_OK;
 }
 
 extern "C" int f110_replay_destroy(f110_replay *rb) {
-    if (!rb) return F110_OK;
-    (void)hipSetDevice(rb->device);
-    for (void *q : rb->allocs) (void)hipFree(q);
     delete rb;
     return F110_OK;
 }
@@ -116,7 +97,7 @@ int replay_add(f110_replay *rb, const char *fn, const float *obs, int64_t obs_st
     if (!obs || !act || (!reward && !reward64) || !next_obs || obs_stride < v.obs_dim || next_stride < v.obs_dim ||
         act_stride < v.act_dim)
         return fail(F110_E_INVALID, std::string(fn) + ": null row pointer or stride below the row length");
-    if (hipSetDevice(rb->device) != hipSuccess) return fail(F110_E_HIP, std::string(fn) + ": hipSetDevice");
+    if (hipSetDevice(rb->arena.device) != hipSuccess) return fail(F110_E_HIP, std::string(fn) + ": hipSetDevice");
     ReplayRows in{};
     in.obs = obs;
     in.next_obs = next_obs;
@@ -133,7 +114,7 @@ int replay_add(f110_replay *rb, const char *fn, const float *obs, int64_t obs_st
     const hipStream_t s = (hipStream_t)stream;
     hipError_t e = launch_replay_add_index(v, mask, mask_skip, priority, n, s);
     if (e == hipSuccess) e = launch_replay_add_copy(v, in, n, s);
-    if (e != hipSuccess) return fail(F110_E_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail(fn, e);
     return F110_OK;
 }
 }  // namespace
@@ -162,7 +143,7 @@ extern "C" int f110_replay_sample(f110_replay *rb, int32_t batch, double beta, i
     if (batch <= 0 || batch > rb->max_batch) return fail(F110_E_INVALID, "f110_replay_sample: batch must be in [1, max_batch]");
     if (obs && (!act || !reward || !next_obs || !done))
         return fail(F110_E_INVALID, "f110_replay_sample: give all batch outputs or none");
-    if (hipSetDevice(rb->device) != hipSuccess) return fail(F110_E_HIP, "f110_replay_sample: hipSetDevice");
+    if (hipSetDevice(rb->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_replay_sample: hipSetDevice");
     ReplayBatch out{};
     out.obs = obs;
     out.next_obs = next_obs;
@@ -173,7 +154,7 @@ extern "C" int f110_replay_sample(f110_replay *rb, int32_t batch, double beta, i
     const hipStream_t s = (hipStream_t)stream;
     hipError_t e = launch_replay_select(rb->v, batch, beta, idx, weights, rb->known_len >= batch, s);
     if (e == hipSuccess) e = launch_replay_gather(rb->v, batch, idx, out, s);
-    if (e != hipSuccess) return fail(F110_E_HIP, std::string("f110_replay_sample: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail("f110_replay_sample", e);
     return F110_OK;
 }
 
@@ -181,19 +162,19 @@ extern "C" int f110_replay_update_priorities(f110_replay *rb, const int64_t *idx
                                              int32_t from_td, float add_eps, void *stream) {
     if (!rb || n < 0 || (n > 0 && (!idx || !values)))
         return fail(F110_E_INVALID, "f110_replay_update_priorities: bad arguments");
-    if (hipSetDevice(rb->device) != hipSuccess) return fail(F110_E_HIP, "f110_replay_update_priorities: hipSetDevice");
+    if (hipSetDevice(rb->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_replay_update_priorities: hipSetDevice");
     hipError_t e = launch_replay_update(rb->v, idx, values, n, add_eps, from_td ? 1 : 0, 0, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(F110_E_HIP, std::string("f110_replay_update_priorities: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail("f110_replay_update_priorities", e);
     return F110_OK;
 }
 
 extern "C" int f110_replay_length(f110_replay *rb, int64_t *length, int64_t *next_idx, void *stream) {
     if (!rb) return fail(F110_E_INVALID, "f110_replay_length: null buffer");
-    if (hipSetDevice(rb->device) != hipSuccess) return fail(F110_E_HIP, "f110_replay_length: hipSetDevice");
+    if (hipSetDevice(rb->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_replay_length: hipSetDevice");
     ReplayHdr h{};
     hipError_t e = hipMemcpyAsync(&h, rb->v.hdr, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return fail(F110_E_HIP, std::string("f110_replay_length: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail("f110_replay_length", e);
     if (length) *length = h.length;
     if (next_idx) *next_idx = h.next;
     if (h.length > rb->known_len) rb->known_len = h.length;  // the ring never shrinks
@@ -214,44 +195,15 @@ extern "C" int f110_replay_arrays(f110_replay *rb, float **priority, float **obs
 
 // ---- n-step accumulator -------------------------------------------------------
 struct f110_nstep {
-    int device = 0;
+    DeviceArena arena;
     NstepView w{};
-    std::vector<void *> allocs;
 
+    // n elements and 16 bytes of slack (the vectorised row copies), all zero
     template <class T>
     hipError_t alloc(T **p, size_t n) {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, n * sizeof(T) + 16);
-        if (e == hipSuccess) e = hipMemset(q, 0, n * sizeof(T) + 16);
-        if (e == hipSuccess || q) allocs.push_back(q);
-        if (e == hipSuccess) *p = static_cast<T *>(q);
-        return e;
+        return arena.alloc(p, n, /*zero=*/true, 16);
     }
 };
-
-namespace {
-int check_nstep_args(const char *fn, int64_t n_envs, int32_t n_step, double gamma, int32_t obs_dim, int32_t act_dim) {
-    if (n_step < 1 || n_step > kNstepMax) return fail(F110_E_INVALID, std::string(fn) + ": n_step must be in [1, 16]");
-    if (!std::isfinite(gamma) || gamma < 0.0 || gamma > 1.0)
-        return fail(F110_E_INVALID, std::string(fn) + ": gamma must be finite and in [0, 1]");
-    if (n_envs <= 0 || n_envs * n_step >= (int64_t)1 << 31)
-        return fail(F110_E_INVALID, std::string(fn) + ": n_envs must be positive (n_envs * n_step < 2^31)");
-    if (obs_dim <= 0 || act_dim <= 0 || act_dim > 256)
-        return fail(F110_E_INVALID, std::string(fn) + ": obs_dim > 0 and 0 < act_dim <= 256");
-    return F110_OK;
-}
-
-int check_nstep_capacity(const char *fn, int64_t n_envs, int32_t n_step, int64_t capacity) {
-    if (n_envs * n_step > capacity)
-        return fail(F110_E_INVALID, std::string(fn) + ": n_envs * n_step must not exceed the replay's capacity");
-    return F110_OK;
-}
-
-void nstep_powers(double gamma, int n, double *pw) {  // sequential products
-    pw[0] = 1.0;
-    for (int i = 1; i <= n; ++i) pw[i] = pw[i - 1] * gamma;
-}
-}  // namespace
 
 extern "C" int f110_nstep_create(f110_nstep **out, int32_t device, int64_t n_envs, int32_t n_step, double gamma,
                                  int32_t obs_dim, int32_t act_dim) {
@@ -263,7 +215,7 @@ extern "C" int f110_nstep_create(f110_nstep **out, int32_t device, int64_t n_env
         return fail(F110_E_NODEVICE, "f110_nstep_create: no such HIP device");
     if (hipSetDevice(device) != hipSuccess) return fail(F110_E_NODEVICE, "f110_nstep_create: hipSetDevice");
     auto *ns = new f110_nstep();
-    ns->device = device;
+    ns->arena.device = device;
     NstepView &w = ns->w;
     w.n_envs = n_envs;
     w.n = n_step;
@@ -290,18 +242,14 @@ extern "C" int f110_nstep_create(f110_nstep **out, int32_t device, int64_t n_env
     if (e == hipSuccess) e = hipMemcpy(dpw, pw, ((size_t)n_step + 1) * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
-        for (void *q : ns->allocs) (void)hipFree(q);
-        delete ns;
-        return fail(F110_E_ALLOC, std::string("f110_nstep_create: ") + hipGetErrorString(e));
+        delete ns;  // (the arena frees what was allocated)
+        return hip_fail("f110_nstep_create", e, F110_E_ALLOC);
     }
     *out = ns;
     return F110_OK;
 }
 
 extern "C" int f110_nstep_destroy(f110_nstep *ns) {
-    if (!ns) return F110_OK;
-    (void)hipSetDevice(ns->device);
-    for (void *q : ns->allocs) (void)hipFree(q);
     delete ns;
     return F110_OK;
 }
@@ -313,7 +261,7 @@ extern "C" int f110_nstep_push(f110_nstep *ns, f110_replay *rb, const float *obs
     if (!ns || !rb) return fail(F110_E_INVALID, "f110_nstep_push: null accumulator or buffer");
     const NstepView &w = ns->w;
     const ReplayView &v = rb->v;
-    if (ns->device != rb->device) return fail(F110_E_INVALID, "f110_nstep_push: accumulator and buffer on different devices");
+    if (ns->arena.device != rb->arena.device) return fail(F110_E_INVALID, "f110_nstep_push: accumulator and buffer on different devices");
     if (w.obs_dim != v.obs_dim || w.act_dim != v.act_dim)
         return fail(F110_E_INVALID, "f110_nstep_push: obs_dim / act_dim differ from the replay's");
     const int rc = check_nstep_capacity("f110_nstep_push", w.n_envs, w.n, v.capacity);
@@ -321,7 +269,7 @@ extern "C" int f110_nstep_push(f110_nstep *ns, f110_replay *rb, const float *obs
     if (!obs || !act || !reward || !next_obs || !terminated || !was_reset || obs_stride < v.obs_dim ||
         next_stride < v.obs_dim || act_stride < v.act_dim)
         return fail(F110_E_INVALID, "f110_nstep_push: null row pointer or stride below the row length");
-    if (hipSetDevice(ns->device) != hipSuccess) return fail(F110_E_HIP, "f110_nstep_push: hipSetDevice");
+    if (hipSetDevice(ns->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_nstep_push: hipSetDevice");
     NstepRows in{};
     in.obs = obs;
     in.act = act;
@@ -337,15 +285,15 @@ extern "C" int f110_nstep_push(f110_nstep *ns, f110_replay *rb, const float *obs
     in.vec4 = (v.obs_dim % 4 == 0 && obs_stride % 4 == 0 && next_stride % 4 == 0 && aligned16(obs) &&
                aligned16(next_obs)) ? 1 : 0;
     hipError_t e = launch_nstep_push(v, w, in, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(F110_E_HIP, std::string("f110_nstep_push: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail("f110_nstep_push", e);
     return F110_OK;
 }
 
 extern "C" int f110_nstep_reset(f110_nstep *ns, const uint8_t *env_mask, void *stream) {
     if (!ns) return fail(F110_E_INVALID, "f110_nstep_reset: null accumulator");
-    if (hipSetDevice(ns->device) != hipSuccess) return fail(F110_E_HIP, "f110_nstep_reset: hipSetDevice");
+    if (hipSetDevice(ns->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_nstep_reset: hipSetDevice");
     hipError_t e = launch_nstep_reset(ns->w, env_mask, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(F110_E_HIP, std::string("f110_nstep_reset: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail("f110_nstep_reset", e);
     return F110_OK;
 }
 
@@ -358,46 +306,6 @@ extern "C" int f110_nstep_arrays(f110_nstep *ns, int32_t **len, int32_t **head, 
     if (k) *k = ns->w.k;
     if (obs) *obs = ns->w.obs;
     if (act) *act = ns->w.act;
-    return F110_OK;
-}
-
-extern "C" int f110_host_nstep(int64_t n_envs, int32_t n_step, double gamma, int32_t obs_dim, int32_t act_dim,
-                               int64_t capacity, int32_t *len, int32_t *head, double *ret, int32_t *k, float *win_obs,
-                               float *win_act, const float *obs, const float *act, const double *reward,
-                               const float *next_obs, const uint8_t *terminated, const uint8_t *truncated,
-                               const uint8_t *was_reset, float *out_obs, float *out_act, float *out_reward,
-                               float *out_next_obs, float *out_done, int64_t *out_count) {
-    int rc = check_nstep_args("f110_host_nstep", n_envs, n_step, gamma, obs_dim, act_dim);
-    if (rc == F110_OK && capacity > 0) rc = check_nstep_capacity("f110_host_nstep", n_envs, n_step, capacity);
-    if (rc != F110_OK) return rc;
-    if (!len || !head || !ret || !k || !win_obs || !win_act || !obs || !act || !reward || !next_obs || !terminated ||
-        !was_reset || !out_obs || !out_act || !out_reward || !out_next_obs || !out_done || !out_count)
-        return fail(F110_E_INVALID, "f110_host_nstep: null argument");
-    const int n = n_step;
-    const size_t D = (size_t)obs_dim, A = (size_t)act_dim;
-    double pw[kNstepMax + 1];
-    nstep_powers(gamma, n, pw);
-    int64_t row = 0;
-    for (int64_t e = 0; e < n_envs; ++e) {
-        int32_t e_slot[kNstepMax], store;
-        float e_reward[kNstepMax], e_done[kNstepMax];
-        const int cnt = nstep_update(n, pw, reward[e], terminated[e], truncated ? truncated[e] : 0, was_reset[e], len[e],
-                                     head[e], ret + e * n, k + e * n, e_slot, e_reward, e_done, store);
-        for (int j = 0; j < cnt; ++j, ++row) {
-            const float *so = e_slot[j] < 0 ? obs + e * D : win_obs + ((size_t)e * n + e_slot[j]) * D;
-            const float *sa = e_slot[j] < 0 ? act + e * A : win_act + ((size_t)e * n + e_slot[j]) * A;
-            std::copy(so, so + D, out_obs + row * D);
-            std::copy(sa, sa + A, out_act + row * A);
-            std::copy(next_obs + e * D, next_obs + (e + 1) * D, out_next_obs + row * D);
-            out_reward[row] = e_reward[j];
-            out_done[row] = e_done[j];
-        }
-        if (store >= 0) {
-            std::copy(obs + e * D, obs + (e + 1) * D, win_obs + ((size_t)e * n + store) * D);
-            std::copy(act + e * A, act + (e + 1) * A, win_act + ((size_t)e * n + store) * A);
-        }
-    }
-    *out_count = row;
     return F110_OK;
 }
 
@@ -421,6 +329,6 @@ extern "C" int f110_adam_step(float *param, float *exp_avg, float *exp_avg_sq, c
     a.tau = (float)tau;
     a.done = reinterpret_cast<uint32_t *>(static_cast<int64_t *>(state) + 1);
     hipError_t e = launch_adam(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(F110_E_HIP, std::string("f110_adam_step: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail("f110_adam_step", e);
     return F110_OK;
 }

@@ -1,0 +1,163 @@
+// f110_task_capi.cpp — the context-free training entry points of include/f110.h: the track of the
+// progress reward (f110_track_*), f110_reward, f110_gap_follow, the collision batches and the
+// episode statistics.  Argument checks and launches; the kernels are in f110_reward.hip,
+// f110_opponent.hip, f110_kernels.hip and f110_episode.hip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "f110_host.h"
+
+using namespace f110;
+
+// ---- training reward (rewards.py / track_progress.py) -----------------------
+struct f110_track {
+    DeviceArena arena;  // empty for a host-only track
+    TrackView v{};
+    std::vector<double> s, tan, nrm, mid;
+};
+
+extern "C" int f110_track_create(f110_track **out, int32_t device, const double *xy, const double *w_right,
+                                 const double *w_left, int32_t n, int32_t closed) {
+    if (!out || !xy || n < 2 || ((w_right == nullptr) != (w_left == nullptr)))
+        return fail(F110_E_INVALID, "f110_track_create: bad arguments (need >= 2 centerline points)");
+    const bool host_only = device < 0;  // derived arrays only (f110_track_arrays), no device copy
+    if (!host_only && hipSetDevice(device) != hipSuccess)
+        return fail(F110_E_NODEVICE, "f110_track_create: no such HIP device");
+    auto *t = new f110_track();
+    t->arena.device = device;
+    track_arrays(xy, n, t->s, t->tan, t->nrm, t->mid);
+    if (!host_only) {
+        const TrackGrid g = track_grid(xy, n, t->mid);
+        DeviceArena &a = t->arena;
+        TrackView &v = t->v;
+        if (!g.cstart.empty()) {
+            v.gh = g.gh;
+            v.gx0 = g.gx0;
+            v.gy0 = g.gy0;
+            v.gnx = g.gnx;
+            v.gny = g.gny;
+        }
+        hipError_t e = a.upload(&v.xy, xy, 2 * (size_t)n);
+        if (e == hipSuccess && !g.cstart.empty()) e = a.upload(&v.cell_start, g.cstart.data(), g.cstart.size());
+        if (e == hipSuccess && !g.citems.empty()) e = a.upload(&v.cell_items, g.citems.data(), g.citems.size());
+        if (e == hipSuccess && !g.cmid.empty()) e = a.upload(&v.cell_mid, g.cmid.data(), g.cmid.size());
+        if (e == hipSuccess) e = a.upload(&v.s, t->s.data(), t->s.size());
+        if (e == hipSuccess) e = a.upload(&v.tan, t->tan.data(), t->tan.size());
+        if (e == hipSuccess) e = a.upload(&v.nrm, t->nrm.data(), t->nrm.size());
+        if (e == hipSuccess) e = a.upload(&v.mid, t->mid.data(), t->mid.size());
+        if (e == hipSuccess && w_right) e = a.upload(&v.wR, w_right, (size_t)n);
+        if (e == hipSuccess && w_left) e = a.upload(&v.wL, w_left, (size_t)n);
+        if (e != hipSuccess) {
+            delete t;  // (the arena frees what was uploaded)
+            return hip_fail("f110_track_create", e);
+        }
+    }
+    t->v.n = n;
+    t->v.closed = closed ? 1 : 0;
+    t->v.L = t->s[(size_t)n - 1];
+    *out = t;
+    return F110_OK;
+}
+
+extern "C" int f110_track_destroy(f110_track *t) {
+    delete t;
+    return F110_OK;
+}
+
+extern "C" double f110_track_arrays(const f110_track *t, double *s, double *tan, double *nrm, double *mid) {
+    if (!t) return 0.0;
+    if (s) std::copy(t->s.begin(), t->s.end(), s);
+    if (tan) std::copy(t->tan.begin(), t->tan.end(), tan);
+    if (nrm) std::copy(t->nrm.begin(), t->nrm.end(), nrm);
+    if (mid) std::copy(t->mid.begin(), t->mid.end(), mid);
+    return t->v.L;
+}
+
+extern "C" int f110_reward(const f110_track *track, const f110_reward_params *params, const float *obs,
+                           int64_t n_envs, int32_t obs_len, int32_t n_beams, f110_reward_state *state,
+                           const uint8_t *reset_mask, double *rewards, void *stream) {
+    if (!params || n_envs < 0 || (n_envs > 0 && (!obs || !state || !rewards)) || n_beams < 0 || n_beams > 2048 ||
+        obs_len < n_beams + 8)
+        return fail(F110_E_INVALID, "f110_reward: bad arguments (obs rows need n_beams + 8 entries, n_beams <= 2048)");
+    if (params->use_progress && (!track || !track->v.mid))
+        return fail(F110_E_INVALID, "f110_reward: use_progress needs a device track");
+    RewardArgs a{};
+    if (track) a.track = track->v;
+    a.p = *params;
+    a.obs = obs;
+    a.E = n_envs;
+    a.obs_len = obs_len;
+    a.B = n_beams;
+    a.state = state;
+    a.reset_mask = reset_mask;
+    a.rewards = rewards;
+    HIP_TRY(launch_reward(a, (hipStream_t)stream));
+    return F110_OK;
+}
+
+// ---- gap-follow opponent, collision batches -----------------------------------
+extern "C" int f110_gap_follow(const float *scans, int64_t n_scans, int64_t scan_stride, int32_t n_beams,
+                               double angle_min, double angle_increment, float *actions, int64_t action_stride,
+                               int32_t *gaps, void *stream) {
+    if (n_scans < 0 || n_beams <= 0 || (n_scans > 0 && (!scans || !actions)) || scan_stride < n_beams ||
+        action_stride < 2)
+        return fail(F110_E_INVALID, "f110_gap_follow: bad arguments");
+    if (gap_follow_lds_bytes(n_beams) > 160 * 1024) return fail(F110_E_INVALID, "f110_gap_follow: n_beams too large");
+    GapFollowArgs a;
+    a.scans = scans;
+    a.M = n_scans;
+    a.scan_stride = scan_stride;
+    a.action_stride = action_stride;
+    a.actions = actions;
+    a.gaps = gaps;
+    a.angle_min = angle_min;
+    a.angle_increment = angle_increment;
+    a.B = n_beams;
+    HIP_TRY(launch_gap_follow(a, (hipStream_t)stream));
+    return F110_OK;
+}
+
+extern "C" int f110_collision_batch(const double *v1, const double *v2, int64_t M, uint8_t *out, void *stream) {
+    if (M < 0 || (M > 0 && (!v1 || !v2 || !out))) return fail(F110_E_INVALID, "f110_collision_batch: bad arguments");
+    HIP_TRY(launch_collision_batch(v1, v2, M, out, (hipStream_t)stream));
+    return F110_OK;
+}
+
+extern "C" int f110_collision_multiple(const double *verts, int64_t M, int32_t N, double *collisions, double *idx,
+                                       void *stream) {
+    if (M < 0 || N < 1 || N > kMaxMultiBodies || (M > 0 && (!verts || !collisions || !idx)))
+        return fail(F110_E_INVALID, "f110_collision_multiple: bad arguments (1 <= N <= 64)");
+    HIP_TRY(launch_collision_multiple(verts, M, N, collisions, idx, (hipStream_t)stream));
+    return F110_OK;
+}
+
+// ----------------------------------------------------- episode statistics --
+extern "C" int64_t f110_episode_scratch_bytes(int64_t n_envs) {
+    return (n_envs > 0 ? episode_blocks(n_envs) : 1) * (int64_t)sizeof(EpisodePart);
+}
+
+extern "C" int f110_episode_stats(const double *rewards, const uint8_t *terminated, const uint8_t *truncated,
+                                  const uint8_t *was_reset, int64_t n_envs, f110_episode_state *state,
+                                  double *last_return, int32_t *last_length, uint8_t *finished,
+                                  f110_episode_totals *totals, void *scratch, void *stream) {
+    const int rc = check_episode_args("f110_episode_stats", rewards, terminated, was_reset, n_envs, state, totals);
+    if (rc != F110_OK) return rc;
+    if (!scratch) return fail(F110_E_INVALID, "f110_episode_stats: null scratch");
+    EpisodeArgs a{};
+    a.rewards = rewards;
+    a.terminated = terminated;
+    a.truncated = truncated;
+    a.was_reset = was_reset;
+    a.E = n_envs;
+    a.state = state;
+    a.last_return = last_return;
+    a.last_length = last_length;
+    a.finished = finished;
+    a.totals = totals;
+    a.part = static_cast<EpisodePart *>(scratch);
+    HIP_TRY(launch_episode_stats(a, (hipStream_t)stream));
+    return F110_OK;
+}

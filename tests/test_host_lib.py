@@ -36,6 +36,32 @@ def test_exports_every_declared_symbol(L):
     assert sorted(_lib.EXPORTS) == names
 
 
+def declared_prototypes():
+    """name -> (return type, parameter count) of every F110_API prototype, comments stripped."""
+    protos = {}
+    for h in ("f110.h", "f110_debug.h"):
+        txt = open(os.path.join(REPO, "include", h)).read()
+        txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+        txt = re.sub(r"//[^\n]*", " ", txt)
+        for ret, name, params in re.findall(r"\bF110_API\s+([\w\s\*]+?)\s*\b(f110_\w+)\s*\(([^()]*)\)\s*;", txt):
+            params = " ".join(params.split())
+            protos[name] = (" ".join(ret.split()), 0 if params in ("", "void") else params.count(",") + 1)
+    return protos
+
+
+def test_bindings_match_prototypes(L):
+    """_lib's one table against the headers: every entry point's argument count and return type."""
+    from f110_gymnasium_ros2_jazzy_amd import _lib
+    ctype = {"int": ctypes.c_int, "void": None, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+             "double": ctypes.c_double, "const char *": ctypes.c_char_p}
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols() == sorted(_lib.EXPORTS)
+    for name, (ret, n_params) in protos.items():
+        fn = getattr(L, name)
+        assert len(fn.argtypes) == n_params, f"{name}: {len(fn.argtypes)} argtypes, {n_params} parameters declared"
+        assert fn.restype is ctype[ret], f"{name}: restype {fn.restype}, declared {ret}"
+
+
 def test_abi_and_defaults(L):
     from f110_gymnasium_ros2_jazzy_amd import _lib
     assert L.f110_abi_version() == 3
