@@ -13,10 +13,10 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libf110.so")
-SOURCES = ["f110_kernels.hip", "f110_opponent.hip", "f110_reward.hip", "f110_episode.hip", "f110_replay.hip", "f110_adam.hip", "f110_ddpg.hip", "f110_gemm.hip",
+SOURCES = ["f110_agents.hip", "f110_rays_tiled.hip", "f110_rays_fx.hip", "f110_rays_fxs.hip", "f110_post.hip", "f110_step.cpp",
+           "f110_batch.hip", "f110_opponent.hip", "f110_reward.hip", "f110_episode.hip", "f110_replay.hip", "f110_adam.hip", "f110_ddpg.hip", "f110_gemm.hip",
            "f110_host.cpp", "f110_ctx.cpp", "f110_ctx_debug.cpp", "f110_task_capi.cpp",
            "f110_replay_capi.cpp"]
-HEADERS = ["f110_device.h", "f110_internal.h", "f110_sincos_table.h", "f110_host_util.h", "f110_host.h", "f110_ctx.h"]
 ARCH = os.environ.get("F110_OFFLOAD_ARCH", "gfx950")
 
 # -ffp-contract=off: the reference (Python/Numba) never fuses a*b+c; hipcc
@@ -36,7 +36,8 @@ def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(REPO, "include", "f110.h"),
+    headers = [f for f in os.listdir(CSRC) if f.endswith(".h")]  # every header on disk: none to forget
+    deps = [os.path.join(CSRC, f) for f in SOURCES + headers] + [os.path.join(REPO, "include", "f110.h"),
                                                                   os.path.join(REPO, "include", "f110_debug.h"),
                                                                   __file__]
     return any(os.path.getmtime(d) > t for d in deps)

@@ -289,7 +289,7 @@ extern "C" int f110_edt_k(const uint8_t *free_mask, int32_t H, int32_t W, uint32
 // ------------------------------------------------- map views and EDT tables --
 namespace f110 {
 
-// k_rays_fx's preconditions (f110_kernels.hip): an axis-aligned map (origin
+// k_rays_fx's preconditions (f110_rays_fx.h): an axis-aligned map (origin
 // yaw 0: cos 1, sin 0 exactly, so x_rot == x_trans), one-wave blocks, H and W
 // below 2^21 and |origin / res| below 2^20 (on-map t = 1.5*2^22 + q stays in
 // [2^22, 2^23)), and every EDT entry 0 or above eps (the loop's d > eps is

@@ -159,7 +159,7 @@ struct RayArgs {
     const uint32_t *heavy_count;
     int32_t HB, nch;
     int32_t wpb;  // chunked: waves (cars) per block
-    // fixed-point cell index of k_rays_fx (see fx_cell in f110_kernels.hip):
+    // fixed-point cell index of k_rays_fx (see fx_step in f110_rays_fx.h):
     // t = fma(x, inv_res, fx_cx) = 1.5*2^22 + column, on a 2^-30 grid
     double fx_cx, fx_cy;
     // |q| bound of a scan origin whose rays stay in t's binade: 2^21 - 32 - max_range / res
@@ -428,8 +428,20 @@ struct AdamArgs {
 };
 hipError_t launch_adam(const AdamArgs &a, hipStream_t s);
 
+// ---- the env step (f110_step.cpp) and its stages, one translation unit each --------------------
 hipError_t launch_env_step(const StepArgs &a, const RayLaunch &r, hipStream_t s,
                            hipEvent_t *ev = nullptr);  // ev: 6 events or null
+// start / stop: the events of the kernel's own dispatch, or null
+hipError_t launch_agents(const StepArgs &a, hipStream_t s, hipEvent_t start, hipEvent_t stop);  // f110_agents.hip
+hipError_t launch_post(const StepArgs &a, bool geo_ready, hipStream_t s, hipEvent_t start,
+                       hipEvent_t stop);  // f110_post.hip; geo_ready: the ray launch computed a.geo
+// The kernel of a plan of the family: each ray file owns the table of its instantiations, and no
+// kernel is referenced from another translation unit except through these.
+using RayKernel = void (*)(RayArgs);
+RayKernel tiled_ray_kernel(const RayPlan &p);  // f110_rays_tiled.hip
+RayKernel fx_ray_kernel(const RayPlan &p);     // f110_rays_fx.hip: k_rays_fx, k_rays_fxn
+RayKernel fxs_ray_kernel(const RayPlan &p);    // f110_rays_fxs.hip
+// ---- the C-ABI batch kernels (f110_batch.hip) and the task kernels ----------------------------
 hipError_t launch_scan_batch(const ScanArgs &a, hipStream_t s);
 hipError_t launch_gap_follow(const GapFollowArgs &a, hipStream_t s);
 hipError_t launch_reward(const RewardArgs &a, hipStream_t s);

@@ -1,7 +1,7 @@
 // f110_task_capi.cpp — the context-free training entry points of include/f110.h: the track of the
 // progress reward (f110_track_*), f110_reward, f110_gap_follow, the collision batches and the
 // episode statistics.  Argument checks and launches; the kernels are in f110_reward.hip,
-// f110_opponent.hip, f110_kernels.hip and f110_episode.hip.
+// f110_opponent.hip, f110_batch.hip and f110_episode.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

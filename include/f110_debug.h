@@ -139,7 +139,7 @@ F110_API int f110_debug_set_ray_lanes(f110_ctx *ctx, int32_t n);
 /* ---- the ray launch plan (host) --------------------------------------------
  * Which ray kernel a context launches, on which grid and EDT table, is one
  * pure function of the plain values below (plan_ray_launch in
- * f110_kernels.hip): f110_step / f110_reset launch what it
+ * f110_host.cpp): f110_step / f110_reset launch what it
  * returns, and the f110_debug_ray_* getters read it. */
 enum { F110_RAY_TILED_FLAT = 0, F110_RAY_TILED_CHUNKED, F110_RAY_FX, F110_RAY_FXN_CLAMPED, F110_RAY_FXN_PADDED,
        F110_RAY_FXS };

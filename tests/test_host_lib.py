@@ -589,3 +589,23 @@ def test_ray_size_rules(L, own, device, contexts, kernel, pad, want):
     assert L.f110_host_ray_rules(own, device, contexts, kernel, pad, out) == 0
     assert tuple(out) == want
     assert L.f110_host_ray_rules(device + 1, device, contexts, kernel, pad, out) < 0
+
+
+def test_sources_on_disk_and_launchers_defined_once():
+    """_build.SOURCES is exactly the csrc/*.hip and csrc/*.cpp on disk, and every launch_* /
+    *_ray_kernel that f110_internal.h declares is defined in exactly one of them (a text scan: a
+    definition is the name at the start of a line's declarator followed by its body's brace)."""
+    from f110_gymnasium_ros2_jazzy_amd import _build
+
+    on_disk = sorted(f for f in os.listdir(_build.CSRC) if f.endswith((".hip", ".cpp")))
+    assert sorted(_build.SOURCES) == on_disk
+    with open(os.path.join(_build.CSRC, "f110_internal.h")) as fh:
+        names = sorted(set(re.findall(r"\b(launch_\w+|\w+_ray_kernel)\s*\(", fh.read())))
+    assert len(names) >= 20 and {"launch_agents", "launch_post", "launch_env_step", "fxs_ray_kernel"} <= set(names)
+    text = {}
+    for f in on_disk:
+        with open(os.path.join(_build.CSRC, f)) as fh:
+            text[f] = fh.read()
+    for n in names:
+        defined = [f for f, t in text.items() if re.search(r"^[A-Za-z_][\w:<> \*&]*\b%s\s*\([^;{]*\)\s*\{" % n, t, re.M)]
+        assert len(defined) == 1, (n, defined)

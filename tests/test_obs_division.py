@@ -1,4 +1,4 @@
-"""k_rays_fxs's obs-entry division (f110_kernels.hip obs_scan_value_fast):
+"""k_rays_fxs's obs-entry division (f110_rays_fx.h obs_scan_value_fast):
 F110Env._pack_flat_obs divides the clipped float32 scan by lidar_max in
 float32 (f110_env.py:557-560).  The kernel computes q = v * y, r = fma(-q,
 lm, v), q' = fma(r, y, q) with y = RN(1 / lm) (obs_reciprocal,
