@@ -208,6 +208,10 @@ _API = {
     "f110_ddpg_actor_explore_env": (_i, _EXPLORE + [_i32, _P, _f64, _f64, _f64, _P, _P, _P, _P]),
     "f110_host_explore_rows": (_i, [_P, _P, _i64, _i32, _i32, _P, _f64, _f64, _f64, _P, _P, _P, _P, _f64, _f64, _P,
                                     _P, _P]),
+    "f110_td3_target_action": (_i, [_P] * 5 + [_i32] * 3 + [_f32, _f32, _P, _P, _u64, _P, _P, _P, _P]),
+    "f110_td3_critic_step": (_i, [_P] * 8 + [_f32] + [_P] * 8 + [_i32, _i32] + [_P] * 9),
+    "f110_host_td3_smooth_rows": (_i, [_P, _P, _i64, _i32, _f32, _f32, _P, _P, _P, _P]),
+    "f110_host_td3_rows": (_i, [_P, _P, _f32] + [_P] * 5 + [_f32, _i64] + [_P] * 6),
     "f110_nstep_create": (_i, [ctypes.POINTER(_P), _i32, _i64, _i32, _f64, _i32, _i32]),
     "f110_nstep_destroy": (_i, [_P]),
     "f110_nstep_push": (_i, [_P, _P, _P, _i64, _P, _i64, _P, _P, _i64, _P, _P, _P, _P]),

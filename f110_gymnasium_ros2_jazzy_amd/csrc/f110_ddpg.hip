@@ -22,18 +22,12 @@
 #include <string>
 #include <type_traits>
 
+#include "f110_head_rows.h"
 #include "f110_host_util.h"
 #include "f110_internal.h"
 
 namespace f110 {
 namespace {
-
-constexpr int kHB = 256;      // threads per block
-constexpr int kRowLanes = 32; // lanes per row (a half-wave): 4 columns each (K <= 128 in one pass)
-constexpr int kRowsPerBlock = kHB / kRowLanes;
-constexpr int kWRows = 64;    // rows per block of the weight-gradient pass
-constexpr int kMaxOut = 4;    // head outputs (act_dim <= 4)
-constexpr int kMaxK = 255;    // hidden width (the weight pass keeps >= 3 row lanes of column quads)
 
 enum HeadMode { kActor = 0, kTarget = 1, kLoss = 2, kMean = 3, kExplore = 4, kExploreEnv = 5 };
 
@@ -68,96 +62,14 @@ struct HeadArgs {
     int32_t kind;
 };
 
-// choose_action's exploration noise (agent.py:350-370, GaussianActionNoise
-// :520-539, np.random.normal(0, sigma)): N(0,1) pairs by Box-Muller on one
-// Philox2x32-10 block per (call, row, output pair), counter (step, row pair
-// index), key from the seed; f32 log / sqrt / sincospi on 24-bit uniforms
-// (u1 in (0, 1]).  Independent across rows, outputs and calls.
-__device__ __forceinline__ float2 explore_normals(uint64_t seed, uint64_t step, int64_t row, int pair) {
-    const uint32_t key = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x85EBCA6Bu) ^ ((uint32_t)(step >> 32) * 0xC2B2AE35u);
-    const U2 r = philox2x32((uint32_t)step, (uint32_t)(row * 2 + pair), key);
-    const float u1 = ((float)(r.x >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u2 = (float)(r.y >> 8) * (1.0f / 16777216.0f);
-    const float rad = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincospif(2.0f * u2, &sn, &cs);
-    return make_float2(rad * cs, rad * sn);
-}
-
-// sum over the 32 lanes of a half-wave (fixed tree); every lane gets it
-__device__ __forceinline__ float half_sum(float v) {
-#pragma unroll
-    for (int o = kRowLanes / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// z[j] = b[j] + sum_k h[k] W[j][k] for the row of this half-wave: lane l
-// takes columns 4l..4l+3 (+128, +256 ...), then a half-wave sum
-template <int NOUT>
-__device__ __forceinline__ void row_dot_of(const float *h, const float *W, const float *b, int32_t K, int64_t row,
-                                           int l, float (&z)[NOUT]) {
-    const float *hr = h + row * K;
-#pragma unroll
-    for (int j = 0; j < NOUT; ++j) z[j] = 0.0f;
-    for (int k = 4 * l; k < K; k += 4 * kRowLanes) {
-        float x[4];
-        if ((K & 3) == 0) {
-            const float4 v = *reinterpret_cast<const float4 *>(hr + k);
-            x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) x[i] = k + i < K ? hr[k + i] : 0.0f;
-        }
-#pragma unroll
-        for (int j = 0; j < NOUT; ++j)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (k + i < K) z[j] = fmaf(x[i], W[(size_t)j * K + k + i], z[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < NOUT; ++j) z[j] = half_sum(z[j]) + b[j];  // addmm: bias added to the product
-}
-
 template <int NOUT>
 __device__ __forceinline__ void row_dot(const HeadArgs &a, int64_t row, int l, float (&z)[NOUT]) {
     row_dot_of<NOUT>(a.h, a.W, a.b, a.K, row, l, z);
 }
 
-// dh[row] = dz W (lane l: columns 4l..4l+3, +128 ...), zero where dh_mask <= 0
 template <int NOUT>
 __device__ __forceinline__ void write_dh(const HeadArgs &a, int64_t row, int l, const float (&dz)[NOUT]) {
-    float *o = a.dh + row * a.K;
-    for (int k = 4 * l; k < a.K; k += 4 * kRowLanes) {
-        float r4[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float s = 0.0f;
-#pragma unroll
-            for (int j = 0; j < NOUT; ++j)
-                if (k + i < a.K) s = fmaf(dz[j], a.W[(size_t)j * a.K + k + i], s);
-            r4[i] = a.dh_mask && k + i < a.K && !(a.dh_mask[row * a.K + k + i] > 0.0f) ? 0.0f : s;
-        }
-        if ((a.K & 3) == 0) {
-            *reinterpret_cast<float4 *>(o + k) = make_float4(r4[0], r4[1], r4[2], r4[3]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (k + i < a.K) o[k + i] = r4[i];
-        }
-    }
-}
-
-// deterministic block sum (fixed shuffle tree per wave, waves in order); thread 0 gets it
-__device__ __forceinline__ float block_sum(float v) {
-    __shared__ float ws[kHB / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.0f;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < kHB / 64; ++w) s += ws[w];
-    return s;
+    write_dh_of<NOUT>(a.dh, a.W, a.dh_mask, a.K, row, l, dz);
 }
 
 // forward: one row per half-wave, the epilogue on its lane 0
@@ -489,19 +401,6 @@ __global__ void __launch_bounds__(kHB) k_colsum_finish(const float *part, int32_
     if (lane == 0) out[c] = s;
 }
 
-template <class F>
-hipError_t with_nout(int nout, F f) {
-    switch (nout) {
-        case 1: return f(std::integral_constant<int, 1>{});
-        case 2: return f(std::integral_constant<int, 2>{});
-        case 3: return f(std::integral_constant<int, 3>{});
-        case 4: return f(std::integral_constant<int, 4>{});
-        default: return hipErrorInvalidValue;
-    }
-}
-
-unsigned row_blocks(int32_t B) { return (unsigned)((B + kRowsPerBlock - 1) / kRowsPerBlock); }
-
 hipError_t wgrad(HeadArgs a, hipStream_t s) {
     if (!a.dW && !a.db) return hipSuccess;
     a.nblk = (a.B + kWRows - 1) / kWRows;
@@ -515,10 +414,6 @@ hipError_t wgrad(HeadArgs a, hipStream_t s) {
     hipLaunchKernelGGL(k_wgrad_finish, dim3((unsigned)((n + per - 1) / per)), dim3(kHB), 0, s, a);
     return hipGetLastError();
 }
-
-bool bad_shape(int32_t B, int32_t K, int32_t nout) { return B <= 0 || K <= 0 || K > kMaxK || nout <= 0 || nout > kMaxOut; }
-
-int fail_arg(const char *fn) { return f110_set_error(F110_E_INVALID, std::string(fn) + ": bad arguments"); }
 
 }  // namespace
 }  // namespace f110

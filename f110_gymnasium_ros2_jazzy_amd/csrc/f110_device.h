@@ -1404,6 +1404,43 @@ F110_HD float explore_one(int kind, float act, float n, double sigma, double the
     return (float)clip((double)act + x, (double)lo, (double)hi);
 }
 
+// ---------------------------------------------------------------- TD3 rows --
+// The two row rules of the TD3 learner (include/f110.h, "TD3 heads"; k_td3_target_action /
+// k_td3_critic_step and f110_host_td3_smooth_rows / f110_host_td3_rows call them).  f32, left to
+// right, no FMA.
+//
+// Target-policy smoothing of one output: act the target actor's action, n the N(0,1) draw,
+// scale_j the actor's half-range 0.5 * (high - low) of this output, so policy_noise and noise_clip
+// are in units of the tanh output (the action box is asymmetric: steer +-0.4189, speed 0..20).
+// NaN stays NaN.
+F110_HD float td3_smooth_one(float act, float n, float policy_noise, float noise_clip, float scale_j, float lo,
+                             float hi) {
+    const float s = policy_noise * scale_j;
+    const float c = noise_clip * scale_j;
+    float e = s * n;
+    e = e < -c ? -c : e;
+    e = e > c ? c : e;
+    float v = act + e;
+    v = v < lo ? lo : v;
+    v = v > hi ? hi : v;
+    return v;
+}
+
+// One row of the twin critic update: clipped double-Q target (torch.minimum of the two target
+// critics, NaN propagates), the two TD errors and their loss gradients (k_critic_step's operations,
+// gb = g / B), the PER priority and the row's loss term.
+F110_HD void td3_row(float r, float d, float gamma, float q1t, float q2t, float q1, float q2, float w, float gb,
+                     float &td1, float &td2, float &dq1, float &dq2, float &prio, float &wl) {
+    const float m = (q2t < q1t || q2t != q2t) ? q2t : q1t;
+    const float y = r + (gamma * (1.0f - d)) * m;
+    td1 = y - q1;
+    td2 = y - q2;
+    dq1 = -((gb * w) * (2.0f * td1));
+    dq2 = -((gb * w) * (2.0f * td2));
+    prio = 0.5f * (fabsf(td1) + fabsf(td2));
+    wl = w * (td1 * td1) + w * (td2 * td2);
+}
+
 // ------------------------------------------------------- n-step returns --
 // One env's push into its n-step window (the semantics of include/f110.h, "n-step returns";
 // k_nstep_update and f110_host_nstep both call it).  The window is a ring of n slots: its len

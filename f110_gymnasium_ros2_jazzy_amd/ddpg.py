@@ -19,6 +19,12 @@ all-reduced in a single collective (critic: 156 289 floats, actor: 156 162
 floats at obs_dim 1088), then the optimizer step.  The critic's all-reduce must finish before the actor's
 forward (the actor loss reads the updated critic), so the two buckets are two
 collectives.  Ranks start from rank 0's weights and stay identical.
+
+``algo="td3"`` (no reference counterpart) swaps the update rule for TD3: a
+``TwinCritic`` with the clipped double-Q target, target-policy smoothing, and
+the actor / target updates only on every ``policy_delay``-th update.  The twin
+is one flat buffer and one bucket, so the collectives per update stay two (one
+on an update that is no actor step).  The default ``algo="ddpg"`` is unchanged.
 """
 from __future__ import annotations
 
@@ -196,6 +202,20 @@ class Critic(nn.Module):
         return F.relu(self.fcs2(z))
 
 
+class TwinCritic(nn.Module):
+    """TD3's two critics as one module (one flat parameter buffer, one gradient
+    bucket, one optimizer): submodules c1, c2, each a Critic.  c1 / c2 may be
+    given (the learner builds them in its seed order)."""
+
+    def __init__(self, obs_dim: int, act_dim: int, c1: Critic | None = None, c2: Critic | None = None):
+        super().__init__()
+        self.c1 = c1 if c1 is not None else Critic(obs_dim, act_dim)
+        self.c2 = c2 if c2 is not None else Critic(obs_dim, act_dim)
+
+    def forward(self, obs: torch.Tensor, act: torch.Tensor):
+        return self.c1(obs, act), self.c2(obs, act)
+
+
 class GradBucket:
     """Gradient all-reduce of one network as ONE flat fp32 bucket.
 
@@ -324,8 +344,23 @@ class DDPGLearner:
                  seed: int = 42, device="cuda:0", replay="device", process_group=None, max_add: int | None = None,
                  check_finite: bool = False, path: str | None = None, graphs: bool = False,
                  noise_type: str = "gaussian", ou_theta: float = 0.15, ou_mu: float = 0.0, ou_dt: float = 1.0,
-                 n_step: int = 1):
+                 n_step: int = 1, algo: str = "ddpg", policy_delay: int = 2, policy_noise: float = 0.2,
+                 noise_clip: float = 0.5):
         self.device = torch.device(device)
+        # algo "td3": twin critics with the clipped double-Q target, target-policy smoothing and the
+        # actor / target updates every policy_delay-th update; the three TD3 arguments are checked
+        # and otherwise unused for "ddpg"
+        if algo not in ("ddpg", "td3"):
+            raise ValueError(f"algo must be 'ddpg' or 'td3'; got {algo!r}")
+        self.algo = algo
+        self.policy_delay = int(policy_delay)
+        self.policy_noise, self.noise_clip = float(policy_noise), float(noise_clip)
+        if self.policy_delay < 1 or self.policy_delay != policy_delay:
+            raise ValueError(f"policy_delay must be an integer >= 1; got {policy_delay!r}")
+        if not (math.isfinite(self.policy_noise) and math.isfinite(self.noise_clip)) or self.policy_noise < 0 \
+                or self.noise_clip < 0:
+            raise ValueError("policy_noise and noise_clip must be finite and >= 0")
+        self.td3 = algo == "td3"
         self.tuned_gemms = enable_tuned_gemms(self.device)
         self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
         self.action_low = np.asarray(action_low, dtype=np.float32)
@@ -343,6 +378,11 @@ class DDPGLearner:
         self.critic = Critic(self.obs_dim, self.act_dim)
         self.actor_target = Actor(self.obs_dim, self.act_dim, self.action_low, self.action_high)
         self.critic_target = Critic(self.obs_dim, self.act_dim)
+        if self.td3:  # after DDPG's four draws: the second critic, then its target (same seed: same actor and c1)
+            c2 = Critic(self.obs_dim, self.act_dim)
+            c2t = Critic(self.obs_dim, self.act_dim)
+            self.critic = TwinCritic(self.obs_dim, self.act_dim, self.critic, c2)
+            self.critic_target = TwinCritic(self.obs_dim, self.act_dim, self.critic_target, c2t)
         self.actor_target.load_state_dict(self.actor.state_dict())
         self.critic_target.load_state_dict(self.critic.state_dict())
         for net in (self.actor, self.critic, self.actor_target, self.critic_target):
@@ -365,7 +405,8 @@ class DDPGLearner:
         self.actor_grads = GradBucket(self.actor, self.group, always_pack=self.flat)
         self.critic_grads = GradBucket(self.critic, self.group, always_pack=self.flat)
         self.graphs = bool(graphs) and self.device.type == "cuda" and replay is not None
-        self._graphs, self._graph_out, self._eager_left = None, None, 3
+        # eager warm-up updates before any capture; TD3 needs both update kinds among them
+        self._graphs, self._graph_out, self._eager_left = None, None, max(3, self.policy_delay) if self.td3 else 3
         self._side = torch.cuda.Stream(self.device) if self.graphs else None
         if self.flat:
             self.actor_optim = FlatAdam(self.actor, self._flat["actor"], lr=actor_lr)
@@ -434,8 +475,20 @@ class DDPGLearner:
             raise ValueError("ou_theta, ou_mu and ou_dt must be finite and ou_dt >= 0")
         self.ou_x = torch.zeros(int(max_add or 0), self.act_dim, dtype=torch.float64, device=self.device) \
             if noise_type == "ou" else None  # (without max_add: the first training call's rows)
+        # TD3: the smoothing draws of the torch path (the explicit path draws on the device, keyed by
+        # _noise_key and the critic optimizer's step word) and the last actor step's loss
+        self._smooth_gen = None
+        if self.td3:
+            self._smooth_gen = torch.Generator(device=self.device)
+            self._smooth_gen.manual_seed((self._noise_key ^ 0x5444335F) & ((1 << 63) - 1))
+        self._last_actor_loss = None
         self._ready = False
         self.global_step = 0
+
+    def is_actor_step(self) -> bool:
+        """Whether the next update (0-based index global_step) also steps the actor and the
+        targets: every update for DDPG, every policy_delay-th for TD3."""
+        return not self.td3 or (self.global_step + 1) % self.policy_delay == 0
 
     # ------------------------------------------------------------------
     def remember(self, state, action, reward, next_state, done, mask=None):
@@ -460,7 +513,42 @@ class DDPGLearner:
 
     # The update is three phases split at the two gradient all-reduces, so a
     # HIP graph can hold each phase while the RCCL collectives stay eager.
-    def _phase_critic(self, states, actions, rewards, next_states, dones, weights):
+    def _td3_target(self, next_states, r, d, smooth_normals=None):
+        """TD3's target on the torch path: the smoothed target action (td3_smooth_one's rule), then
+        y = r + gamma (1 - d) min(q1t, q2t).  r, d: [M, 1]."""
+        with torch.no_grad():
+            a = self.actor_target(next_states)
+            n = smooth_normals if smooth_normals is not None else \
+                torch.randn(a.shape, generator=self._smooth_gen, device=self.device)
+            scale = 0.5 * (self._high32 - self._low32)
+            c = self.noise_clip * scale
+            e = torch.minimum(torch.maximum((self.policy_noise * scale) * n.to(a.dtype), -c), c)
+            a = torch.minimum(torch.maximum(a + e, self._low32), self._high32)
+            q1t, q2t = self.critic_target(next_states, a)
+            return r + self.gamma * (1.0 - d) * torch.minimum(q1t, q2t)
+
+    def _phase_critic_td3(self, states, actions, r, next_states, d, w, smooth_normals):
+        """The twin critic phase: loss mean(w td1^2) + mean(w td2^2); returns (loss, the PER
+        priority 0.5 (|td1| + |td2|) as [M, 1])."""
+        if smooth_normals is not None:
+            smooth_normals = torch.as_tensor(smooth_normals, device=self.device, dtype=torch.float32).contiguous()
+            if smooth_normals.shape != (states.shape[0], self.act_dim):
+                raise ValueError(f"smooth_normals must be [{states.shape[0]}, {self.act_dim}]; "
+                                 f"got {tuple(smooth_normals.shape)}")
+        if self.explicit is not None:
+            critic_loss, td = self.explicit.critic_td3(states, actions, r, next_states, d, w, smooth_normals)
+            self._finite("td", td)
+            return critic_loss, td
+        target_y = self._td3_target(next_states, r, d, smooth_normals)
+        self._finite("target_y", target_y)
+        self.critic_grads.zero()
+        q1, q2 = self.critic(states, actions)
+        td1, td2 = target_y - q1, target_y - q2
+        critic_loss = (w * td1 ** 2).mean() + (w * td2 ** 2).mean()
+        critic_loss.backward()
+        return critic_loss.detach(), (0.5 * (td1.abs() + td2.abs())).detach()
+
+    def _phase_critic(self, states, actions, rewards, next_states, dones, weights, smooth_normals=None):
         """agent.py:302-319: TD target, critic loss, critic backward."""
         r = rewards.reshape(-1, 1)
         d = dones.reshape(-1, 1)
@@ -468,6 +556,8 @@ class DDPGLearner:
         for name, t in (("states", states), ("actions", actions), ("next_states", next_states), ("rewards", r),
                         ("dones", d)):
             self._finite(name, t)
+        if self.td3:
+            return self._phase_critic_td3(states, actions, r, next_states, d, w, smooth_normals)
         if self.explicit is not None:  # learner_fused.py: the same graph without autograd
             critic_loss, td = self.explicit.critic(states, actions, r, next_states, d, w)
             self._finite("td", td)
@@ -504,16 +594,16 @@ class DDPGLearner:
     def _phase_actor(self, states):
         """agent.py:321-331: critic step, actor loss through the frozen critic."""
         self._optim_step(self.critic_optim, self.critic_grads, self._flat["critic_target"] if self.flat else None)
+        cr = self.critic.c1 if self.td3 else self.critic  # TD3's actor loss reads the first critic only
         if self.explicit is not None:
-            return self.explicit.actor(states)
+            return self.explicit.actor(states, cr=cr)
         for p in self.critic.parameters():
             p.requires_grad_(False)
         if _fused(states):
             from .ddpg_heads import q_mean
-            actor_loss = q_mean(self.critic.hidden(states, self.actor(states)), self.critic.q.weight,
-                                self.critic.q.bias, -1.0)
+            actor_loss = q_mean(cr.hidden(states, self.actor(states)), cr.q.weight, cr.q.bias, -1.0)
         else:
-            actor_loss = -self.critic(states, self.actor(states)).mean()
+            actor_loss = -cr(states, self.actor(states)).mean()
         self.actor_grads.zero()
         actor_loss.backward()
         for p in self.critic.parameters():
@@ -528,16 +618,32 @@ class DDPGLearner:
                 for tgt, src in zip(self._target, self._online):
                     tgt.lerp_(src, self.tau)
 
-    def update(self, states, actions, rewards, next_states, dones, weights) -> dict:
+    def _phase_critic_only(self):
+        """A TD3 update that is no actor step: the critics' optimizer step alone (no soft update)."""
+        self._optim_step(self.critic_optim, self.critic_grads, None)
+
+    def update(self, states, actions, rewards, next_states, dones, weights, smooth_normals=None) -> dict:
         """The learning part of replay() (agent.py:302-343) on one batch:
         critic step, actor step, soft target update.  Returns device tensors
-        (critic_loss, actor_loss, td [B])."""
+        (critic_loss, actor_loss, td [B]).  algo "td3": the twin critic step on
+        every update (td is then the PER priority 0.5 (|td1| + |td2|)); the
+        actor step and every soft target update only when is_actor_step(), else
+        actor_loss is the last actor step's (None before the first).
+        smooth_normals: [B, act_dim] float32 N(0, 1) draws for TD3's target
+        smoothing (None: the learner's own stream)."""
+        actor_step = self.is_actor_step()
         with TunedGemms(self.tuned_gemms):
-            critic_loss, td = self._phase_critic(states, actions, rewards, next_states, dones, weights)
+            critic_loss, td = self._phase_critic(states, actions, rewards, next_states, dones, weights,
+                                                 smooth_normals)
             self.critic_grads.all_reduce()
-            actor_loss = self._phase_actor(states)
-            self.actor_grads.all_reduce()
-            self._phase_finish()
+            if actor_step:
+                actor_loss = self._phase_actor(states)
+                self.actor_grads.all_reduce()
+                self._phase_finish()
+                self._last_actor_loss = actor_loss
+            else:
+                self._phase_critic_only()
+                actor_loss = self._last_actor_loss
         self.global_step += 1
         return {"critic_loss": critic_loss, "actor_loss": actor_loss, "td": td}
 
@@ -566,8 +672,11 @@ class DDPGLearner:
         self.memory.update_priorities(idxs, st["td"], td_errors=True, add_eps=self.priority_epsilon)
         return st
 
-    def _graph_phases(self):
-        """The replay() body as three callables split at the all-reduces."""
+    def _graph_phases(self, actor_step: bool = True):
+        """The replay() body as callables split at the all-reduces: three for an
+        update that is an actor step (every DDPG update), two for a TD3 update
+        that is not (the critic phase; then, after the critic bucket's reduce,
+        the critics' optimizer step without a target and the priority update)."""
         m = self.memory
         out = {}
 
@@ -586,39 +695,56 @@ class DDPGLearner:
             self.actor_grads.unpack()
             self._phase_finish()
             m.update_priorities(m.idx, out["td"], td_errors=True, add_eps=self.priority_epsilon)
-        return (a, b_, c), out
+
+        def c_only():
+            self.critic_grads.unpack()
+            self._phase_critic_only()
+            m.update_priorities(m.idx, out["td"], td_errors=True, add_eps=self.priority_epsilon)
+        return ((a, b_, c) if actor_step else (a, c_only)), out
+
+    def _run_phases(self, run):
+        """The phases of one update (run(k) runs or replays phase k) with the eager
+        bucket all-reduces (RCCL) between them."""
+        run[0]()
+        self.critic_grads.reduce()
+        run[1]()
+        if len(run) == 3:
+            self.actor_grads.reduce()
+            run[2]()
+
+    def _graphed_result(self, out, actor_step):
+        """An update's outputs; a TD3 update that is no actor step reports the last actor step's loss."""
+        if actor_step:
+            self._last_actor_loss = out["actor_loss"]
+            return out
+        return dict(out, actor_loss=self._last_actor_loss)
 
     def _replay_graphed(self):
         cur = torch.cuda.current_stream(self.device)
+        actor_step = self.is_actor_step()  # the host picks the capture set by global_step
+        if self._eager_left > 0:  # warm-up: real updates on a side stream (allocator, optimizer state)
+            phases, out = self._graph_phases(actor_step)
+            side = self._side
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                self._run_phases(phases)
+            cur.wait_stream(side)
+            self._eager_left -= 1
+            self.global_step += 1
+            return self._graphed_result(dict(out), actor_step)
         if self._graphs is None:
-            phases, out = self._graph_phases()
-            if self._eager_left > 0:  # warm-up: real updates on a side stream (allocator, optimizer state)
-                side = self._side
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    phases[0]()
-                    self.critic_grads.reduce()
-                    phases[1]()
-                    self.actor_grads.reduce()
-                    phases[2]()
-                cur.wait_stream(side)
-                self._eager_left -= 1
-                self.global_step += 1
-                return dict(out)
+            self._graphs, self._graph_out = {}, {}
+        if actor_step not in self._graphs:  # one capture set per update kind, each with its own pool
+            phases, out = self._graph_phases(actor_step)
             graphs = [torch.cuda.CUDAGraph() for _ in phases]
             pool = torch.cuda.graph_pool_handle()
             for g, ph in zip(graphs, phases):  # capture records, it does not run
                 with torch.cuda.graph(g, pool=pool, stream=self._side):
                     ph()
-            self._graphs, self._graph_out = graphs, out
-        g = self._graphs
-        g[0].replay()
-        self.critic_grads.reduce()  # eager RCCL between the captured phases
-        g[1].replay()
-        self.actor_grads.reduce()
-        g[2].replay()
+            self._graphs[actor_step], self._graph_out[actor_step] = graphs, out
+        self._run_phases([g.replay for g in self._graphs[actor_step]])
         self.global_step += 1
-        return self._graph_out
+        return self._graphed_result(self._graph_out[actor_step], actor_step)
 
     def _row_mask(self, m, n, what):
         """eval_mask / reset as a contiguous uint8 [n] device tensor (as it is when it already is one:
@@ -733,6 +859,9 @@ class DDPGLearner:
             "action_low": self.action_low.tolist(), "action_high": self.action_high.tolist(),
             "gamma": self.gamma, "tau": self.tau, "obs_dim": self.obs_dim, "act_dim": self.act_dim,
             "global_step": self.global_step, "torch_version": str(torch.__version__),  # (a plain str: load_model's weights_only loader)
+            # TD3 only (a DDPG file has none of these keys): "critic*" then hold the twin, keys c1.* / c2.*
+            **({"algo": self.algo, "policy_delay": self.policy_delay, "policy_noise": self.policy_noise,
+                "noise_clip": self.noise_clip} if self.td3 else {}),
         }, os.path.join(self.path, filename))
 
     def load_model(self, filename: str = "ddpg_checkpoint.pt") -> bool:
@@ -741,6 +870,9 @@ class DDPGLearner:
         if not os.path.exists(model_path):
             return False
         ckpt = torch.load(model_path, map_location=self.device, weights_only=True)
+        if ckpt.get("algo", "ddpg") != self.algo:  # (a file without the key is a DDPG checkpoint)
+            raise ValueError(f"{model_path} is a {ckpt.get('algo', 'ddpg')!r} checkpoint; this learner's algo is "
+                             f"{self.algo!r}")
         self.actor.load_state_dict(ckpt["actor"], strict=True)
         self.critic.load_state_dict(ckpt["critic"], strict=True)
         self.actor_target.load_state_dict(ckpt.get("actor_target", ckpt["actor"]), strict=False)

@@ -239,3 +239,80 @@ def host_explore_rows(act, normals, kind, ou_x, sigma, low, high, theta=0.15, mu
                                                   float(decay), float(sigma_min), P(low), P(high), P(out)),
                "f110_host_explore_rows")
     return out, (float(st_out[0]), float(st_out[1]))
+
+
+def td3_target_action(h, W, b, scale, shift, policy_noise, noise_clip, low, high, seed=0, counter=None,
+                      normals_ext=None):
+    """f110_td3_target_action (include/f110.h) on device tensors: the target actor's last layer with
+    target-policy smoothing, [B, nout] float32.  The draws are normals_ext ([B, nout] float32) when
+    given, else the device stream of (seed, counter[0]); counter is a device int64 tensor that is
+    only read.  No autograd."""
+    _check(h, W, b)
+    B, K = h.shape
+    n = W.shape[0]
+    if normals_ext is not None and (normals_ext.dtype != torch.float32 or tuple(normals_ext.shape) != (B, n)
+                                    or not normals_ext.is_contiguous() or not normals_ext.is_cuda):
+        raise _lib.F110Error(f"td3_target_action: normals_ext must be a contiguous device float32 tensor {(B, n)}")
+    if counter is not None and (counter.dtype != torch.int64 or not counter.is_cuda):
+        raise _lib.F110Error("td3_target_action: counter must be a device int64 tensor")
+    h, W = h.contiguous(), W.contiguous()
+    out = torch.empty(B, n, dtype=torch.float32, device=h.device)
+    _lib.check(_lib.load().f110_td3_target_action(
+        _p(h), _p(W), _p(b), _p(scale), _p(shift), B, K, n, float(policy_noise), float(noise_clip), _p(low),
+        _p(high), int(seed) & ((1 << 64) - 1), _p(counter), _p(normals_ext), _p(out), _stream(h)),
+        "f110_td3_target_action")
+    return out
+
+
+def td3_critic_step(ht1, Wt1, bt1, ht2, Wt2, bt2, r, d, gamma, h1, W1, b1, h2, W2, b2, w, g, dh_masks=(None, None),
+                    want_dh=True):
+    """f110_td3_critic_step (include/f110.h) on device tensors.  Returns a dict: td (the PER
+    priority, [B, 1]), dq1 / dq2 [B, 1], dh1 / dh2 [B, K] (want_dh; masked by dh_masks) and part
+    (the loss is part.sum() / B).  No autograd."""
+    for hh, WW, bb in ((ht1, Wt1, bt1), (ht2, Wt2, bt2), (h1, W1, b1), (h2, W2, b2)):
+        _check(hh, WW, bb)
+    L = _lib.load()
+    B, K = h1.shape
+    dev = h1.device
+    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+    out = {"td": e(B, 1), "dq1": e(B, 1), "dq2": e(B, 1), "dh1": e(B, K) if want_dh else None,
+           "dh2": e(B, K) if want_dh else None, "part": e(L.f110_ddpg_row_blocks(B))}
+    r, d, w = r.reshape(-1).contiguous(), d.reshape(-1).contiguous(), w.reshape(-1).contiguous()
+    _lib.check(L.f110_td3_critic_step(_p(ht1), _p(Wt1), _p(bt1), _p(ht2), _p(Wt2), _p(bt2), _p(r), _p(d),
+                                      float(gamma), _p(h1), _p(W1), _p(b1), _p(h2), _p(W2), _p(b2), _p(w), _p(g), B,
+                                      K, _p(out["td"]), _p(out["dh1"]), _p(dh_masks[0]), _p(out["dh2"]),
+                                      _p(dh_masks[1]), _p(out["dq1"]), _p(out["dq2"]), _p(out["part"]), _stream(h1)),
+               "f110_td3_critic_step")
+    return out
+
+
+def host_td3_smooth_rows(act, normals, policy_noise, noise_clip, scale, low, high):
+    """f110_host_td3_smooth_rows over NumPy arrays: f110_td3_target_action's per-row epilogue on the
+    CPU, on given actions act [n, nout] float32 and draws normals [n, nout] float32."""
+    act = np.ascontiguousarray(act, np.float32)
+    n, nout = act.shape
+    normals = np.ascontiguousarray(normals, np.float32)
+    scale, low, high = (np.ascontiguousarray(v, np.float32) for v in (scale, low, high))
+    if normals.shape != act.shape or any(v.shape != (nout,) for v in (scale, low, high)):
+        raise ValueError("host_td3_smooth_rows: normals must match act; scale / low / high must have nout entries")
+    out = np.empty_like(act)
+    P = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    _lib.check(_lib.load().f110_host_td3_smooth_rows(P(act), P(normals), n, nout, float(policy_noise),
+                                                     float(noise_clip), P(scale), P(low), P(high), P(out)),
+               "f110_host_td3_smooth_rows")
+    return out
+
+
+def host_td3_rows(r, d, gamma, q1t, q2t, q1, q2, w, g=1.0):
+    """f110_host_td3_rows over NumPy arrays ([B] float32 each): f110_td3_critic_step's row rule on
+    the CPU.  Returns a dict of td1, td2, dq1, dq2, prio, wl ([B] float32)."""
+    a = [np.ascontiguousarray(v, np.float32).reshape(-1) for v in (r, d, q1t, q2t, q1, q2, w)]
+    B = a[0].shape[0]
+    if any(v.shape != (B,) for v in a):
+        raise ValueError("host_td3_rows: every input must have B entries")
+    out = {k: np.empty(B, np.float32) for k in ("td1", "td2", "dq1", "dq2", "prio", "wl")}
+    P = lambda x: ctypes.c_void_p(x.ctypes.data)  # noqa: E731
+    _lib.check(_lib.load().f110_host_td3_rows(P(a[0]), P(a[1]), float(gamma), P(a[2]), P(a[3]), P(a[4]), P(a[5]),
+                                              P(a[6]), float(g), B, *(P(out[k]) for k in out)),
+               "f110_host_td3_rows")
+    return out

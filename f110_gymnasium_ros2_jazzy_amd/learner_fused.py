@@ -33,8 +33,9 @@ class ExplicitUpdate:
 
     @staticmethod
     def supported(ln) -> bool:
+        critics = (ln.critic.c1, ln.critic.c2) if ln.td3 else (ln.critic,)
         return ln.device.type == "cuda" and ln.act_dim <= 2 and ln.actor.fc1.out_features == ExplicitUpdate.H \
-            and ln.critic.fcs1.out_features == ExplicitUpdate.H
+            and all(c.fcs1.out_features == ExplicitUpdate.H for c in critics)
 
     def __init__(self, ln):
         self.ln = ln
@@ -111,11 +112,74 @@ class ExplicitUpdate:
                  loss=(part, 1.0, loss))
         return loss, td
 
-    def actor(self, s):
-        """agent.py:321-331 after the critic step: actor loss -mean(q) through
-        the updated critic, its gradients into the actor's bucket."""
+    def critic_td3(self, s, a, r, ns, d, w, normals=None):
+        """The TD3 critic phase: the smoothed target action, the clipped
+        double-Q target, both critics' losses and their gradients into the twin's
+        bucket (views named c1.* / c2.*).  normals: [M, act_dim] float32 N(0, 1)
+        draws for the smoothing, or None: the head draws them (keyed by the
+        learner's noise key and the critic optimizer's device step word, which
+        that optimizer's launch advances later in the same update).  Returns
+        (loss, the PER priority 0.5 (|td1| + |td2|) as [M, 1])."""
         ln, L, H = self.ln, self.L, self.H
-        ac, cr = ln.actor, ln.critic
+        at = ln.actor_target
+        c1t, c2t, c1, c2 = ln.critic_target.c1, ln.critic_target.c2, ln.critic.c1, ln.critic.c2
+        s, a, ns = s.contiguous(), a.contiguous(), ns.contiguous()
+        r, d, w = r.reshape(-1).contiguous(), d.reshape(-1).contiguous(), w.reshape(-1).contiguous()
+        M, D = s.shape
+        nA = a.shape[1]
+        dev = s.device
+        st = _stream(s)
+        h1t, z1t1, z1t2 = self._e(M), self._e(M), self._e(M)
+        lg.gemm([self._fwd(ns, at.fc1, h1t), self._fwd(ns, c1t.fcs1, z1t1), self._fwd(ns, c2t.fcs1, z1t2)], M, dev)
+        z11, z12 = self._e(M), self._e(M)
+        lg.gemm([self._fwd(s, c1.fcs1, z11), self._fwd(s, c2.fcs1, z12)], M, dev)
+        h2t, z21, z22 = self._e(M), self._e(M), self._e(M)
+        lg.gemm([self._fwd(h1t, at.fc2, h2t), self._fwd(z11, c1.fcs2, z21, x2=a),
+                 self._fwd(z12, c2.fcs2, z22, x2=a)], M, dev)
+        # the target actor's head with the smoothing noise and both clips in one launch
+        scale, shift = at._affine()
+        a_next = self._e(M, nA)
+        _lib.check(L.f110_td3_target_action(_p(h2t), _p(at.fc3.weight), _p(at.fc3.bias), _p(scale), _p(shift), M, H,
+                                            nA, ln.policy_noise, ln.noise_clip, _p(ln._low32), _p(ln._high32),
+                                            ln._noise_key, _p(ln.critic_optim.state), _p(normals), _p(a_next), st),
+                   "f110_td3_target_action")
+        z2t1, z2t2 = self._e(M), self._e(M)
+        lg.gemm([self._fwd(z1t1, c1t.fcs2, z2t1, x2=a_next), self._fwd(z1t2, c2t.fcs2, z2t2, x2=a_next)], M, dev)
+        # one launch: min of the target critics' heads, both TD errors, the loss partials, and each
+        # critic head's backward (dq_i, g2_i = dq_i Wq_i where z2_i > 0)
+        td = self._e(M, 1)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        part = torch.empty(L.f110_ddpg_row_blocks(M), dtype=torch.float32, device=dev)
+        dq1, dq2 = self._e(M, 1), self._e(M, 1)
+        g21, g22 = self._e(M), self._e(M)
+        _lib.check(L.f110_td3_critic_step(_p(z2t1), _p(c1t.q.weight), _p(c1t.q.bias), _p(z2t2), _p(c2t.q.weight),
+                                          _p(c2t.q.bias), _p(r), _p(d), ln.gamma, _p(z21), _p(c1.q.weight),
+                                          _p(c1.q.bias), _p(z22), _p(c2.q.weight), _p(c2.q.bias), _p(w),
+                                          _p(self.one), M, H, _p(td), _p(g21), _p(z21), _p(g22), _p(z22), _p(dq1),
+                                          _p(dq2), _p(part), st), "f110_td3_critic_step")
+        gc = self.gc
+        g11, g12 = self._e(M), self._e(M)  # d loss / d fcs1_i's pre-activation: g2_i Ws2_i[:, :H] where z1_i > 0
+        lg.gemm([lg.op(g2, c.fcs2.weight, g1, H, H, H, c.fcs2.weight.stride(0), H, omask=z1, nn=True)
+                 for c, g2, g1, z1 in ((c1, g21, g11, z11), (c2, g22, g12, z12))], M, dev)
+        # each critic's four weight gradients in one launch; the second one's finishing launch also
+        # writes the loss of both (the one part array)
+        for n, c, g2, g1, z1, z2, dq, last in (("c1.", c1, g21, g11, z11, z21, dq1, False),
+                                               ("c2.", c2, g22, g12, z12, z22, dq2, True)):
+            ld2 = c.fcs2.weight.stride(0)
+            lg.wgrad([lg.wop(g2, z1, gc[n + "fcs2.weight"], H, H, H, H, ld2, db=gc[n + "fcs2.bias"]),
+                      lg.wop(g2, a, (gc[n + "fcs2.weight"], H), H, nA, H, a.stride(0), ld2),
+                      lg.wop(g1, s, gc[n + "fcs1.weight"], H, D, H, s.stride(0), gc[n + "fcs1.weight"].stride(0),
+                             db=gc[n + "fcs1.bias"]),
+                      lg.wop(dq, z2, gc[n + "q.weight"], 1, H, 1, H, gc[n + "q.weight"].stride(0),
+                             db=gc[n + "q.bias"])], M, dev, loss=(part, 1.0, loss) if last else None)
+        return loss, td
+
+    def actor(self, s, cr=None):
+        """agent.py:321-331 after the critic step: actor loss -mean(q) through
+        the updated critic cr (None: the learner's critic; TD3 passes its first
+        critic), its gradients into the actor's bucket."""
+        ln, L, H = self.ln, self.L, self.H
+        ac, cr = ln.actor, ln.critic if cr is None else cr
         s = s.contiguous()
         M, D = s.shape
         dev = s.device

@@ -11,7 +11,8 @@ Per vector step, everything on the device:
   remember      (:184) every transition except the reset rows of autoreset steps;
                 with --n-step N as N-step returns (device windows in front of the ring)
   replay        (:187-188) `updates_per_step` learner updates after warm-up,
-                gradients averaged over ranks by RCCL
+                gradients averaged over ranks by RCCL; with --algo td3 the TD3 rule
+                (twin critics, target smoothing, delayed actor / target updates)
 
     python -m torch.distributed.run --nproc-per-node 8 -m f110_gymnasium_ros2_jazzy_amd.train --envs-per-gpu 4096
 """
@@ -43,7 +44,8 @@ class VectorTrainer:
                  memory_size: int = 1 << 20, warmup_steps: int = 1000, updates_per_step: int = 1, seed: int = 42,
                  device=None, env_offset: int = 0, rank_seed: int = 0, graphs: bool = True,
                  max_episode_steps: int | None = None, stall_speed: float = 0.0, stall_steps: int | None = None,
-                 noise_type: str = "gaussian", eval_envs: int = 0, ou_reset: bool = False, n_step: int = 1):
+                 noise_type: str = "gaussian", eval_envs: int = 0, ou_reset: bool = False, n_step: int = 1,
+                 algo: str = "ddpg", policy_delay: int = 2, policy_noise: float = 0.2, noise_clip: float = 0.5):
         from .ddpg import DDPGLearner
         from .maps import MAP_DIR
         from .reward import BatchedCenterlineReward, CenterlineTrack
@@ -79,15 +81,20 @@ class VectorTrainer:
                                  actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size,
                                  alpha=0.6, beta=0.4, priority_epsilon=1e-5, noise_sigma_start=0.20,
                                  noise_sigma_min=0.02, noise_decay=0.9995, seed=seed, device=self.device,
-                                 max_add=self.N, graphs=graphs, noise_type=noise_type, n_step=n_step)
+                                 max_add=self.N, graphs=graphs, noise_type=noise_type, n_step=n_step,
+                                 algo=algo, policy_delay=policy_delay, policy_noise=policy_noise,
+                                 noise_clip=noise_clip)
         self.warmup = int(warmup_steps)
         self.updates_per_step = int(updates_per_step)
         # HIP graphs per vector step once the learner's eager warm-up updates are done (explicit
         # learner, one update per step): even / odd steps have their own captures, which swap the two
         # fixed observation buffers and the learner's two noise-state slots; one graph per step on
-        # one rank, three (split at the gradient all-reduces) on several
+        # one rank, three (split at the gradient all-reduces) on several.  The captures are keyed by
+        # (parity, actor step): _sg[parity] holds a step whose update is an actor step (every DDPG
+        # update), _sg_critic[parity] a TD3 step whose update is not (two graphs on several ranks)
         self.step_graphs = bool(graphs) and os.environ.get("F110_STEP_GRAPH", "1") != "0"
         self._sg = [None, None]
+        self._sg_critic = [None, None]
         self._sg_parity = 0
         self._sg_obs = None
         self._gen = torch.Generator(device=self.device)
@@ -159,15 +166,16 @@ class VectorTrainer:
         phase_a()
         return rew, term
 
-    def _capture(self, p):
-        """The parity's step graphs: its own learner phases and loss outputs
+    def _capture(self, p, actor_step=True):
+        """The step graphs of one (parity, update kind): its own learner phases and loss outputs
         (ddpg._graph_phases per parity: the two captures share a memory pool,
         so one parity's outputs must not be the other's scratch).  One rank: the
         whole step is one graph.  Several ranks: three graphs split at the two
-        gradient-bucket all-reduces, which run eagerly (RCCL) between the replays."""
+        gradient-bucket all-reduces, which run eagerly (RCCL) between the replays (two graphs and
+        one all-reduce for a TD3 update that is no actor step)."""
         ag = self.agent
         bufs = self._sg_obs
-        phases, out = ag._graph_phases()
+        phases, out = ag._graph_phases(actor_step)
         ret = {}
 
         def head():
@@ -175,9 +183,9 @@ class VectorTrainer:
 
         def whole():
             head()
-            phases[1]()
-            phases[2]()
-        segs = [head, phases[1], phases[2]] if ag.distributed else [whole]
+            for ph in phases[1:]:
+                ph()
+        segs = [head, *phases[1:]] if ag.distributed else [whole]
         cur = torch.cuda.current_stream(self.device)
         graphs = []
         for seg in segs:  # capture records, it does not run
@@ -201,8 +209,10 @@ class VectorTrainer:
         bufs = self._sg_obs
         if self.obs.data_ptr() != bufs[p].data_ptr():
             bufs[p].copy_(self.obs)
-        if self._sg[p] is None:
-            self._sg[p] = self._capture(p)
+        actor_step = ag.is_actor_step()  # the host picks the capture by the learner's update index
+        sg = self._sg if actor_step else self._sg_critic
+        if sg[p] is None:
+            sg[p] = self._capture(p, actor_step)
         else:  # what the capture's Python side did once
             s = ag._noise_slot
             if ag._noise_dev != (ag.sigma, ag._noise_calls):  # the host changed sigma: the slot the graph reads
@@ -210,15 +220,16 @@ class VectorTrainer:
                 ag._noise_state[s, 1] = float(ag._noise_calls)
             ag.noise_advance()
             ag.memory._added += self.N
-        graphs, out, ret = self._sg[p]
+        graphs, out, ret = sg[p]
         graphs[0].replay()
         if len(graphs) > 1:  # several ranks: the bucket all-reduces between the learner's phases
             ag.critic_grads.reduce()
             graphs[1].replay()
+        if len(graphs) > 2:
             ag.actor_grads.reduce()
             graphs[2].replay()
         ag.global_step += 1
-        self.last = out
+        self.last = ag._graphed_result(out, actor_step)
         self.obs = bufs[1 - p]
         self._sg_parity ^= 1
         self.global_step += 1
@@ -276,6 +287,11 @@ def main():
     ap.add_argument("--eval-envs", type=int, default=0, help="noise-free evaluation envs per GPU (the last K)")
     ap.add_argument("--ou-reset", action="store_true", help="zero an env's OU state when its episode resets")
     ap.add_argument("--n-step", type=int, default=1, help="n-step returns in the replay (1: one-step targets)")
+    ap.add_argument("--algo", choices=("ddpg", "td3"), default="ddpg", help="the learner's update rule")
+    ap.add_argument("--policy-delay", type=int, default=2, help="td3: actor / target update every N-th update")
+    ap.add_argument("--policy-noise", type=float, default=0.2,
+                    help="td3: target smoothing noise, in units of the action half-range")
+    ap.add_argument("--noise-clip", type=float, default=0.5, help="td3: clip of the smoothing noise, same units")
     ap.add_argument("--save-dir", default=None, help="rank 0 saves best.pt here when eval_return_mean improves")
     args = ap.parse_args()
     rank, world, local = D.init()
@@ -285,7 +301,8 @@ def main():
                        updates_per_step=args.updates_per_step, seed=args.seed, env_offset=shard.offset,
                        rank_seed=rank, max_episode_steps=args.max_episode_steps, stall_speed=args.stall_speed,
                        stall_steps=args.stall_steps, noise_type=args.noise, eval_envs=args.eval_envs,
-                       ou_reset=args.ou_reset, n_step=args.n_step)
+                       ou_reset=args.ou_reset, n_step=args.n_step, algo=args.algo, policy_delay=args.policy_delay,
+                       policy_noise=args.policy_noise, noise_clip=args.noise_clip)
     best = -float("inf")
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)
@@ -301,7 +318,7 @@ def main():
                 tr.agent.save_model("best.pt")
             if rank == 0:
                 st = tr.last or {}
-                print(json.dumps({"step": k + 1,
+                print(json.dumps({"step": k + 1, "algo": args.algo,
                                   "env_steps_per_s": shard.count * world * (k + 1) / (time.perf_counter() - t0),
                                   "critic_loss": float(st["critic_loss"]) if st else None,
                                   "mean_return": float(ret.mean()), **ep}), flush=True)

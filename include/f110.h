@@ -660,6 +660,45 @@ F110_API int f110_ddpg_q_mean_bwd(const float *h, const float *W, const float *g
                                   float *dh, const float *dh_mask, float *dW, float *db, float *scratch,
                                   void *stream);
 
+/* ---- TD3 heads -------------------------------------------------------------------
+ * The two heads the TD3 update rule (clipped double-Q, target-policy smoothing) adds to the learner
+ * heads above; same buffers, shapes and limits (K <= 255, nout <= 4, B > 0), f32 left to right
+ * without FMA in the epilogues, deterministic, async on stream.
+ *
+ * f110_td3_target_action: the target actor's output layer with smoothing.  act = scale[j] *
+ * tanh(h W^T + b) + shift[j] is f110_ddpg_actor_head's value bit for bit; per row r, output j
+ *   s = policy_noise * scale[j];  c = noise_clip * scale[j];  e = clip(s * n, -c, c);
+ *   out[r][j] = clip(act + e, low[j], high[j])        (out: [B][nout], packed)
+ * so policy_noise and noise_clip are in units of the tanh output (scale = the actor's half-range
+ * 0.5 (high - low)).  The draw n is normals_ext[r * nout + j] when normals_ext ([B][nout] f32) is
+ * given, else f110_ddpg_actor_explore's Philox / Box-Muller draw for (seed ^ a fixed 64-bit tag,
+ * *counter, r, j): a stream of its own, never the exploration stream's for the same (seed, counter,
+ * row).  counter is a device int64 the launch only reads -- the learner passes the critic
+ * optimizer's step word (f110_adam_step's state), which that optimizer's launch advances later in
+ * the same update, so a replayed graph draws fresh noise per update and a resumed checkpoint
+ * continues the stream.  policy_noise = 0 gives clip(act, low, high).  NaN stays NaN.
+ * F110_E_INVALID before any device call for a null required pointer, a bad shape, a negative or
+ * non-finite policy_noise / noise_clip, or counter == NULL with normals_ext == NULL. */
+F110_API int f110_td3_target_action(const float *h, const float *W, const float *b, const float *scale,
+                                    const float *shift, int32_t B, int32_t K, int32_t nout, float policy_noise,
+                                    float noise_clip, const float *low, const float *high, uint64_t seed,
+                                    const int64_t *counter, const float *normals_ext, float *out, void *stream);
+/* f110_ddpg_critic_step for twin critics, in one launch.  Per row, with q1t = ht1 Wt1^T + bt1,
+ * q2t = ht2 Wt2^T + bt2 (the two target critics) and q_i = h_i W_i^T + b_i (ht_i, h_i: [B][K]):
+ *   m = min(q1t, q2t) (torch.minimum: NaN propagates);  y = r + (gamma (1 - d)) m;  td_i = y - q_i;
+ *   dq_i = -((g / B) w) (2 td_i)   (dq1 / dq2: [B], each may be null);
+ *   dh_i = dq_i W_i where dh_i_mask > 0   (dh_i may be null; its mask may be null);
+ *   td[r] = 0.5 (|td1| + |td2|), the PER priority (non-negative);
+ *   part[blk] = block sums of w td1^2 + w td2^2 (f110_ddpg_row_blocks(B) floats; the loss
+ *   mean(w td1^2) + mean(w td2^2) is sum(part) / B: f110_learner_wgrad_loss).
+ * F110_E_INVALID before any device call for a null required pointer or a bad shape. */
+F110_API int f110_td3_critic_step(const float *ht1, const float *Wt1, const float *bt1, const float *ht2,
+                                  const float *Wt2, const float *bt2, const float *r, const float *d, float gamma,
+                                  const float *h1, const float *W1, const float *b1, const float *h2,
+                                  const float *W2, const float *b2, const float *w, const float *g, int32_t B,
+                                  int32_t K, float *td, float *dh1, const float *dh1_mask, float *dh2,
+                                  const float *dh2_mask, float *dq1, float *dq2, float *part, void *stream);
+
 /* ---- learner GEMMs (fp32 matrix cores) -------------------------------------------
  * The hidden layers of the DDPG networks (agent.py:25-97: fc1 / fc2, fcs1 /
  * fcs2 and replay()'s backward through them, :302-331), forward and backward,

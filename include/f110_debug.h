@@ -281,6 +281,21 @@ F110_API int f110_host_explore_rows(const float *act, const float *normals, int6
                                     double *state_out, double decay, double sigma_min, const float *low,
                                     const float *high, float *out);
 
+/* The TD3 heads' row rules over HOST arrays: the same functions the kernels run (td3_smooth_one,
+ * td3_row, csrc/f110_device.h).  f110_host_td3_smooth_rows: f110_td3_target_action's epilogue on
+ * given actions act and draws normals ([n_rows][nout] f32), scale / low / high [nout]; writes out
+ * [n_rows][nout].  f110_host_td3_rows: f110_td3_critic_step's row rule on given head outputs q1t,
+ * q2t, q1, q2 and r, d, w ([B] f32), g the loss gradient (a host scalar; gb = g / B); writes td1,
+ * td2, dq1, dq2, prio (the kernel's td) and wl (the row's loss term), each [B].  Same validation
+ * (F110_E_INVALID).  Host test hooks: the CPU suite and the GPU tests share one statement of the
+ * semantics. */
+F110_API int f110_host_td3_smooth_rows(const float *act, const float *normals, int64_t n_rows, int32_t nout,
+                                       float policy_noise, float noise_clip, const float *scale, const float *low,
+                                       const float *high, float *out);
+F110_API int f110_host_td3_rows(const float *r, const float *d, float gamma, const float *q1t, const float *q2t,
+                                const float *q1, const float *q2, const float *w, float g, int64_t B, float *td1,
+                                float *td2, float *dq1, float *dq2, float *prio, float *wl);
+
 /* One f110_nstep_push over HOST arrays: the same per-env function the kernel runs (nstep_update,
  * csrc/f110_device.h), envs in ascending order.  len / head [n_envs], ret / k [n_envs][n_step],
  * win_obs [n_envs][n_step][obs_dim] and win_act [n_envs][n_step][act_dim] are the windows
