@@ -383,6 +383,9 @@ class DDPGLearner:
             c2t = Critic(self.obs_dim, self.act_dim)
             self.critic = TwinCritic(self.obs_dim, self.act_dim, self.critic, c2)
             self.critic_target = TwinCritic(self.obs_dim, self.act_dim, self.critic_target, c2t)
+        # (online, target, prefix of its parameter names in self.critic); the actor loss reads the first
+        self.critics = [(self.critic.c1, self.critic_target.c1, "c1."), (c2, c2t, "c2.")] if self.td3 else \
+            [(self.critic, self.critic_target, "")]
         self.actor_target.load_state_dict(self.actor.state_dict())
         self.critic_target.load_state_dict(self.critic.state_dict())
         for net in (self.actor, self.critic, self.actor_target, self.critic_target):
@@ -530,15 +533,6 @@ class DDPGLearner:
     def _phase_critic_td3(self, states, actions, r, next_states, d, w, smooth_normals):
         """The twin critic phase: loss mean(w td1^2) + mean(w td2^2); returns (loss, the PER
         priority 0.5 (|td1| + |td2|) as [M, 1])."""
-        if smooth_normals is not None:
-            smooth_normals = torch.as_tensor(smooth_normals, device=self.device, dtype=torch.float32).contiguous()
-            if smooth_normals.shape != (states.shape[0], self.act_dim):
-                raise ValueError(f"smooth_normals must be [{states.shape[0]}, {self.act_dim}]; "
-                                 f"got {tuple(smooth_normals.shape)}")
-        if self.explicit is not None:
-            critic_loss, td = self.explicit.critic_td3(states, actions, r, next_states, d, w, smooth_normals)
-            self._finite("td", td)
-            return critic_loss, td
         target_y = self._td3_target(next_states, r, d, smooth_normals)
         self._finite("target_y", target_y)
         self.critic_grads.zero()
@@ -556,12 +550,17 @@ class DDPGLearner:
         for name, t in (("states", states), ("actions", actions), ("next_states", next_states), ("rewards", r),
                         ("dones", d)):
             self._finite(name, t)
-        if self.td3:
-            return self._phase_critic_td3(states, actions, r, next_states, d, w, smooth_normals)
-        if self.explicit is not None:  # learner_fused.py: the same graph without autograd
-            critic_loss, td = self.explicit.critic(states, actions, r, next_states, d, w)
+        if self.td3 and smooth_normals is not None:
+            smooth_normals = torch.as_tensor(smooth_normals, device=self.device, dtype=torch.float32).contiguous()
+            if smooth_normals.shape != (states.shape[0], self.act_dim):
+                raise ValueError(f"smooth_normals must be [{states.shape[0]}, {self.act_dim}]; "
+                                 f"got {tuple(smooth_normals.shape)}")
+        if self.explicit is not None:  # learner_fused.py: the same graph without autograd, either algo
+            critic_loss, td = self.explicit.critic(states, actions, r, next_states, d, w, smooth_normals)
             self._finite("td", td)
             return critic_loss, td
+        if self.td3:
+            return self._phase_critic_td3(states, actions, r, next_states, d, w, smooth_normals)
         fused = _fused(states)
         with torch.no_grad():  # :302-308
             a_next = self.actor_target(next_states)
@@ -594,7 +593,7 @@ class DDPGLearner:
     def _phase_actor(self, states):
         """agent.py:321-331: critic step, actor loss through the frozen critic."""
         self._optim_step(self.critic_optim, self.critic_grads, self._flat["critic_target"] if self.flat else None)
-        cr = self.critic.c1 if self.td3 else self.critic  # TD3's actor loss reads the first critic only
+        cr = self.critics[0][0]  # TD3's actor loss reads the first critic only
         if self.explicit is not None:
             return self.explicit.actor(states, cr=cr)
         for p in self.critic.parameters():
@@ -618,9 +617,56 @@ class DDPGLearner:
                 for tgt, src in zip(self._target, self._online):
                     tgt.lerp_(src, self.tau)
 
-    def _phase_critic_only(self):
-        """A TD3 update that is no actor step: the critics' optimizer step alone (no soft update)."""
-        self._optim_step(self.critic_optim, self.critic_grads, None)
+    def _phases(self, actor_step: bool = True, batch=None):
+        """One update as callables split at the all-reduces (the only definition of an update:
+        update(), replay() and every graph capture run these), and the dict they fill.  Three for an
+        update that is an actor step (every DDPG update), two for a TD3 update that is not (the
+        critic phase; then, after the critic bucket's reduce, the critics' optimizer step without a
+        soft update).  batch: update()'s seven arguments; None: the first phase samples
+        self.memory and the last one writes the priorities back."""
+        m, out = self.memory, {}
+
+        def critic():
+            b = batch
+            if b is None:
+                _, g, w = m.sample(beta=self.beta)
+                b = (g["states"], g["actions"], g["rewards"], g["next_states"], g["dones"], w)
+            out["critic_loss"], out["td"] = self._phase_critic(*b)
+            self.critic_grads.pack()
+
+        def actor():
+            self.critic_grads.unpack()
+            out["actor_loss"] = self._phase_actor(m.batch["states"] if batch is None else batch[0])
+            self.actor_grads.pack()
+
+        def finish():
+            if actor_step:
+                self.actor_grads.unpack()
+                self._phase_finish()
+            else:
+                self.critic_grads.unpack()
+                self._optim_step(self.critic_optim, self.critic_grads, None)
+            if batch is None:
+                m.update_priorities(m.idx, out["td"], td_errors=True, add_eps=self.priority_epsilon)
+        return ((critic, actor, finish) if actor_step else (critic, finish)), out
+
+    def _run_phases(self, run):
+        """The phases of one update (run[k]() runs or replays phase k), each after the eager
+        all-reduce (RCCL) of the bucket the phase before it filled.  One entry is a whole update in
+        one piece (a single rank's captured step): nothing to reduce."""
+        for phase, bucket in zip(run, (None, self.critic_grads, self.actor_grads)):
+            if bucket is not None:
+                bucket.reduce()
+            phase()
+
+    def _update_result(self, out, actor_step):
+        """Counts the update that filled ``out`` and returns its outputs; a TD3 update that is no
+        actor step reports the last actor step's loss."""
+        self.global_step += 1
+        if actor_step:
+            self._last_actor_loss = out["actor_loss"]
+            return out
+        return dict(out, actor_loss=self._last_actor_loss)
 
     def update(self, states, actions, rewards, next_states, dones, weights, smooth_normals=None) -> dict:
         """The learning part of replay() (agent.py:302-343) on one batch:
@@ -632,20 +678,11 @@ class DDPGLearner:
         smooth_normals: [B, act_dim] float32 N(0, 1) draws for TD3's target
         smoothing (None: the learner's own stream)."""
         actor_step = self.is_actor_step()
+        phases, out = self._phases(actor_step, (states, actions, rewards, next_states, dones, weights,
+                                                smooth_normals))
         with TunedGemms(self.tuned_gemms):
-            critic_loss, td = self._phase_critic(states, actions, rewards, next_states, dones, weights,
-                                                 smooth_normals)
-            self.critic_grads.all_reduce()
-            if actor_step:
-                actor_loss = self._phase_actor(states)
-                self.actor_grads.all_reduce()
-                self._phase_finish()
-                self._last_actor_loss = actor_loss
-            else:
-                self._phase_critic_only()
-                actor_loss = self._last_actor_loss
-        self.global_step += 1
-        return {"critic_loss": critic_loss, "actor_loss": actor_loss, "td": td}
+            self._run_phases(phases)
+        return self._update_result(out, actor_step)
 
     @staticmethod
     def td_priorities(td: torch.Tensor, priority_epsilon: float) -> torch.Tensor:
@@ -667,75 +704,26 @@ class DDPGLearner:
             return self._replay_eager()
 
     def _replay_eager(self):
-        idxs, b, w = self.memory.sample(beta=self.beta)
-        st = self.update(b["states"], b["actions"], b["rewards"], b["next_states"], b["dones"], w)
-        self.memory.update_priorities(idxs, st["td"], td_errors=True, add_eps=self.priority_epsilon)
-        return st
-
-    def _graph_phases(self, actor_step: bool = True):
-        """The replay() body as callables split at the all-reduces: three for an
-        update that is an actor step (every DDPG update), two for a TD3 update
-        that is not (the critic phase; then, after the critic bucket's reduce,
-        the critics' optimizer step without a target and the priority update)."""
-        m = self.memory
-        out = {}
-
-        def a():
-            idxs, b, w = m.sample(beta=self.beta)
-            out["critic_loss"], out["td"] = self._phase_critic(b["states"], b["actions"], b["rewards"],
-                                                               b["next_states"], b["dones"], w)
-            self.critic_grads.pack()
-
-        def b_():
-            self.critic_grads.unpack()
-            out["actor_loss"] = self._phase_actor(m.batch["states"])
-            self.actor_grads.pack()
-
-        def c():
-            self.actor_grads.unpack()
-            self._phase_finish()
-            m.update_priorities(m.idx, out["td"], td_errors=True, add_eps=self.priority_epsilon)
-
-        def c_only():
-            self.critic_grads.unpack()
-            self._phase_critic_only()
-            m.update_priorities(m.idx, out["td"], td_errors=True, add_eps=self.priority_epsilon)
-        return ((a, b_, c) if actor_step else (a, c_only)), out
-
-    def _run_phases(self, run):
-        """The phases of one update (run(k) runs or replays phase k) with the eager
-        bucket all-reduces (RCCL) between them."""
-        run[0]()
-        self.critic_grads.reduce()
-        run[1]()
-        if len(run) == 3:
-            self.actor_grads.reduce()
-            run[2]()
-
-    def _graphed_result(self, out, actor_step):
-        """An update's outputs; a TD3 update that is no actor step reports the last actor step's loss."""
-        if actor_step:
-            self._last_actor_loss = out["actor_loss"]
-            return out
-        return dict(out, actor_loss=self._last_actor_loss)
+        actor_step = self.is_actor_step()
+        phases, out = self._phases(actor_step)
+        self._run_phases(phases)
+        return self._update_result(out, actor_step)
 
     def _replay_graphed(self):
         cur = torch.cuda.current_stream(self.device)
-        actor_step = self.is_actor_step()  # the host picks the capture set by global_step
         if self._eager_left > 0:  # warm-up: real updates on a side stream (allocator, optimizer state)
-            phases, out = self._graph_phases(actor_step)
             side = self._side
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                self._run_phases(phases)
+                st = self._replay_eager()
             cur.wait_stream(side)
             self._eager_left -= 1
-            self.global_step += 1
-            return self._graphed_result(dict(out), actor_step)
+            return st
+        actor_step = self.is_actor_step()  # the host picks the capture set by global_step
         if self._graphs is None:
             self._graphs, self._graph_out = {}, {}
         if actor_step not in self._graphs:  # one capture set per update kind, each with its own pool
-            phases, out = self._graph_phases(actor_step)
+            phases, out = self._phases(actor_step)
             graphs = [torch.cuda.CUDAGraph() for _ in phases]
             pool = torch.cuda.graph_pool_handle()
             for g, ph in zip(graphs, phases):  # capture records, it does not run
@@ -743,8 +731,7 @@ class DDPGLearner:
                     ph()
             self._graphs[actor_step], self._graph_out[actor_step] = graphs, out
         self._run_phases([g.replay for g in self._graphs[actor_step]])
-        self.global_step += 1
-        return self._graphed_result(self._graph_out[actor_step], actor_step)
+        return self._update_result(self._graph_out[actor_step], actor_step)
 
     def _row_mask(self, m, n, what):
         """eval_mask / reset as a contiguous uint8 [n] device tensor (as it is when it already is one:
@@ -790,10 +777,7 @@ class DDPGLearner:
                 eval_mask = self._row_mask(eval_mask, N, "eval_mask")
                 reset = self._row_mask(reset, N, "reset")
             if self.explicit is not None and training and o.dim() == 2:
-                s = self._noise_slot
-                if self._noise_dev != (self.sigma, self._noise_calls):  # the host changed sigma: upload it
-                    self._noise_state[s, 0] = self.sigma
-                    self._noise_state[s, 1] = float(self._noise_calls)
+                s = self._noise_upload()
                 rows = None
                 if per_row:  # f110_ddpg_actor_explore_env; Gaussian without masks stays on f110_ddpg_actor_explore
                     ou = self.noise_type == "ou"
@@ -834,6 +818,22 @@ class DDPGLearner:
             out.copy_(a)
             return out
         return a
+
+    def _noise_upload(self) -> int:
+        """The slot the next explicit training call reads, holding the host's (sigma, call index):
+        uploaded if the host changed them since the device wrote the slot."""
+        s = self._noise_slot
+        if self._noise_dev != (self.sigma, self._noise_calls):
+            self._noise_state[s, 0] = self.sigma
+            self._noise_state[s, 1] = float(self._noise_calls)
+        return s
+
+    def step_graph_replay(self, n_rows: int):
+        """The host side of a captured trainer step (one explicit training choose_action and one
+        remember_env of n_rows rows), which a capture runs once; call it before each later replay."""
+        self._noise_upload()
+        self.noise_advance()
+        self.memory.note_added(n_rows)
 
     def noise_advance(self):
         """The host mirror of one explicit training choose_action: the device

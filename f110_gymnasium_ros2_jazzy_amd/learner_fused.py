@@ -33,9 +33,8 @@ class ExplicitUpdate:
 
     @staticmethod
     def supported(ln) -> bool:
-        critics = (ln.critic.c1, ln.critic.c2) if ln.td3 else (ln.critic,)
         return ln.device.type == "cuda" and ln.act_dim <= 2 and ln.actor.fc1.out_features == ExplicitUpdate.H \
-            and all(c.fcs1.out_features == ExplicitUpdate.H for c in critics)
+            and all(c.fcs1.out_features == ExplicitUpdate.H for c, _, _ in ln.critics)
 
     def __init__(self, ln):
         self.ln = ln
@@ -69,109 +68,76 @@ class ExplicitUpdate:
                                                _stream(h)), "f110_ddpg_actor_head")
         return act, t
 
-    def critic(self, s, a, r, ns, d, w):
-        """agent.py:302-319: TD target, critic loss, its gradients into the
-        critic's bucket.  Returns (loss, td [M, 1])."""
+    def critic(self, s, a, r, ns, d, w, normals=None):
+        """agent.py:302-319 for every critic of the learner (ln.critics): TD target,
+        critic loss, the gradients into the critic bucket's views.  Returns
+        (loss, td [M, 1]).  TD3: the smoothed target action, the clipped double-Q
+        target and the sum of both critics' losses; td is then the PER priority
+        0.5 (|td1| + |td2|).  normals: [M, act_dim] float32 N(0, 1) draws for the
+        smoothing, or None: the head draws them (keyed by the learner's noise key
+        and the critic optimizer's device step word, which that optimizer's
+        launch advances later in the same update)."""
         ln, L, H = self.ln, self.L, self.H
-        at, ct, cr = ln.actor_target, ln.critic_target, ln.critic
-        s, a, ns = s.contiguous(), a.contiguous(), ns.contiguous()
-        r, d, w = r.reshape(-1).contiguous(), d.reshape(-1).contiguous(), w.reshape(-1).contiguous()
-        M, D = s.shape
-        nA = a.shape[1]
-        dev = s.device
-        h1t, z1t, z1 = self._e(M), self._e(M), self._e(M)
-        lg.gemm([self._fwd(ns, at.fc1, h1t), self._fwd(ns, ct.fcs1, z1t), self._fwd(s, cr.fcs1, z1)], M, dev)
-        h2t, z2 = self._e(M), self._e(M)
-        lg.gemm([self._fwd(h1t, at.fc2, h2t), self._fwd(z1, cr.fcs2, z2, x2=a)], M, dev)
-        a_next, _ = self._actor_head(at, h2t)
-        z2t = self._e(M)
-        lg.gemm([self._fwd(z1t, ct.fcs2, z2t, x2=a_next)], M, dev)
-        # one launch: TD target (critic_target's head), td / w td^2 partials (critic's head) and the
-        # head's backward: dq and g2 = dq Wq where z2 > 0 (d loss / d fcs2's pre-activation)
-        td = self._e(M, 1)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        part = torch.empty(L.f110_ddpg_row_blocks(M), dtype=torch.float32, device=dev)
-        dq = self._e(M, 1)
-        g2 = self._e(M)
-        _lib.check(L.f110_ddpg_critic_step(_p(z2t), _p(ct.q.weight), _p(ct.q.bias), _p(r), _p(d), ln.gamma,
-                                           _p(z2), _p(cr.q.weight), _p(cr.q.bias), _p(w), _p(self.one), M, H,
-                                           _p(td), _p(g2), _p(z2), _p(dq), _p(part), _stream(s)),
-                   "f110_ddpg_critic_step")
-        gc = self.gc
-        Ws2 = cr.fcs2.weight
-        ld2 = Ws2.stride(0)
-        g1 = self._e(M)  # d loss / d fcs1's pre-activation: g2 Ws2[:, :H] where z1 > 0
-        lg.gemm([lg.op(g2, Ws2, g1, H, H, H, ld2, H, omask=z1, nn=True)], M, dev)
-        # the four weight gradients (q, fcs2 and its action columns, fcs1) in one launch; its
-        # finishing launch also writes the loss
-        lg.wgrad([lg.wop(g2, z1, gc["fcs2.weight"], H, H, H, H, ld2, db=gc["fcs2.bias"]),
-                  lg.wop(g2, a, (gc["fcs2.weight"], H), H, nA, H, a.stride(0), ld2),
-                  lg.wop(g1, s, gc["fcs1.weight"], H, D, H, s.stride(0), gc["fcs1.weight"].stride(0),
-                         db=gc["fcs1.bias"]),
-                  lg.wop(dq, z2, gc["q.weight"], 1, H, 1, H, gc["q.weight"].stride(0), db=gc["q.bias"])], M, dev,
-                 loss=(part, 1.0, loss))
-        return loss, td
-
-    def critic_td3(self, s, a, r, ns, d, w, normals=None):
-        """The TD3 critic phase: the smoothed target action, the clipped
-        double-Q target, both critics' losses and their gradients into the twin's
-        bucket (views named c1.* / c2.*).  normals: [M, act_dim] float32 N(0, 1)
-        draws for the smoothing, or None: the head draws them (keyed by the
-        learner's noise key and the critic optimizer's device step word, which
-        that optimizer's launch advances later in the same update).  Returns
-        (loss, the PER priority 0.5 (|td1| + |td2|) as [M, 1])."""
-        ln, L, H = self.ln, self.L, self.H
-        at = ln.actor_target
-        c1t, c2t, c1, c2 = ln.critic_target.c1, ln.critic_target.c2, ln.critic.c1, ln.critic.c2
+        at, cs = ln.actor_target, ln.critics
+        online, target = [c for c, _, _ in cs], [t for _, t, _ in cs]
         s, a, ns = s.contiguous(), a.contiguous(), ns.contiguous()
         r, d, w = r.reshape(-1).contiguous(), d.reshape(-1).contiguous(), w.reshape(-1).contiguous()
         M, D = s.shape
         nA = a.shape[1]
         dev = s.device
         st = _stream(s)
-        h1t, z1t1, z1t2 = self._e(M), self._e(M), self._e(M)
-        lg.gemm([self._fwd(ns, at.fc1, h1t), self._fwd(ns, c1t.fcs1, z1t1), self._fwd(ns, c2t.fcs1, z1t2)], M, dev)
-        z11, z12 = self._e(M), self._e(M)
-        lg.gemm([self._fwd(s, c1.fcs1, z11), self._fwd(s, c2.fcs1, z12)], M, dev)
-        h2t, z21, z22 = self._e(M), self._e(M), self._e(M)
-        lg.gemm([self._fwd(h1t, at.fc2, h2t), self._fwd(z11, c1.fcs2, z21, x2=a),
-                 self._fwd(z12, c2.fcs2, z22, x2=a)], M, dev)
-        # the target actor's head with the smoothing noise and both clips in one launch
-        scale, shift = at._affine()
-        a_next = self._e(M, nA)
-        _lib.check(L.f110_td3_target_action(_p(h2t), _p(at.fc3.weight), _p(at.fc3.bias), _p(scale), _p(shift), M, H,
-                                            nA, ln.policy_noise, ln.noise_clip, _p(ln._low32), _p(ln._high32),
-                                            ln._noise_key, _p(ln.critic_optim.state), _p(normals), _p(a_next), st),
-                   "f110_td3_target_action")
-        z2t1, z2t2 = self._e(M), self._e(M)
-        lg.gemm([self._fwd(z1t1, c1t.fcs2, z2t1, x2=a_next), self._fwd(z1t2, c2t.fcs2, z2t2, x2=a_next)], M, dev)
-        # one launch: min of the target critics' heads, both TD errors, the loss partials, and each
-        # critic head's backward (dq_i, g2_i = dq_i Wq_i where z2_i > 0)
+        es = lambda: [self._e(M) for _ in cs]  # noqa: E731  (one [M, H] per critic)
+        # the first layers that read next_states, then the ones that read states: one launch when
+        # its four ops hold them all
+        h1t, z1t, z1 = self._e(M), es(), es()
+        on_ns = [self._fwd(ns, at.fc1, h1t)] + [self._fwd(ns, t.fcs1, y) for t, y in zip(target, z1t)]
+        on_s = [self._fwd(s, c.fcs1, y) for c, y in zip(online, z1)]
+        for ops in ([on_ns + on_s] if len(on_ns) + len(on_s) <= 4 else [on_ns, on_s]):
+            lg.gemm(ops, M, dev)
+        h2t, z2 = self._e(M), es()
+        lg.gemm([self._fwd(h1t, at.fc2, h2t)] + [self._fwd(x, c.fcs2, y, x2=a) for c, x, y in zip(online, z1, z2)],
+                M, dev)
+        if ln.td3:  # the target actor's head with the smoothing noise and both clips in one launch
+            scale, shift = at._affine()
+            a_next = self._e(M, nA)
+            _lib.check(L.f110_td3_target_action(_p(h2t), _p(at.fc3.weight), _p(at.fc3.bias), _p(scale), _p(shift), M,
+                                                H, nA, ln.policy_noise, ln.noise_clip, _p(ln._low32), _p(ln._high32),
+                                                ln._noise_key, _p(ln.critic_optim.state), _p(normals), _p(a_next),
+                                                st), "f110_td3_target_action")
+        else:
+            a_next, _ = self._actor_head(at, h2t)
+        z2t = es()
+        lg.gemm([self._fwd(x, t.fcs2, y, x2=a_next) for t, x, y in zip(target, z1t, z2t)], M, dev)
+        # one launch: the TD target (the target critics' heads, TD3: their minimum), td / w td^2
+        # partials (the critics' heads) and each head's backward: dq and g2 = dq Wq where z2 > 0
+        # (d loss / d fcs2's pre-activation)
         td = self._e(M, 1)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         part = torch.empty(L.f110_ddpg_row_blocks(M), dtype=torch.float32, device=dev)
-        dq1, dq2 = self._e(M, 1), self._e(M, 1)
-        g21, g22 = self._e(M), self._e(M)
-        _lib.check(L.f110_td3_critic_step(_p(z2t1), _p(c1t.q.weight), _p(c1t.q.bias), _p(z2t2), _p(c2t.q.weight),
-                                          _p(c2t.q.bias), _p(r), _p(d), ln.gamma, _p(z21), _p(c1.q.weight),
-                                          _p(c1.q.bias), _p(z22), _p(c2.q.weight), _p(c2.q.bias), _p(w),
-                                          _p(self.one), M, H, _p(td), _p(g21), _p(z21), _p(g22), _p(z22), _p(dq1),
-                                          _p(dq2), _p(part), st), "f110_td3_critic_step")
+        dq = [self._e(M, 1) for _ in cs]
+        g2 = es()
+        step, name = (L.f110_td3_critic_step, "f110_td3_critic_step") if ln.td3 else \
+            (L.f110_ddpg_critic_step, "f110_ddpg_critic_step")
+        # per q head its (input, weight, bias); per critic (g2, its mask z2: the head reads z2 as both)
+        q_t = [_p(x) for t, h in zip(target, z2t) for x in (h, t.q.weight, t.q.bias)]
+        q_o = [_p(x) for c, h in zip(online, z2) for x in (h, c.q.weight, c.q.bias)]
+        dh = [_p(x) for g, z in zip(g2, z2) for x in (g, z)]
+        _lib.check(step(*q_t, _p(r), _p(d), ln.gamma, *q_o, _p(w), _p(self.one), M, H, _p(td), *dh,
+                        *[_p(x) for x in dq], _p(part), st), name)
         gc = self.gc
-        g11, g12 = self._e(M), self._e(M)  # d loss / d fcs1_i's pre-activation: g2_i Ws2_i[:, :H] where z1_i > 0
-        lg.gemm([lg.op(g2, c.fcs2.weight, g1, H, H, H, c.fcs2.weight.stride(0), H, omask=z1, nn=True)
-                 for c, g2, g1, z1 in ((c1, g21, g11, z11), (c2, g22, g12, z12))], M, dev)
-        # each critic's four weight gradients in one launch; the second one's finishing launch also
-        # writes the loss of both (the one part array)
-        for n, c, g2, g1, z1, z2, dq, last in (("c1.", c1, g21, g11, z11, z21, dq1, False),
-                                               ("c2.", c2, g22, g12, z12, z22, dq2, True)):
+        g1 = es()  # d loss / d fcs1's pre-activation: g2 Ws2[:, :H] where z1 > 0
+        lg.gemm([lg.op(g, c.fcs2.weight, y, H, H, H, c.fcs2.weight.stride(0), H, omask=z, nn=True)
+                 for c, g, y, z in zip(online, g2, g1, z1)], M, dev)
+        # each critic's four weight gradients (fcs2 and its action columns, fcs1, q) in one launch; the
+        # last one's finishing launch also writes the loss (the one part array)
+        for i, (c, _, n) in enumerate(cs):
             ld2 = c.fcs2.weight.stride(0)
-            lg.wgrad([lg.wop(g2, z1, gc[n + "fcs2.weight"], H, H, H, H, ld2, db=gc[n + "fcs2.bias"]),
-                      lg.wop(g2, a, (gc[n + "fcs2.weight"], H), H, nA, H, a.stride(0), ld2),
-                      lg.wop(g1, s, gc[n + "fcs1.weight"], H, D, H, s.stride(0), gc[n + "fcs1.weight"].stride(0),
+            lg.wgrad([lg.wop(g2[i], z1[i], gc[n + "fcs2.weight"], H, H, H, H, ld2, db=gc[n + "fcs2.bias"]),
+                      lg.wop(g2[i], a, (gc[n + "fcs2.weight"], H), H, nA, H, a.stride(0), ld2),
+                      lg.wop(g1[i], s, gc[n + "fcs1.weight"], H, D, H, s.stride(0), gc[n + "fcs1.weight"].stride(0),
                              db=gc[n + "fcs1.bias"]),
-                      lg.wop(dq, z2, gc[n + "q.weight"], 1, H, 1, H, gc[n + "q.weight"].stride(0),
-                             db=gc[n + "q.bias"])], M, dev, loss=(part, 1.0, loss) if last else None)
+                      lg.wop(dq[i], z2[i], gc[n + "q.weight"], 1, H, 1, H, gc[n + "q.weight"].stride(0),
+                             db=gc[n + "q.bias"])], M, dev, loss=(part, 1.0, loss) if i == len(cs) - 1 else None)
         return loss, td
 
     def actor(self, s, cr=None):

@@ -109,6 +109,11 @@ class DeviceReplayBuffer:
                 self._stream()), "f110_replay_add")
         self._added += n
 
+    def note_added(self, n: int):
+        """A captured add / add_env of n rows was replayed (or rows reached the ring some other way
+        than through these methods): the host's bound on len() follows."""
+        self._added += int(n)
+
     def add_env(self, states, actions, rewards, next_states, terminated, was_reset):
         """add() of a vector env's raw step outputs (f110_replay_add_env): rewards
         float64, terminated / was_reset uint8 device tensors as the simulator
@@ -253,7 +258,7 @@ class NStepAccumulator:
         _lib.check(self.L.f110_nstep_push(self.handle, memory.handle, _p(s), s.stride(0), _p(a), a.stride(0), _p(r),
                                           _p(ns), ns.stride(0), _p(d), _p(t), _p(m), self._stream()),
                    "f110_nstep_push")
-        memory._added += n  # an upper bound: emitted rows never outnumber pushed rows in total
+        memory.note_added(n)  # an upper bound: emitted rows never outnumber pushed rows in total
 
     def reset(self, env_mask=None):
         """Drop the windows of the envs with env_mask != 0 (None: all); nothing is emitted."""

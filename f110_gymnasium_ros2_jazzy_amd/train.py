@@ -90,11 +90,10 @@ class VectorTrainer:
         # learner, one update per step): even / odd steps have their own captures, which swap the two
         # fixed observation buffers and the learner's two noise-state slots; one graph per step on
         # one rank, three (split at the gradient all-reduces) on several.  The captures are keyed by
-        # (parity, actor step): _sg[parity] holds a step whose update is an actor step (every DDPG
-        # update), _sg_critic[parity] a TD3 step whose update is not (two graphs on several ranks)
+        # (parity, actor step): every DDPG update is an actor step; a delayed-actor update that is
+        # none has two graphs on several ranks
         self.step_graphs = bool(graphs) and os.environ.get("F110_STEP_GRAPH", "1") != "0"
-        self._sg = [None, None]
-        self._sg_critic = [None, None]
+        self._sg = {}
         self._sg_parity = 0
         self._sg_obs = None
         self._gen = torch.Generator(device=self.device)
@@ -168,14 +167,14 @@ class VectorTrainer:
 
     def _capture(self, p, actor_step=True):
         """The step graphs of one (parity, update kind): its own learner phases and loss outputs
-        (ddpg._graph_phases per parity: the two captures share a memory pool,
+        (ddpg._phases per parity: the two captures share a memory pool,
         so one parity's outputs must not be the other's scratch).  One rank: the
         whole step is one graph.  Several ranks: three graphs split at the two
         gradient-bucket all-reduces, which run eagerly (RCCL) between the replays (two graphs and
-        one all-reduce for a TD3 update that is no actor step)."""
+        one all-reduce for an update that is no actor step)."""
         ag = self.agent
         bufs = self._sg_obs
-        phases, out = ag._graph_phases(actor_step)
+        phases, out = ag._phases(actor_step)
         ret = {}
 
         def head():
@@ -200,7 +199,7 @@ class VectorTrainer:
     def _step_graphed(self):
         """step() as replays of the parity's captured graphs (captured on its
         first use: the capture runs the Python side once, which is this step's
-        host bookkeeping; later replays repeat that bookkeeping here)."""
+        host bookkeeping; before later replays the learner repeats it)."""
         ag = self.agent
         p = self._sg_parity
         if self._sg_obs is None:
@@ -210,26 +209,13 @@ class VectorTrainer:
         if self.obs.data_ptr() != bufs[p].data_ptr():
             bufs[p].copy_(self.obs)
         actor_step = ag.is_actor_step()  # the host picks the capture by the learner's update index
-        sg = self._sg if actor_step else self._sg_critic
-        if sg[p] is None:
-            sg[p] = self._capture(p, actor_step)
-        else:  # what the capture's Python side did once
-            s = ag._noise_slot
-            if ag._noise_dev != (ag.sigma, ag._noise_calls):  # the host changed sigma: the slot the graph reads
-                ag._noise_state[s, 0] = ag.sigma
-                ag._noise_state[s, 1] = float(ag._noise_calls)
-            ag.noise_advance()
-            ag.memory._added += self.N
-        graphs, out, ret = sg[p]
-        graphs[0].replay()
-        if len(graphs) > 1:  # several ranks: the bucket all-reduces between the learner's phases
-            ag.critic_grads.reduce()
-            graphs[1].replay()
-        if len(graphs) > 2:
-            ag.actor_grads.reduce()
-            graphs[2].replay()
-        ag.global_step += 1
-        self.last = ag._graphed_result(out, actor_step)
+        if (p, actor_step) not in self._sg:
+            self._sg[p, actor_step] = self._capture(p, actor_step)
+        else:
+            ag.step_graph_replay(self.N)
+        graphs, out, ret = self._sg[p, actor_step]
+        ag._run_phases([g.replay for g in graphs])  # several ranks: with the bucket all-reduces between
+        self.last = ag._update_result(out, actor_step)
         self.obs = bufs[1 - p]
         self._sg_parity ^= 1
         self.global_step += 1

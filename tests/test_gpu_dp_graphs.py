@@ -48,11 +48,11 @@ def _worker(rank, world, port, q):
                     losses.append((float(tr.last["critic_loss"]), float(tr.last["actor_loss"])))
             T.cuda.synchronize()
             ag = tr.agent
-            graphed = tr._sg[0] is not None and tr._sg[1] is not None
+            graphed = (0, True) in tr._sg and (1, True) in tr._sg
             params = np.concatenate([p.detach().reshape(-1).cpu().numpy() for p in
                                      list(ag.actor.parameters()) + list(ag.critic.parameters())])
             out[flag] = dict(graphed=graphed, params=params, losses=losses, sigma=ag.sigma, calls=ag._noise_calls,
-                             n=len(ag.memory), ngraphs=len(tr._sg[0][0]) if graphed else 0)
+                             n=len(ag.memory), ngraphs=len(tr._sg[(0, True)][0]) if graphed else 0)
             tr.close()
         q.put((rank, out))
         D.shutdown()

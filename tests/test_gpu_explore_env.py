@@ -298,7 +298,7 @@ def test_trainer_eval_rows_and_graphs_match_eager(gpu, monkeypatch):
                 if k >= 3:
                     assert not bool((got[:56] == want[:56]).all(1).any()), f"training rows, step {k}"
             torch.cuda.synchronize()
-            assert (tr._sg[0] is not None and tr._sg[1] is not None) == (flag == "1")
+            assert ((0, True) in tr._sg and (1, True) in tr._sg) == (flag == "1")
             assert bool((ag.ou_x[56:] == 0).all()) and bool((ag.ou_x[:56] != 0).all())
             params = [p.detach().clone() for p in list(ag.actor.parameters()) + list(ag.critic.parameters())]
             n = len(ag.memory)
@@ -348,7 +348,7 @@ def test_trainer_eval_statistics_and_ou_reset(gpu, monkeypatch):
                 assert not bool((ag.ou_x[rest] == want[rest]).any())
                 checked += len(rows)
             assert bool((ag.ou_x[56:] == 0).all())
-        assert checked >= 56 and tr._sg[0] is not None and tr._sg[1] is not None
+        assert checked >= 56 and (0, True) in tr._sg and (1, True) in tr._sg
         rep = episode_report(tr)
         assert rep["eval_episodes"] > 0 and rep["episodes"] > 0
         assert rep["episodes"] == fin[:56].sum() and rep["eval_episodes"] == fin[56:].sum()

@@ -288,7 +288,7 @@ def test_trainer_graphs_match_eager(gpu, monkeypatch):
                 trunc += int((tr.env.truncated != 0).sum())
             assert trunc > 0
             if tr.agent.explicit is not None:
-                assert (tr._sg[0] is not None and tr._sg[1] is not None) == (flag == "1")
+                assert ((0, True) in tr._sg and (1, True) in tr._sg) == (flag == "1")
             runs.append(_trainer_state(tr))
         finally:
             tr.agent.nstep.close()
@@ -330,7 +330,7 @@ def test_trainer_default_is_add_env(gpu, monkeypatch):
         assert ag.n_step == 1 and ag.nstep is None
         for _ in range(5):  # 2 warm-up steps and the learner's 3 eager updates: every call goes through Python
             tr.step()
-        assert calls == [6] * 5 and ag._graphs is None and tr._sg == [None, None]
+        assert calls == [6] * 5 and ag._graphs is None and tr._sg == {}
         torch.cuda.synchronize()
         ln, _ = _buffers_equal(mem, twin, "default trainer")
         assert 40 <= ln <= 80  # 5 x 16 rows less the reset rows

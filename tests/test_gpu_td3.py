@@ -143,8 +143,8 @@ def _bucket_close(x, y):
 
 @pytest.mark.parametrize("M,D", [(333, 64), (64, 12)])
 def test_explicit_td3_matches_autograd(gpu, monkeypatch, M, D):
-    """ExplicitUpdate.critic_td3 / actor(cr=c1) against the autograd TD3 learner on the same weights,
-    batch and smoothing draws, policy_delay 2, three updates (critic-only, actor step, critic-only):
+    """ExplicitUpdate.critic with twin critics / actor(cr=c1) against the autograd TD3 learner on the same
+    weights, batch and smoothing draws, policy_delay 2, three updates (critic-only, actor step, critic-only):
     test_explicit_update_matches_autograd's tolerances."""
     import f110_gymnasium_ros2_jazzy_amd.ddpg as Dd
     batch, N = _data(M, D, M + D)
@@ -248,7 +248,7 @@ def test_td3_trainer_step_graphs_match_eager(gpu, monkeypatch):
         tr.step()
         torch.cuda.synchronize()
         # updates 0-2 are the eager warm-up; then step parity and update kind alternate together
-        captured = [x is not None for x in tr._sg + tr._sg_critic]
+        captured = [k in tr._sg for k in ((0, True), (1, True), (0, False), (1, False))]  # (parity, actor step)
         assert captured == ([True, False, False, True] if flag == "1" else [False] * 4)
         ag = tr.agent
         params = [p.detach().clone() for p in list(ag.actor.parameters()) + list(ag.critic.parameters()) +

@@ -49,7 +49,8 @@ def _worker(rank, world, port, q):
             params = np.concatenate([p.detach().reshape(-1).cpu().numpy() for p in
                                      list(ag.actor.parameters()) + list(ag.critic.parameters()) +
                                      list(ag.critic_target.parameters())])
-            ngraphs = [len(x[0]) if x is not None else 0 for x in tr._sg + tr._sg_critic]
+            ngraphs = [len(tr._sg[k][0]) if k in tr._sg else 0  # (parity, actor step)
+                       for k in ((0, True), (1, True), (0, False), (1, False))]
             out[flag] = dict(ngraphs=ngraphs, params=params, losses=losses, sigma=ag.sigma, calls=ag._noise_calls,
                              n=len(ag.memory), updates=ag.global_step, actor_steps=int(ag.actor_optim.state[0]))
             tr.close()

@@ -371,3 +371,25 @@ def test_checkpoint_round_trip(batches, tmp_path):
         other.load_model("ddpg.pt")
     with pytest.raises(ValueError, match="td3"):
         dd.load_model("td3.pt")
+
+
+@pytest.mark.parametrize("algo,want", [("ddpg", [["critic", "actor"]] * 4),
+                                       ("td3", [["critic"], ["critic", "actor"]] * 2)])
+def test_update_schedule_runs_through_the_phase_runner(batches, algo, want):
+    """update() is the learner's phases under _run_phases: the critic bucket is reduced in every
+    update, the actor bucket only in an actor step (every DDPG update, every second TD3 update with
+    policy_delay 2), critic first.  A one-entry phase list is a whole update: nothing is reduced."""
+    bs, normals = batches
+    ln = _learner(algo, policy_delay=2)
+    calls = []
+    ln.critic_grads.reduce = lambda: calls.append("critic")
+    ln.actor_grads.reduce = lambda: calls.append("actor")
+    got = []
+    for _ in range(4):
+        del calls[:]
+        ln.update(*bs[0], smooth_normals=normals[0])
+        got.append(list(calls))
+    assert got == want and ln.global_step == 4
+    del calls[:]
+    ln._run_phases([lambda: calls.append("whole")])
+    assert calls == ["whole"]
