@@ -85,9 +85,10 @@ __global__ void __launch_bounds__(kHB) k_head_fwd(HeadArgs a) {
             if (MODE == kActor) {  // tanh, then 0.5*(high-low) * t + 0.5*(high+low) (agent.py:60-61)
 #pragma unroll
                 for (int j = 0; j < NOUT; ++j) {
-                    const float t = tanhf(z[j]);
+                    float t;
+                    const float act = actor_action(z[j], a.aux0[j], a.aux1[j], t);
                     a.out1[row * NOUT + j] = t;
-                    a.out0[row * NOUT + j] = a.aux0[j] * t + a.aux1[j];
+                    a.out0[row * NOUT + j] = act;
                 }
             } else if (MODE == kExplore) {  // the action, + sigma N(0,1), clipped to [low, high] (NaN kept)
                 const float sigma = (float)a.nstate_in[0];

@@ -1376,6 +1376,18 @@ F110_HD void episode_totals_add(f110_episode_totals &t, const EpisodePart &b) {
     t.return_max = a.mx;
 }
 
+// ------------------------------------------------------------- obs scan entry --
+// F110Env._pack_flat_obs's scan entry (f110_env.py:557-560) from the float32 range: NaN -> lidar_max,
+// +-inf -> lidar_max / 0, clip to [0, lidar_max], one IEEE f32 divide by lidar_max.  The step's
+// packers (obs_scan_value(double, .), f110_step_device.h), f110_agent_obs and f110_host_agent_obs
+// all call it.
+F110_HD float obs_scan_value(float v, float lmax) {
+    if (v != v) v = lmax;
+    else if (__builtin_isinf(v)) v = v > 0 ? lmax : 0.0f;
+    v = v < 0.0f ? 0.0f : (v > lmax ? lmax : v);
+    return v / lmax;
+}
+
 // ---------------------------------------------------- exploration head rows --
 // One output of one row of f110_ddpg_actor_explore_env (include/f110.h; k_head_fwd's kExploreEnv
 // epilogue and f110_host_explore_rows both call it): act the deterministic action, n the N(0,1) draw,

@@ -1,5 +1,5 @@
-// f110_head_rows.h — what the learner-head translation units share (private; f110_ddpg.hip and
-// f110_td3.hip): the launch geometry of the row-per-half-wave kernels, the row dot product and
+// f110_head_rows.h — what the learner-head translation units share (private; f110_ddpg.hip,
+// f110_td3.hip and f110_selfplay.hip): the launch geometry of the row-per-half-wave kernels, the row dot product and
 // its backward, the deterministic sums, the exploration draw and the argument checks.  Everything
 // sits in an anonymous namespace: each translation unit gets its own copy, inlined into its kernels.
 #pragma once
@@ -70,6 +70,13 @@ __device__ __forceinline__ void row_dot_of(const float *h, const float *W, const
     }
 #pragma unroll
     for (int j = 0; j < NOUT; ++j) z[j] = half_sum(z[j]) + b[j];  // addmm: bias added to the product
+}
+
+// Actor.forward's last line (agent.py:56-61) on one head output z: t = tanh(z), the action
+// 0.5*(high-low) * t + 0.5*(high+low) with scale / shift those two constants of the output
+__device__ __forceinline__ float actor_action(float z, float scale, float shift, float &t) {
+    t = tanhf(z);
+    return scale * t + shift;
 }
 
 // dh[row] = dz W (lane l: columns 4l..4l+3, +128 ...), zero where dh_mask <= 0 (dh_mask may be null)

@@ -727,3 +727,23 @@ extern "C" int f110_host_nstep(int64_t n_envs, int32_t n_step, double gamma, int
     *out_count = row;
     return F110_OK;
 }
+
+// ---- self-play: the flat observation from an agent's seat ---------------------
+extern "C" int f110_host_agent_obs(const float *scans, int64_t scan_env_stride, const float *obs, int64_t obs_stride,
+                                   int64_t n_envs, int32_t n_agents, int32_t n_beams, int32_t agent, float lidar_max,
+                                   float *out, int64_t out_stride) {
+    if (agent_obs_bad_args(scans, scan_env_stride, obs, obs_stride, n_envs, n_agents, n_beams, agent, out, out_stride))
+        return fail(F110_E_INVALID, "f110_host_agent_obs: bad arguments");
+    const int64_t B = n_beams;
+    for (int64_t e = 0; e < n_envs; ++e) {
+        const float *s = scans + e * scan_env_stride + agent * B;
+        const float *p = obs + e * obs_stride + B;
+        float *o = out + e * out_stride;
+        for (int64_t b = 0; b < B; ++b) o[b] = obs_scan_value(s[b], lidar_max);
+        for (int g = 0; g < n_agents; ++g) {  // the seat's own pose group first, then the others ascending
+            const int src = g == 0 ? agent : (g <= agent ? g - 1 : g);
+            std::copy(p + 4 * src, p + 4 * src + 4, o + B + 4 * g);
+        }
+    }
+    return F110_OK;
+}

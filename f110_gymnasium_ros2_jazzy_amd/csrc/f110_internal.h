@@ -105,6 +105,16 @@ inline float obs_reciprocal(float lmax) {
     return 1.0f / l;
 }
 
+// f110_agent_obs / f110_host_agent_obs: the argument errors both report as F110_E_INVALID
+inline bool agent_obs_bad_args(const float *scans, int64_t scan_env_stride, const float *obs, int64_t obs_stride,
+                               int64_t n_envs, int32_t n_agents, int32_t n_beams, int32_t agent, const float *out,
+                               int64_t out_stride) {
+    if (!scans || !obs || !out || n_envs <= 0 || n_agents <= 0 || n_beams <= 0 || agent < 0 || agent >= n_agents)
+        return true;
+    const int64_t row = (int64_t)n_beams + 4 * (int64_t)n_agents;
+    return scan_env_stride < (int64_t)n_agents * n_beams || obs_stride < row || out_stride < row;
+}
+
 // k_rays_tiled's own argument block: only what the ray loop and its epilogue
 // read (the full StepArgs kept 90 SGPRs live: 7 instead of 8 blocks per CU).
 // One (car, opponent) pair's agent ray_cast geometry (RaceCar.ray_cast_agents,

@@ -38,14 +38,8 @@ __host__ __device__ __forceinline__ int64_t obs_row(const StepArgs &a) {
 }
 
 // F110Env._pack_flat_obs's scan entry (f110_env.py:557-560): f32, NaN ->
-// lidar_max, +-inf -> lidar_max / 0, clip, / lidar_max in f32.
-__device__ __forceinline__ float obs_scan_value(double r, float lmax) {
-    float v = (float)r;
-    if (v != v) v = lmax;
-    else if (isinf(v)) v = v > 0 ? lmax : 0.0f;
-    v = v < 0.0f ? 0.0f : (v > lmax ? lmax : v);
-    return v / lmax;
-}
+// lidar_max, +-inf -> lidar_max / 0, clip, / lidar_max in f32 (the f32 part: f110_device.h).
+__device__ __forceinline__ float obs_scan_value(double r, float lmax) { return obs_scan_value((float)r, lmax); }
 
 // check_ttc_jit's per-beam test (laser_models.py:188-217):
 //   ttc = (range - side) / proj_vel;  hit = ttc < thresh && ttc >= 0.

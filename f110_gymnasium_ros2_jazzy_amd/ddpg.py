@@ -849,8 +849,9 @@ class DDPGLearner:
         self.critic_target.load_state_dict(self.critic.state_dict())
 
     # ---------------------------------------------------------- checkpoint --
-    def save_model(self, filename: str = "ddpg_checkpoint.pt"):
-        """agent.py:384-405 (same keys)."""
+    def save_model(self, filename: str = "ddpg_checkpoint.pt", extra: dict | None = None):
+        """agent.py:384-405 (same keys).  extra: further entries a trainer stores beside them
+        (load_model reads its own keys and ignores the rest)."""
         os.makedirs(self.path, exist_ok=True)
         torch.save({
             "actor": self.actor.state_dict(), "critic": self.critic.state_dict(),
@@ -862,6 +863,7 @@ class DDPGLearner:
             # TD3 only (a DDPG file has none of these keys): "critic*" then hold the twin, keys c1.* / c2.*
             **({"algo": self.algo, "policy_delay": self.policy_delay, "policy_noise": self.policy_noise,
                 "noise_clip": self.noise_clip} if self.td3 else {}),
+            **(extra or {}),
         }, os.path.join(self.path, filename))
 
     def load_model(self, filename: str = "ddpg_checkpoint.pt") -> bool:

@@ -32,9 +32,26 @@ class ExplicitUpdate:
     H = 128  # hidden width of both networks (agent.py:35-37, :72-74)
 
     @staticmethod
+    def actor_supported(actor, device) -> bool:
+        """Whether actor_hidden and the head launches take this actor on this device."""
+        return torch.device(device).type == "cuda" and actor.fc3.out_features <= 2 \
+            and actor.fc1.out_features == ExplicitUpdate.H
+
+    @staticmethod
     def supported(ln) -> bool:
-        return ln.device.type == "cuda" and ln.act_dim <= 2 and ln.actor.fc1.out_features == ExplicitUpdate.H \
+        return ln.act_dim <= 2 and ExplicitUpdate.actor_supported(ln.actor, ln.device) \
             and all(c.fcs1.out_features == ExplicitUpdate.H for c, _, _ in ln.critics)
+
+    @staticmethod
+    def actor_hidden(actor, obs):
+        """relu(fc2(relu(fc1(obs)))) of an Actor on the learner GEMMs, one launch per layer: what
+        policy() runs before its head launch; needs no learner (opponent.PolicyOpponent runs the same)."""
+        M = obs.shape[0]
+        h1 = torch.empty(M, ExplicitUpdate.H, dtype=torch.float32, device=obs.device)
+        h2 = torch.empty_like(h1)
+        lg.gemm([ExplicitUpdate._fwd(obs, actor.fc1, h1)], M, obs.device)
+        lg.gemm([ExplicitUpdate._fwd(h1, actor.fc2, h2)], M, obs.device)
+        return h2
 
     def __init__(self, ln):
         self.ln = ln
@@ -199,9 +216,7 @@ class ExplicitUpdate:
         (reset, eval_mask: u8 [M] or None)."""
         obs = obs.contiguous()
         M = obs.shape[0]
-        h1, h2 = self._e(M), self._e(M)
-        lg.gemm([self._fwd(obs, actor.fc1, h1)], M, obs.device)
-        lg.gemm([self._fwd(h1, actor.fc2, h2)], M, obs.device)
+        h2 = self.actor_hidden(actor, obs)
         if explore is None:
             return self._actor_head(actor, h2)[0]
         st_in, st_out, decay, sigma_min, low, high, seed, out = explore

@@ -1,15 +1,23 @@
-"""Rule-based opponent on the device: gap_follow_action
-(rl_training/utils/gap_follow.py:3-58) for a batch of float32 scans through
-libf110's f110_gap_follow, bit-exact with the reference's NumPy float32
-arithmetic.  train_ddpg.py:168 computes it on the host from the previous
-step's info["scans"][1]; F110VectorEnv(opponent="gap_follow") keeps that loop
-on the GPU.
+"""Opponents on the device.
+
+Rule-based: gap_follow_action (rl_training/utils/gap_follow.py:3-58) for a
+batch of float32 scans through libf110's f110_gap_follow, bit-exact with the
+reference's NumPy float32 arithmetic.  train_ddpg.py:168 computes it on the
+host from the previous step's info["scans"][1];
+F110VectorEnv(opponent="gap_follow") keeps that loop on the GPU.
+
+Self-play (no reference counterpart): ``agent_obs`` packs the flat observation
+from any agent's seat (f110_agent_obs), ``PolicyOpponent`` holds a frozen copy
+of an Actor and writes its actions into the opponent's rows of the env's action
+buffer (the learner GEMMs, then f110_policy_head_rows), and ``selfplay_mask``
+is the fixed per-env rule that splits the envs between the two opponents.
 """
 from __future__ import annotations
 
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -40,3 +48,168 @@ def gap_follow(scans: torch.Tensor, out: torch.Tensor | None = None, angle_min: 
                                  ctypes.c_void_p(gaps.data_ptr()) if gaps is not None else None,
                                  ctypes.c_void_p(s)), "f110_gap_follow")
     return (out, gaps) if return_gaps else out
+
+
+# ---------------------------------------------------------------- self-play --
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def agent_obs(scans: torch.Tensor, obs: torch.Tensor, agent: int, lidar_max: float, out: torch.Tensor | None = None):
+    """The flat observation as agent ``agent`` sees it (f110_agent_obs): its scan
+    normalised as the step normalises the ego's, its pose group, then the other
+    agents' pose groups in ascending index.  scans: float32 device tensor
+    [E, A, B] (``sim.out.scans``); obs: the step's float32 obs [E, >= B + 4A]
+    (rows may be strided; only the pose block is read); out: float32
+    [E, >= B + 4A] (rows may be strided; a new packed tensor if None), which is
+    returned.  agent == the step's ego reproduces obs[:, :B + 4A] bit for bit."""
+    if scans.dim() != 3 or scans.dtype != torch.float32 or scans.device.type != "cuda" or not scans.is_contiguous():
+        raise ValueError("scans must be a contiguous float32 cuda tensor [E, A, B]")
+    E, A, B = scans.shape
+    W = B + 4 * A
+    if out is None:
+        out = torch.empty(E, W, dtype=torch.float32, device=scans.device)
+    for name, t in (("obs", obs), ("out", out)):
+        if (t.dim() != 2 or t.dtype != torch.float32 or t.device != scans.device or t.shape[0] != E or t.shape[1] < W
+                or t.stride(1) != 1 or (E > 1 and t.stride(0) < W)):
+            raise ValueError(f"{name} must be a float32 [E, >= B + 4A] tensor on the scans' device, unit column stride")
+    if not 0 <= int(agent) < A:
+        raise ValueError(f"agent must be in [0, {A}); got {agent}")
+    s = torch.cuda.current_stream(scans.device).cuda_stream
+    _lib.check(_lib.load().f110_agent_obs(_vp(scans), A * B, _vp(obs), obs.stride(0) if E > 1 else obs.shape[1], E, A,
+                                          B, int(agent), float(lidar_max), _vp(out),
+                                          out.stride(0) if E > 1 else out.shape[1], ctypes.c_void_p(s)),
+               "f110_agent_obs")
+    return out
+
+
+def host_agent_obs(scans: np.ndarray, obs: np.ndarray, agent: int, lidar_max: float, out: np.ndarray | None = None):
+    """f110_host_agent_obs over NumPy arrays (scans [E, A, B], obs / out [E, >= B + 4A] float32,
+    C-contiguous): the host statement of agent_obs, for tests without a GPU."""
+    scans = np.ascontiguousarray(scans, dtype=np.float32)
+    obs = np.ascontiguousarray(obs, dtype=np.float32)
+    E, A, B = scans.shape
+    if out is None:
+        out = np.empty((E, B + 4 * A), dtype=np.float32)
+    if out.dtype != np.float32 or not out.flags.c_contiguous or out.ndim != 2 or obs.ndim != 2:
+        raise ValueError("obs and out must be C-contiguous float32 [E, >= B + 4A] arrays")
+    _lib.check(_lib.load().f110_host_agent_obs(scans.ctypes.data, A * B, obs.ctypes.data, obs.shape[1], E, A, B,
+                                               int(agent), float(lidar_max), out.ctypes.data, out.shape[1]),
+               "f110_host_agent_obs")
+    return out
+
+
+def policy_head_rows(h: torch.Tensor, W: torch.Tensor, b: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                     out: torch.Tensor, row_mask: torch.Tensor | None = None):
+    """scale * tanh(h W^T + b) + shift (f110_policy_head_rows; the actor head without noise) into
+    the rows of ``out`` ([M, nout] float32, rows may be strided, e.g. ``act[:, 1]`` of an [M, A, 2]
+    action buffer) with row_mask != 0 (uint8 [M]; None: every row).  The other rows keep their values."""
+    M, K = h.shape
+    n = W.shape[0]
+    if h.dtype != torch.float32 or not h.is_contiguous() or not W.is_contiguous() or W.shape[1] != K:
+        raise ValueError("policy_head_rows: h [M, K] and W [nout, K] must be contiguous float32")
+    if out.shape != (M, n) or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != h.device:
+        raise ValueError("policy_head_rows: out must be [M, nout] float32 on h's device with unit column stride")
+    if row_mask is not None and (row_mask.dtype != torch.uint8 or row_mask.shape != (M,) or not row_mask.is_contiguous()
+                                 or row_mask.device != h.device):
+        raise ValueError("policy_head_rows: row_mask must be a contiguous uint8 [M] tensor on h's device")
+    s = torch.cuda.current_stream(h.device).cuda_stream
+    _lib.check(_lib.load().f110_policy_head_rows(_vp(h), _vp(W), _vp(b), _vp(scale), _vp(shift), M, K, n,
+                                                 _vp(row_mask), _vp(out), out.stride(0) if M > 1 else n,
+                                                 ctypes.c_void_p(s)), "f110_policy_head_rows")
+    return out
+
+
+def selfplay_mask(n: int, env_offset: int = 0, fraction: float = 1.0) -> np.ndarray:
+    """uint8 [n]: 1 where env ``g = env_offset + e`` races the policy opponent, 0 where it races
+    gap_follow.  Fixed per global env id, so neither the sharding nor the GPU count changes it:
+    ``((g * 2654435761) mod 2^32) < fraction * 2^32`` (Knuth's multiplicative hash of the id)."""
+    if not 0.0 <= float(fraction) <= 1.0:
+        raise ValueError(f"fraction must be in [0, 1]; got {fraction!r}")
+    g = np.arange(int(env_offset), int(env_offset) + int(n), dtype=np.uint64)
+    hashed = (g * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)
+    return (hashed.astype(np.float64) < float(fraction) * 4294967296.0).astype(np.uint8)
+
+
+class PolicyOpponent:
+    """A frozen copy of a ddpg.Actor that drives the opponent car on the device.
+
+    The copy's parameters live in one flat buffer (``flat``) allocated here once, and its
+    observations in one fixed [n_envs, obs_dim] buffer (``obs``), so a captured step graph that
+    holds ``act``'s launches sees new weights after a ``load`` without a re-capture.  The action
+    bounds are the source actor's at construction.  Device only: a device or actor shape the
+    explicit learner path does not take (learner_fused.ExplicitUpdate.actor_supported) is a
+    ValueError -- there is no torch path to keep in step."""
+
+    def __init__(self, actor, n_envs: int, device, lidar_max: float = 30.0):
+        from .ddpg import Actor, flatten_params
+        from .learner_fused import ExplicitUpdate
+        self.device = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if not ExplicitUpdate.actor_supported(actor, self.device):
+            raise ValueError("PolicyOpponent needs a HIP device and an actor of the explicit learner path "
+                             "(hidden width 128, act_dim <= 2)")
+        self.n_envs = int(n_envs)
+        if self.n_envs < 1:
+            raise ValueError(f"n_envs must be at least 1; got {n_envs}")
+        self.lidar_max = float(lidar_max)
+        self.obs_dim, self.act_dim = actor.fc1.in_features, actor.fc3.out_features
+        low, high = actor.action_low.detach().cpu().tolist(), actor.action_high.detach().cpu().tolist()
+        with torch.random.fork_rng(devices=[]):  # the copy's throw-away init draws leave the caller's generator alone
+            self.actor = Actor(self.obs_dim, self.act_dim, low, high)
+        self.actor = self.actor.to(self.device).requires_grad_(False)
+        self.flat = flatten_params(self.actor)
+        self._scale, self._shift = (t.contiguous() for t in self.actor._affine())
+        self.obs = torch.zeros(self.n_envs, self.obs_dim, dtype=torch.float32, device=self.device)
+        self.load(actor)
+
+    @staticmethod
+    def _flat_of(actor):
+        """The flat buffer an actor's parameters are views of, in parameter order (flatten_params'
+        layout), or None."""
+        params = list(actor.parameters())
+        p0, off = params[0], 0
+        for p in params:
+            if (not p.is_contiguous() or p.untyped_storage().data_ptr() != p0.untyped_storage().data_ptr()
+                    or p.storage_offset() != p0.storage_offset() + off):
+                return None
+            off += p.numel()
+        return torch.empty(0, dtype=p0.dtype, device=p0.device).set_(p0.untyped_storage(), p0.storage_offset(), (off,))
+
+    def load(self, actor):
+        """Take ``actor``'s weights: one flat device-to-device copy on the current stream when its
+        parameters are one flat buffer (a learner's on the GPU are), else one copy per parameter."""
+        src = [p.detach() for p in actor.parameters()]
+        dst = list(self.actor.parameters())
+        if len(src) != len(dst) or any(a.shape != b.shape for a, b in zip(src, dst)):
+            raise ValueError("PolicyOpponent.load: the actor's shape differs from the snapshot's")
+        flat = self._flat_of(actor) if src[0].device == self.device and src[0].dtype == torch.float32 else None
+        with torch.no_grad():
+            if flat is not None:
+                self.flat.copy_(flat)
+            else:
+                for a, b in zip(src, dst):
+                    b.copy_(a)
+
+    def state_dict(self):
+        return self.actor.state_dict()
+
+    def load_state_dict(self, sd):
+        """The parameters of a saved snapshot, copied into the flat buffer in place."""
+        with torch.no_grad():
+            for name, p in self.actor.named_parameters():
+                p.copy_(sd[name])
+
+    def act(self, sim_out, agent: int, out_rows: torch.Tensor, row_mask: torch.Tensor | None = None, obs=None):
+        """The snapshot's action (no noise: choose_action(training=False)) for agent ``agent`` of
+        every env, from the simulator outputs ``sim_out`` (obs: the step's obs tensor when the step
+        wrote it elsewhere than sim_out.obs), into ``out_rows`` ([n_envs, act_dim] float32, rows may
+        be strided) where row_mask != 0 (None: every row).  Three stages on the current stream:
+        f110_agent_obs into the fixed buffer, fc1 and fc2 on the learner GEMMs over all rows,
+        f110_policy_head_rows."""
+        from .learner_fused import ExplicitUpdate
+        agent_obs(sim_out.scans, sim_out.obs if obs is None else obs, agent, self.lidar_max, out=self.obs)
+        h2 = ExplicitUpdate.actor_hidden(self.actor, self.obs)
+        return policy_head_rows(h2, self.actor.fc3.weight, self.actor.fc3.bias, self._scale, self._shift, out_rows,
+                                row_mask)

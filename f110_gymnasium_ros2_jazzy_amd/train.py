@@ -5,7 +5,10 @@ Per vector step, everything on the device:
   ego action    random U(low, high) during warm-up (:162-163), else the actor
                 + Gaussian or OU noise (:165); the last `eval_envs` envs are
                 evaluation envs (:158-165): the actor's action, noise-free, from step 0
-  opponent      gap_follow_action on its previous scan (:168), inside F110VectorEnv
+  opponent      gap_follow_action on its previous scan (:168), inside F110VectorEnv; with
+                --opponent self a frozen snapshot of the learner's actor instead (its own seat's
+                observation, noise-free), refreshed every --selfplay-sync learner updates, in the
+                --selfplay-fraction of the envs picked by opponent.selfplay_mask
   env.step      (:174) with device autoreset (gymnasium NEXT_STEP)
   reward        CenterlineSafetyProgressReward (:127-146, :179) on the device
   remember      (:184) every transition except the reset rows of autoreset steps;
@@ -45,7 +48,22 @@ class VectorTrainer:
                  device=None, env_offset: int = 0, rank_seed: int = 0, graphs: bool = True,
                  max_episode_steps: int | None = None, stall_speed: float = 0.0, stall_steps: int | None = None,
                  noise_type: str = "gaussian", eval_envs: int = 0, ou_reset: bool = False, n_step: int = 1,
-                 algo: str = "ddpg", policy_delay: int = 2, policy_noise: float = 0.2, noise_clip: float = 0.5):
+                 algo: str = "ddpg", policy_delay: int = 2, policy_noise: float = 0.2, noise_clip: float = 0.5,
+                 opponent: str = "gap_follow", selfplay_sync: int = 1000, selfplay_fraction: float = 1.0):
+        # the self-play arguments: ValueError before anything is built
+        if opponent not in ("gap_follow", "self"):
+            raise ValueError(f"opponent must be 'gap_follow' or 'self'; got {opponent!r}")
+        if int(selfplay_sync) != selfplay_sync or selfplay_sync < 1:
+            raise ValueError(f"selfplay_sync must be an integer >= 1; got {selfplay_sync!r}")
+        if not 0.0 <= float(selfplay_fraction) <= 1.0:
+            raise ValueError(f"selfplay_fraction must be in [0, 1]; got {selfplay_fraction!r}")
+        self.selfplay = opponent == "self"
+        self.selfplay_sync, self.selfplay_fraction = int(selfplay_sync), float(selfplay_fraction)
+        if self.selfplay:
+            from . import ddpg
+            if torch.device(device or "cuda").type != "cuda" or not (ddpg.FUSED and ddpg.EXPLICIT):
+                raise ValueError("opponent='self' needs the explicit learner path (a HIP device, F110_DDPG_FUSED "
+                                 "and F110_DDPG_EXPLICIT on): the policy opponent has no torch path")
         from .ddpg import DDPGLearner
         from .maps import MAP_DIR
         from .reward import BatchedCenterlineReward, CenterlineTrack
@@ -65,10 +83,36 @@ class VectorTrainer:
         # With evaluation envs the trainer keeps the statistics itself, one EpisodeStats over the
         # training rows and one over the eval rows (contiguous row ranges of the step's buffers)
         self.episode_stats = bool(max_episode_steps or stall_steps or self.eval_envs)
-        self.env = F110VectorEnv(self.N, map=map_name, num_agents=2, seed=seed, device=self.device,
-                                 env_offset=env_offset, opponent="gap_follow", reward_fn=self.reward_fn,
-                                 infos="minimal", max_episode_steps=max_episode_steps, stall_speed=stall_speed,
-                                 stall_steps=stall_steps, episode_stats=self.episode_stats and not self.eval_envs)
+        env_kw = dict(map=map_name, num_agents=2, seed=seed, device=self.device, env_offset=env_offset,
+                      reward_fn=self.reward_fn, infos="minimal", max_episode_steps=max_episode_steps,
+                      stall_speed=stall_speed, stall_steps=stall_steps,
+                      episode_stats=self.episode_stats and not self.eval_envs)
+        learner = lambda obs_dim: DDPGLearner(  # noqa: E731
+            obs_dim=obs_dim, act_dim=2, action_low=ACTION_LOW, action_high=ACTION_HIGH, gamma=0.99, tau=0.005,
+            actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size, alpha=0.6, beta=0.4,
+            priority_epsilon=1e-5, noise_sigma_start=0.20, noise_sigma_min=0.02, noise_decay=0.9995, seed=seed,
+            device=self.device, max_add=self.N, graphs=graphs, noise_type=noise_type, n_step=n_step, algo=algo,
+            policy_delay=policy_delay, policy_noise=policy_noise, noise_clip=noise_clip)
+        self.opp = None
+        if self.selfplay:
+            # the snapshot needs the learner's actor, the env the snapshot: the learner comes first (its
+            # obs_dim from the library's beam count), and the snapshot starts as the initial actor, which
+            # the warm-up is raced against
+            from . import _lib
+            from .opponent import PolicyOpponent, selfplay_mask
+            self.agent = learner(_lib.default_config().n_beams + 4 * 2)
+            if self.agent.explicit is None:
+                raise ValueError("opponent='self' needs a learner with the explicit path")
+            self.opp = PolicyOpponent(self.agent.actor, self.N, self.device)
+            mixed = self.selfplay_fraction < 1.0
+            self.env = F110VectorEnv(self.N, opponent="mixed" if mixed else "policy", opponent_policy=self.opp,
+                                     opponent_mask=selfplay_mask(self.N, env_offset, self.selfplay_fraction)
+                                     if mixed else None, **env_kw)
+            if self.env.single_observation_space.shape[0] != self.agent.obs_dim:
+                raise ValueError("the env's observation size differs from the learner's")
+        else:
+            self.env = F110VectorEnv(self.N, opponent="gap_follow", **env_kw)
+        self._synced_at = 0  # the learner update index of the snapshot's last load
         self.train_stats = self.eval_stats = self._eval_mask = None
         if self.eval_envs:
             from .episode import EpisodeStats
@@ -76,14 +120,8 @@ class VectorTrainer:
             self.eval_stats = EpisodeStats(self.eval_envs, device=self.device)
             self._eval_mask = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
             self._eval_mask[self.N - self.eval_envs:] = 1
-        self.agent = DDPGLearner(obs_dim=self.env.single_observation_space.shape[0], act_dim=2,
-                                 action_low=ACTION_LOW, action_high=ACTION_HIGH, gamma=0.99, tau=0.005,
-                                 actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size,
-                                 alpha=0.6, beta=0.4, priority_epsilon=1e-5, noise_sigma_start=0.20,
-                                 noise_sigma_min=0.02, noise_decay=0.9995, seed=seed, device=self.device,
-                                 max_add=self.N, graphs=graphs, noise_type=noise_type, n_step=n_step,
-                                 algo=algo, policy_delay=policy_delay, policy_noise=policy_noise,
-                                 noise_clip=noise_clip)
+        if not self.selfplay:
+            self.agent = learner(self.env.single_observation_space.shape[0])
         self.warmup = int(warmup_steps)
         self.updates_per_step = int(updates_per_step)
         # HIP graphs per vector step once the learner's eager warm-up updates are done (explicit
@@ -122,9 +160,38 @@ class VectorTrainer:
         if self.global_step >= self.warmup:
             for _ in range(self.updates_per_step):
                 self.last = self.agent.replay()
+        self._selfplay_sync()
         self.obs = next_obs
         self.global_step += 1
         return rew, term
+
+    def _selfplay_sync(self):
+        """After every selfplay_sync-th completed learner update the snapshot takes the actor's
+        weights: one flat copy on the current stream, on the host side of the step and outside any
+        captured graph.  The snapshot's buffers are fixed, so the next step's opponent forward --
+        eager or a replayed step graph -- is the first to use them."""
+        if self.opp is None:
+            return
+        n = self.agent.global_step
+        if n != self._synced_at and n % self.selfplay_sync == 0:
+            self.opp.load(self.agent.actor)
+            self._synced_at = n
+
+    def save_checkpoint(self, filename: str = "best.pt"):
+        """DDPGLearner.save_model (same keys); with self-play also "opponent_actor", the snapshot's
+        state dict, so a resumed run races the same opponent."""
+        self.agent.save_model(filename, extra={"opponent_actor": self.opp.state_dict()} if self.opp else None)
+
+    def load_checkpoint(self, filename: str = "best.pt") -> bool:
+        """DDPGLearner.load_model, then the snapshot from "opponent_actor" (a file without the key
+        leaves the snapshot as it is)."""
+        if not self.agent.load_model(filename):
+            return False
+        if self.opp is not None:
+            ckpt = torch.load(os.path.join(self.agent.path, filename), map_location=self.device, weights_only=True)
+            if "opponent_actor" in ckpt:
+                self.opp.load_state_dict(ckpt["opponent_actor"])
+        return True
 
     def _graph_ready(self) -> bool:
         ag = self.agent
@@ -216,6 +283,7 @@ class VectorTrainer:
         graphs, out, ret = self._sg[p, actor_step]
         ag._run_phases([g.replay for g in graphs])  # several ranks: with the bucket all-reduces between
         self.last = ag._update_result(out, actor_step)
+        self._selfplay_sync()
         self.obs = bufs[1 - p]
         self._sg_parity ^= 1
         self.global_step += 1
@@ -278,6 +346,12 @@ def main():
     ap.add_argument("--policy-noise", type=float, default=0.2,
                     help="td3: target smoothing noise, in units of the action half-range")
     ap.add_argument("--noise-clip", type=float, default=0.5, help="td3: clip of the smoothing noise, same units")
+    ap.add_argument("--opponent", choices=("gap_follow", "self"), default="gap_follow",
+                    help="the car the learner races: the rule-based gap follower, or a frozen copy of its own actor")
+    ap.add_argument("--selfplay-sync", type=int, default=1000,
+                    help="self: refresh the frozen copy every K learner updates")
+    ap.add_argument("--selfplay-fraction", type=float, default=1.0,
+                    help="self: share of the envs that race the copy (the others race gap_follow)")
     ap.add_argument("--save-dir", default=None, help="rank 0 saves best.pt here when eval_return_mean improves")
     args = ap.parse_args()
     rank, world, local = D.init()
@@ -288,7 +362,8 @@ def main():
                        rank_seed=rank, max_episode_steps=args.max_episode_steps, stall_speed=args.stall_speed,
                        stall_steps=args.stall_steps, noise_type=args.noise, eval_envs=args.eval_envs,
                        ou_reset=args.ou_reset, n_step=args.n_step, algo=args.algo, policy_delay=args.policy_delay,
-                       policy_noise=args.policy_noise, noise_clip=args.noise_clip)
+                       policy_noise=args.policy_noise, noise_clip=args.noise_clip, opponent=args.opponent,
+                       selfplay_sync=args.selfplay_sync, selfplay_fraction=args.selfplay_fraction)
     best = -float("inf")
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)
@@ -301,7 +376,7 @@ def main():
             if rank == 0 and args.save_dir and ev is not None and ev > best:  # train_ddpg.py:213-216, batched
                 best = ev
                 tr.agent.path = args.save_dir
-                tr.agent.save_model("best.pt")
+                tr.save_checkpoint("best.pt")
             if rank == 0:
                 st = tr.last or {}
                 print(json.dumps({"step": k + 1, "algo": args.algo,

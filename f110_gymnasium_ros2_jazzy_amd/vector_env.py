@@ -22,7 +22,11 @@ rule-based opponent (gap_follow.py) on the device, as train_ddpg.py:168 does
 on the host: its action for step t comes from its own float32 scan of step
 t-1 (or of the reset).  ``step`` then takes the other agents' actions
 ([N, 2] for two agents) and ``infos["opponent_actions"]`` shows the
-opponent's.
+opponent's.  ``opponent="policy"`` drives it with ``opponent_policy`` (an
+opponent.PolicyOpponent: a frozen Actor's noise-free action from the
+opponent's own seat, same timing), ``opponent="mixed"`` with the policy in the
+envs where ``opponent_mask`` (uint8 [N]) is set and gap_follow in the others;
+the infos and the action rows are the same for all three.
 
 ``param_ranges`` ({field: (lo, hi)}, or one such dict per agent) turns on the
 device's domain randomization of the vehicle dynamics: every reset and
@@ -71,10 +75,13 @@ class F110VectorEnv:
                  ego_idx: int = 0, as_numpy: bool = False, autoreset: bool = True, opponent: str | None = None,
                  opponent_idx: int = 1, reward_fn=None, infos: str = "full", options_dtype=np.float32,
                  param_ranges=None, param_seed: int | None = None, max_episode_steps: int | None = None,
-                 stall_speed: float = 0.0, stall_steps: int | None = None, episode_stats: bool = False, **kwargs):
+                 stall_speed: float = 0.0, stall_steps: int | None = None, episode_stats: bool = False,
+                 opponent_policy=None, opponent_mask=None, **kwargs):
         self.num_envs = int(num_envs)
         self.num_agents = int(num_agents)
         self.params = dict(params or DEFAULT_PARAMS)
+        # a bad opponent argument: ValueError before anything is built
+        self._check_opponent(opponent, int(opponent_idx), opponent_policy, opponent_mask)
         if param_ranges is not None:  # an unknown field: ValueError before anything is built
             param_range_rows(param_ranges, [{**DEFAULT_PARAMS, **self.params}] * self.num_agents)
         # a bad episode limit: ValueError before anything is built
@@ -128,11 +135,16 @@ class F110VectorEnv:
         self.infos_mode = infos
         if reward_fn is not None and reward_fn.n_envs != self.num_envs:
             raise ValueError("reward_fn must be built for num_envs envs")
+        self.opponent_policy = opponent_policy if opponent in ("policy", "mixed") else None
+        self.opponent_mask = None
+        if self.opponent_policy is not None and (self.opponent_policy.obs_dim != B + 4 * A
+                                                 or self.opponent_policy.device != self.device):
+            raise ValueError(f"opponent_policy must take {B + 4 * A} observations on {self.device}")
         if opponent is not None:
-            if opponent != "gap_follow":
-                raise ValueError(f"unknown opponent policy {opponent!r} (supported: 'gap_follow')")
-            if not (0 <= self.opponent_idx < A) or A < 2:
-                raise ValueError("opponent needs num_agents >= 2 and 0 <= opponent_idx < num_agents")
+            if opponent == "mixed":
+                m = torch.as_tensor(opponent_mask)
+                m = m.view(torch.uint8) if m.dtype == torch.bool else m
+                self.opponent_mask = m.to(self.device).contiguous()
             self._act = torch.zeros(self.num_envs, A, 2, dtype=torch.float32, device=self.device)
             self._others = [i for i in range(A) if i != self.opponent_idx]
             # a contiguous run of caller-driven agents is written with a slice
@@ -140,11 +152,44 @@ class F110VectorEnv:
             o = self._others
             self._others_sl = slice(o[0], o[-1] + 1) if o and o == list(range(o[0], o[-1] + 1)) else o
 
-    def _opponent_next(self, out):
-        """Next step's opponent action from this step's scans (train_ddpg.py:168)."""
-        if self.opponent is not None:
+    OPPONENTS = ("gap_follow", "policy", "mixed")
+
+    def _check_opponent(self, opponent, idx, policy, mask):
+        """The opponent arguments against each other and the env's shape (host values only)."""
+        if opponent is None:
+            return
+        N, A = self.num_envs, self.num_agents
+        if opponent not in self.OPPONENTS:
+            raise ValueError(f"unknown opponent policy {opponent!r} (supported: 'gap_follow', 'policy', 'mixed')")
+        if not (0 <= idx < A) or A < 2:
+            raise ValueError("opponent needs num_agents >= 2 and 0 <= opponent_idx < num_agents")
+        if opponent == "gap_follow":
+            return
+        if policy is None:
+            raise ValueError(f"opponent={opponent!r} needs opponent_policy (an opponent.PolicyOpponent)")
+        lidar_max = float({**DEFAULT_PARAMS, **self.params}["lidar_max"])
+        if policy.n_envs != N or policy.act_dim != 2 or policy.lidar_max != lidar_max:
+            raise ValueError(f"opponent_policy must be built for {N} envs, 2 action columns and lidar_max {lidar_max}")
+        if opponent == "mixed":
+            if mask is None:
+                raise ValueError("opponent='mixed' needs opponent_mask (uint8 [num_envs])")
+            if tuple(mask.shape) != (N,) or str(mask.dtype).split(".")[-1] not in ("uint8", "bool"):
+                raise ValueError(f"opponent_mask must be a uint8 [{N}] array or tensor")
+
+    def _opponent_next(self, out, obs=None):
+        """Next step's opponent action from this step's outputs: gap_follow from its scan
+        (train_ddpg.py:168); "policy": the PolicyOpponent's forward from the opponent's seat (obs: the
+        step's obs when the simulator wrote it elsewhere than out.obs); "mixed": gap_follow writes
+        every row, then the policy head overwrites the rows with opponent_mask != 0 -- the policy's
+        hidden layers still run over all N rows (one fixed-shape GEMM pair, whatever the mask)."""
+        if self.opponent is None:
+            return
+        rows = self._act[:, self.opponent_idx]
+        if self.opponent != "policy":
             from .opponent import gap_follow
-            gap_follow(out.scans[:, self.opponent_idx], out=self._act[:, self.opponent_idx])
+            gap_follow(out.scans[:, self.opponent_idx], out=rows)
+        if self.opponent_policy is not None:
+            self.opponent_policy.act(out, self.opponent_idx, rows, row_mask=self.opponent_mask, obs=obs)
 
     # ------------------------------------------------------------------
     def _episode_infos(self, infos, out):
@@ -261,7 +306,7 @@ class F110VectorEnv:
             a = a.unsqueeze(1)
         out = self.sim.step(a, obs_out=obs_out)  # the simulator writes obs_out itself (no copy)
         obs = out.obs if obs_out is None else obs_out
-        self._opponent_next(out)
+        self._opponent_next(out, obs)
         if self.reward_fn is not None:
             rewards = self.reward_fn(obs, reset_mask=out.was_reset)
         else:

@@ -339,6 +339,34 @@ F110_API int f110_gap_follow(const float *scans, int64_t n_scans, int64_t scan_s
                              double angle_min, double angle_increment, float *actions, int64_t action_stride,
                              int32_t *gaps, void *stream);
 
+/* ---- self-play ---------------------------------------------------------------
+ * An opponent driven by a policy instead of gap_follow_action: the observation from its seat and
+ * an actor head that writes into its rows of the next f110_step's action array.  No reference
+ * counterpart (train_ddpg.py races the rule-based opponent only).  Device pointers, async on
+ * `stream`; deterministic (no atomics). */
+
+/* F110Env._pack_flat_obs (f110_env.py:552-584) as agent `agent` would see it:
+ * out[e] = [ obs_scan(scans[e][agent][0..B)) , pose block of `agent`,
+ *            pose blocks of the other agents in ascending index ]
+ * The scan entries are the step's own (NaN / +inf -> lidar_max, -inf -> 0, clip to [0, lidar_max],
+ * one f32 divide): agent == ego_idx reproduces the step's obs row bit for bit.  out must not
+ * overlap obs.  16-byte accesses when n_beams and the three strides are multiples of 4 and the
+ * pointers 16-byte aligned, 4-byte ones otherwise; the same values either way.  F110_E_INVALID:
+ * agent outside [0, n_agents), a stride too small, a null pointer. */
+F110_API int f110_agent_obs(const float *scans, int64_t scan_env_stride,      /* f110_outputs.scans, floats per env (>= A*B) */
+                            const float *obs, int64_t obs_stride,             /* the step's obs: only its pose block [B, B+4A) is read */
+                            int64_t n_envs, int32_t n_agents, int32_t n_beams, int32_t agent, float lidar_max,
+                            float *out, int64_t out_stride, void *stream);    /* out_stride >= B + 4A */
+
+/* act = shift + scale * tanh(h W^T + b) (Actor.forward's last line, agent.py:56-61) for the rows with
+ * row_mask[i] != 0 (row_mask NULL: every row), written to out + i*out_stride; other rows of out untouched.
+ * h [n_rows][K], W [nout][K], b / scale / shift [nout] as f110_ddpg_actor_head takes them; an
+ * unmasked row gets the bits of that head's act.  No noise, no clip, no noise state:
+ * choose_action(training=False) for those rows. */
+F110_API int f110_policy_head_rows(const float *h, const float *W, const float *b, const float *scale, const float *shift,
+                                   int64_t n_rows, int32_t K, int32_t nout, const uint8_t *row_mask,
+                                   float *out, int64_t out_stride, void *stream);
+
 /* ---- training reward ---------------------------------------------------------
  * Replaces rl_training/utils/rewards.py:CenterlineSafetyProgressReward
  * (:185-355) over utils/track_progress.py:CenterlineProgress (:5-110), the

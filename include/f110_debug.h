@@ -312,6 +312,14 @@ F110_API int f110_host_nstep(int64_t n_envs, int32_t n_step, double gamma, int32
                              const uint8_t *was_reset, float *out_obs, float *out_act, float *out_reward,
                              float *out_next_obs, float *out_done, int64_t *out_count);
 
+/* f110_agent_obs over HOST arrays (same arguments, no stream): the same scan entry the kernels run
+ * (obs_scan_value, csrc/f110_device.h) and the same pose-group order.  Same validation
+ * (F110_E_INVALID).  Host test hook: the CPU suite and the GPU tests share one statement of the
+ * semantics. */
+F110_API int f110_host_agent_obs(const float *scans, int64_t scan_env_stride, const float *obs, int64_t obs_stride,
+                                 int64_t n_envs, int32_t n_agents, int32_t n_beams, int32_t agent, float lidar_max,
+                                 float *out, int64_t out_stride);
+
 #ifdef __cplusplus
 }
 #endif
