@@ -154,6 +154,9 @@ _API = {
     "f110_replay_update_priorities": (_i, [_P, _P, _P, _i64, _i32, _f32, _P]),
     "f110_replay_length": (_i, [_P, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _P]),
     "f110_replay_arrays": (_i, [_P] + _PTRS6),
+    "f110_replay_select_keys": (_i, [_P, _P, _i64, _i32, _f64, _P, _P, _P]),
+    "f110_replay_select_state": (_i, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P)] +
+                                 [ctypes.POINTER(ctypes.c_uint32)] * 3 + [_D, ctypes.POINTER(ctypes.c_uint32), _P]),
     "f110_debug_wave_trace": (_i, [_P, _i32, _P, _i64, ctypes.POINTER(_i64), _P]),
     "f110_debug_set_ray_gate": (_i, [_P, _P, _P]),
     "f110_debug_disable_heavy_first": (_i, [_P]),

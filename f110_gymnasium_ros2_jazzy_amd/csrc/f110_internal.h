@@ -346,7 +346,7 @@ struct ReplayHdr {
     uint32_t prefix;    // radix select: threshold key so far
     uint32_t kleft;     //   rank still to select below/at the prefix
     uint32_t n_lt, n_tie;  // keys below / equal to the threshold (n_tie zeroed by k_finish)
-    uint32_t overflow;  // samples whose tie list overflowed kTieCap
+    uint32_t overflow;  // samples whose tie list overflowed kTieCap (k_finish then walks the keys itself)
     uint32_t pad_;
     uint32_t sel_prefix[4], sel_kleft[4];  // the select through digit q (written by the kernel after
                                            // pass q's histogram, read by the next one)
@@ -389,6 +389,8 @@ hipError_t launch_replay_add_index(const ReplayView &v, const uint8_t *mask, int
 hipError_t launch_replay_add_copy(const ReplayView &v, const ReplayRows &in, int64_t n, hipStream_t s);  // the rows
 hipError_t launch_replay_select(const ReplayView &v, int32_t batch, double beta, int64_t *idx, float *w,
                                 bool known_full, hipStream_t s);  // idx / weights (reads no row data)
+hipError_t launch_replay_select_keys(const ReplayView &v, int32_t batch, double beta, int64_t *idx, float *w,
+                                     hipStream_t s);  // the same select over given v.keys (length >= batch)
 hipError_t launch_replay_gather(const ReplayView &v, int32_t batch, const int64_t *idx, const ReplayBatch &out,
                                 hipStream_t s);
 hipError_t launch_replay_update(const ReplayView &v, const int64_t *idx, const float *val, int64_t n, float add_eps,

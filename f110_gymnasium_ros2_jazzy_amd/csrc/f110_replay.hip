@@ -388,6 +388,8 @@ __global__ void __launch_bounds__(kRB) k_nstep_reset(NstepView w, const uint8_t 
 // kRB threads: the same rows per thread and the same den partials, summed
 // per virtual block in wave order, as one kRB block each), with one LDS
 // histogram and one set of global atomics per real block.
+// kGiven: the keys are already in v.keys (f110_replay_select_keys) and are read, not drawn.
+template <bool kGiven>
 __global__ void __launch_bounds__(kKB) k_keys(ReplayView v, int32_t batch, int vgrid) {
     constexpr int Q = kKB / kRB;
     __shared__ uint32_t hist[256];
@@ -404,11 +406,16 @@ __global__ void __launch_bounds__(kKB) k_keys(ReplayView v, int32_t batch, int v
         for (int64_t i = (int64_t)vb * kRB + t; i < len; i += (int64_t)vgrid * kRB) {
             const double w = v.wt[i];  // prio_weight(prio[i]), cached at add / update
             acc += w;
-            U4 c = {(uint32_t)i, (uint32_t)((uint64_t)i >> 32), (uint32_t)draw, (uint32_t)(draw >> 32)};
-            U4 r = philox(c, (uint32_t)v.seed, (uint32_t)(v.seed >> 32) ^ 0x9E3779B9u);
-            const double e = -log(u01_open(r.x, r.y));  // Exp(1)
-            const uint32_t key = f32_bits((float)(e / w));
-            v.keys[i] = key;
+            uint32_t key;
+            if constexpr (kGiven) {
+                key = v.keys[i];
+            } else {
+                U4 c = {(uint32_t)i, (uint32_t)((uint64_t)i >> 32), (uint32_t)draw, (uint32_t)(draw >> 32)};
+                U4 r = philox(c, (uint32_t)v.seed, (uint32_t)(v.seed >> 32) ^ 0x9E3779B9u);
+                const double e = -log(u01_open(r.x, r.y));  // Exp(1)
+                key = f32_bits((float)(e / w));
+                v.keys[i] = key;
+            }
             hist_add_wave(hist, key >> 24);
         }
     // per virtual block: a shuffle tree per wave, its waves added in order (block_sum_f64)
@@ -609,28 +616,68 @@ __global__ void __launch_bounds__(kOneBlock) k_finish(ReplayView v, int32_t batc
     if (len < batch) return;
     int64_t *idx = reinterpret_cast<int64_t *>(smem);     // [batch]
     double *wsh = reinterpret_cast<double *>(idx + batch);  // [batch]
-    __shared__ uint32_t chosen[64];
+    // the chosen ties in index order, need <= batch of them: they lie in wsh (room for 2 * batch)
+    // until the merge is done and the weights overwrite them
+    uint32_t *chosen = reinterpret_cast<uint32_t *>(wsh);
     __shared__ uint32_t n_ch;
+    __shared__ uint32_t wcnt[kOneBlock / 64];
     const uint32_t n_lt = min(v.hdr->n_lt, (uint32_t)batch);
-    const uint32_t n_tie = min(v.hdr->n_tie, (uint32_t)kTieCap);
+    const uint32_t n_all = v.hdr->n_tie;  // every key equal to T; the list holds the first kTieCap to arrive
+    const uint32_t n_tie = min(n_all, (uint32_t)kTieCap);
     const uint32_t need = (uint32_t)batch - n_lt;
     if (threadIdx.x == 0) n_ch = 0;
     __syncthreads();
-    for (uint32_t t = threadIdx.x; t < n_tie; t += blockDim.x) {  // rank among the ties by index
-        const uint32_t mine = v.tie[t];
-        uint32_t rank = 0;
-        for (uint32_t u = 0; u < n_tie; ++u) rank += v.tie[u] < mine ? 1u : 0u;
-        if (rank < need) {
-            if (rank < 64) chosen[rank] = mine;
-            atomicAdd(&n_ch, 1u);
+    if (__builtin_expect(n_all <= (uint32_t)kTieCap, 1)) {
+        for (uint32_t t = threadIdx.x; t < n_tie; t += blockDim.x) {  // rank among the ties by index
+            const uint32_t mine = v.tie[t];
+            uint32_t rank = 0;
+            for (uint32_t u = 0; u < n_tie; ++u) rank += v.tie[u] < mine ? 1u : 0u;
+            if (rank < need) {
+                chosen[rank] = mine;
+                atomicAdd(&n_ch, 1u);
+            }
         }
+    } else {
+        // The list overflowed and holds an arbitrary kTieCap of the ties: the block walks the keys
+        // in index order itself and takes the first `need` equal to T (tiles of blockDim.x rows, a
+        // ballot per wave, the waves' counts added in order).  One pass over at most len keys, on
+        // a sample that meets more than kTieCap equal keys at its threshold; counted in overflow.
+        const uint32_t T = v.hdr->prefix;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (int)(blockDim.x >> 6);
+        uint32_t found = 0;  // block-uniform
+        for (int64_t j0 = 0; j0 < len && found < need; j0 += blockDim.x) {
+            const int64_t i = j0 + threadIdx.x;
+            const bool is = i < len && v.keys[i] == T;
+            const uint64_t bal = __builtin_amdgcn_ballot_w64(is);
+            const uint32_t before =
+                __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+            if (lane == 0) wcnt[wave] = (uint32_t)__builtin_popcountll(bal);
+            __syncthreads();
+            uint32_t pre = 0, total = 0;
+            for (int w = 0; w < nw; ++w) {
+                pre += w < wave ? wcnt[w] : 0u;
+                total += wcnt[w];
+            }
+            const uint32_t s = found + pre + before;
+            if (is && s < need) chosen[s] = (uint32_t)i;
+            found += total;
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) n_ch = min(found, need);
     }
     __syncthreads();
-    const uint32_t nc = min(n_ch, 64u);  // kTieCap ties, of which need (typically 1) are taken
+    const uint32_t nc = n_ch;  // need of them (typically 1)
+    // The merge below fills slots 0 .. n_lt + nc - 1.  Fewer than the batch only if the select's
+    // counts were inconsistent: the rest is row 0, so that no slot leaves [0, len).
+    for (uint32_t j = n_lt + nc + threadIdx.x; j < (uint32_t)batch; j += blockDim.x) idx[j] = 0;
     for (uint32_t j = threadIdx.x; j < n_lt; j += blockDim.x) {  // main rows shift past smaller ties
         const uint64_t i = v.sel[j];
-        uint32_t k = 0;
-        for (uint32_t c = 0; c < nc; ++c) k += chosen[c] < i ? 1u : 0u;
+        uint32_t k = 0, hi = nc;  // chosen ties with an index below i
+        while (k < hi) {
+            const uint32_t mid = (k + hi) >> 1;
+            if (chosen[mid] < i) k = mid + 1;
+            else hi = mid;
+        }
         idx[j + k] = (int64_t)i;
     }
     for (uint32_t c = threadIdx.x; c < nc; c += blockDim.x) {  // ties after the smaller main rows
@@ -649,7 +696,7 @@ __global__ void __launch_bounds__(kOneBlock) k_finish(ReplayView v, int32_t batc
     if (threadIdx.x == 0) {
         v.hdr->draws += 1;
         v.hdr->replace = 0;
-        if (v.hdr->n_tie > (uint32_t)kTieCap || n_ch > 64u) v.hdr->overflow += 1;
+        if (n_all > (uint32_t)kTieCap) v.hdr->overflow += 1;
         v.hdr->n_tie = 0;  // consumed: zero for the next sample
     }
 }
@@ -663,7 +710,8 @@ __global__ void __launch_bounds__(kOneBlock) k_sample_replace(ReplayView v, int3
     if (len >= batch || len <= 0) return;
     double *cdf = reinterpret_cast<double *>(smem);  // [batch] (len < batch)
     int64_t *idx = reinterpret_cast<int64_t *>(cdf + batch);
-    double *wsh = reinterpret_cast<double *>(idx + batch);
+    double *wsh = cdf;  // the weights take the cdf's place once every row is drawn: 16 B per row, as k_finish
+                        // (24 B per row would pass the LDS of a CU at the largest batch)
     for (int64_t i = threadIdx.x; i < len; i += blockDim.x) cdf[i] = v.wt[i];
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -787,7 +835,7 @@ int keys_grid(int grid) { return (grid + kKB / kRB - 1) / (kKB / kRB); }
 
 size_t replay_finish_lds(int32_t batch) { return (size_t)batch * 16; }
 
-size_t replay_replace_lds(int32_t batch) { return (size_t)batch * 24; }
+size_t replay_replace_lds(int32_t batch) { return (size_t)batch * 16; }
 
 hipError_t launch_replay_add_index(const ReplayView &v, const uint8_t *mask, int mask_skip, const float *priority,
                                    int64_t n, hipStream_t s) {
@@ -820,20 +868,38 @@ hipError_t launch_nstep_reset(const NstepView &w, const uint8_t *env_mask, hipSt
     return hipGetLastError();
 }
 
-hipError_t launch_replay_select(const ReplayView &v, int32_t batch, double beta, int64_t *idx, float *w,
-                                bool known_full, hipStream_t s) {
-    const int grid = replay_grid(v.capacity);
-    // histograms and tie count are cleared by k_place / k_finish of the previous sample
-    // (and at create), so a sample is kernels only
-    hipLaunchKernelGGL(k_keys, dim3(keys_grid(grid)), dim3(kKB), 0, s, v, batch, grid);
+namespace {
+// The select after k_keys: the three lower digits, the counts, the placement and the tie merge.
+void launch_select_tail(const ReplayView &v, int grid, int32_t batch, double beta, int64_t *idx, float *w,
+                        hipStream_t s) {
     for (int pass = 1; pass < 4; ++pass)  // each block selects the digits so far from the histograms itself
         hipLaunchKernelGGL(k_hist, dim3(grid), dim3(kRB), 0, s, v, batch, pass);
     hipLaunchKernelGGL(k_count, dim3(grid), dim3(kRB), 0, s, v, batch, grid);
     hipLaunchKernelGGL(k_place, dim3(grid), dim3(kRB), 0, s, v, batch);
     hipLaunchKernelGGL(k_finish, dim3(1), dim3(kOneBlock), replay_finish_lds(batch), s, v, batch, beta, idx, w);
+}
+}  // namespace
+
+hipError_t launch_replay_select(const ReplayView &v, int32_t batch, double beta, int64_t *idx, float *w,
+                                bool known_full, hipStream_t s) {
+    const int grid = replay_grid(v.capacity);
+    // histograms and tie count are cleared by k_place / k_finish of the previous sample
+    // (and at create), so a sample is kernels only
+    hipLaunchKernelGGL(k_keys<false>, dim3(keys_grid(grid)), dim3(kKB), 0, s, v, batch, grid);
+    launch_select_tail(v, grid, batch, beta, idx, w, s);
     if (!known_full)  // (f110_replay_length has seen length >= batch: the with-replacement path cannot run)
         hipLaunchKernelGGL(k_sample_replace, dim3(1), dim3(kOneBlock), replay_replace_lds(batch), s, v, batch, beta,
                            idx, w);
+    return hipGetLastError();
+}
+
+// The same select over the keys the caller has put into v.keys (the caller has checked
+// length >= batch: nothing is drawn, with or without replacement).
+hipError_t launch_replay_select_keys(const ReplayView &v, int32_t batch, double beta, int64_t *idx, float *w,
+                                     hipStream_t s) {
+    const int grid = replay_grid(v.capacity);
+    hipLaunchKernelGGL(k_keys<true>, dim3(keys_grid(grid)), dim3(kKB), 0, s, v, batch, grid);
+    launch_select_tail(v, grid, batch, beta, idx, w, s);
     return hipGetLastError();
 }
 

@@ -158,6 +158,24 @@ extern "C" int f110_replay_sample(f110_replay *rb, int32_t batch, double beta, i
     return F110_OK;
 }
 
+// Test hook: the select of f110_replay_sample over keys the caller chooses (no draw, no gather).
+extern "C" int f110_replay_select_keys(f110_replay *rb, const uint32_t *keys, int64_t n, int32_t batch, double beta,
+                                       int64_t *idx, float *weights, void *stream) {
+    if (!rb || !keys || !idx || !weights) return fail(F110_E_INVALID, "f110_replay_select_keys: null argument");
+    if (batch <= 0 || batch > rb->max_batch)
+        return fail(F110_E_INVALID, "f110_replay_select_keys: batch must be in [1, max_batch]");
+    int64_t len = 0;
+    const int rc = f110_replay_length(rb, &len, nullptr, stream);
+    if (rc != F110_OK) return rc;
+    if (n != len || batch > n)
+        return fail(F110_E_INVALID, "f110_replay_select_keys: n must be the buffer's length and batch <= n");
+    const hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(rb->v.keys, keys, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = launch_replay_select_keys(rb->v, batch, beta, idx, weights, s);
+    if (e != hipSuccess) return hip_fail("f110_replay_select_keys", e);
+    return F110_OK;
+}
+
 extern "C" int f110_replay_update_priorities(f110_replay *rb, const int64_t *idx, const float *values, int64_t n,
                                              int32_t from_td, float add_eps, void *stream) {
     if (!rb || n < 0 || (n > 0 && (!idx || !values)))
@@ -190,6 +208,26 @@ extern "C" int f110_replay_arrays(f110_replay *rb, float **priority, float **obs
     if (reward) *reward = rb->v.reward;
     if (next_obs) *next_obs = rb->v.next_obs;
     if (done) *done = rb->v.done;
+    return F110_OK;
+}
+
+extern "C" int f110_replay_select_state(f110_replay *rb, uint32_t **keys, double **wt, uint32_t *prefix,
+                                        uint32_t *kleft, uint32_t *n_lt, double *den, uint32_t *overflow,
+                                        void *stream) {
+    if (!rb) return fail(F110_E_INVALID, "f110_replay_select_state: null buffer");
+    if (keys) *keys = rb->v.keys;
+    if (wt) *wt = rb->v.wt;
+    if (!prefix && !kleft && !n_lt && !den && !overflow) return F110_OK;
+    if (hipSetDevice(rb->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_replay_select_state: hipSetDevice");
+    ReplayHdr h{};
+    hipError_t e = hipMemcpyAsync(&h, rb->v.hdr, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail("f110_replay_select_state", e);
+    if (prefix) *prefix = h.prefix;
+    if (kleft) *kleft = h.kleft;
+    if (n_lt) *n_lt = h.n_lt;
+    if (den) *den = h.den;
+    if (overflow) *overflow = h.overflow;
     return F110_OK;
 }
 

@@ -197,6 +197,56 @@ class DeviceReplayBuffer:
     def priorities(self) -> torch.Tensor:
         return self.arrays(("priority",))["priority"]
 
+    # ---- the select, for tests (f110_replay_select_keys / f110_replay_select_state) ----
+    def select_keys(self, keys, beta: float = 0.4, batch_size: int | None = None):
+        """sample()'s selection over ``keys`` [len] (uint32 patterns, one per stored row) in place
+        of the drawn ones: (idxs [B] int64 ascending, weights [B] float32), no gather."""
+        k = torch.as_tensor(keys, device=self.device).reshape(-1)
+        if k.dtype != torch.uint32:
+            k = k.to(torch.int64).to(torch.uint32)
+        k = k.contiguous()
+        B = int(batch_size or self._batch_size)
+        self._keep_k = k
+        _lib.check(self.L.f110_replay_select_keys(self.handle, _p(k), k.shape[0], B, float(beta), _p(self.idx),
+                                                  _p(self.weights), self._stream()), "f110_replay_select_keys")
+        return self.idx[:B], self.weights[:B]
+
+    def _select_state(self, **out):
+        _lib.check(self.L.f110_replay_select_state(
+            self.handle, *[None if out.get(n) is None else ctypes.byref(out[n])
+                           for n in ("keys", "wt", "prefix", "kleft", "n_lt", "den", "overflow")], self._stream()),
+            "f110_replay_select_state")
+
+    def keys(self) -> torch.Tensor:
+        """[cap] uint32 copy of the last sample's keys (rows past len() hold no key)."""
+        p = ctypes.c_void_p()
+        self._select_state(keys=p)
+        t = torch.empty(self._buffer_size, dtype=torch.uint32, device=self.device)
+        _d2d(t, p.value, self._stream())
+        return t
+
+    def sampling_weights(self) -> torch.Tensor:
+        """[cap] float64 copy of (priority + eps)^alpha, as the sampler caches it."""
+        p = ctypes.c_void_p()
+        self._select_state(wt=p)
+        t = torch.empty(self._buffer_size, dtype=torch.float64, device=self.device)
+        _d2d(t, p.value, self._stream())
+        return t
+
+    def select_state(self) -> dict:
+        """The last without-replacement sample's threshold key (prefix), rows still to take among
+        its ties (kleft), rows below it (n_lt), sum of the sampling weights (den), and the
+        tie-list overflows so far (waits for the stream)."""
+        u = {n: ctypes.c_uint32() for n in ("prefix", "kleft", "n_lt", "overflow")}
+        den = ctypes.c_double()
+        self._select_state(den=den, **u)
+        return {"prefix": u["prefix"].value, "kleft": u["kleft"].value, "n_lt": u["n_lt"].value,
+                "den": den.value, "overflow": u["overflow"].value}
+
+    def tie_overflows(self) -> int:
+        """Samples so far that met more keys equal to the threshold than the tie list holds."""
+        return self.select_state()["overflow"]
+
     def close(self):
         if getattr(self, "handle", None):
             torch.cuda.synchronize(self.device)

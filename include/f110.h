@@ -465,7 +465,8 @@ F110_API int f110_episode_stats(const double *rewards, const uint8_t *terminated
  * (state, action, reward, next_state, done) with one float32 priority each.
  * All of it lives in device memory; every call below is asynchronous on
  * `stream` and takes device pointers, except f110_replay_length /
- * f110_replay_stats, which wait for the stream. */
+ * f110_replay_stats and the test hooks f110_replay_select_keys /
+ * f110_replay_select_state, which wait for the stream. */
 typedef struct f110_replay f110_replay;
 
 /* PrioritizedExperienceReplayBuffer(buffer_size=capacity, batch_size, alpha,
@@ -512,6 +513,16 @@ F110_API int f110_replay_add_env(f110_replay *rb, const float *obs, int64_t obs_
 F110_API int f110_replay_sample(f110_replay *rb, int32_t batch, double beta, int64_t *idx, float *weights, float *obs,
                                 float *act, float *reward, float *next_obs, float *done, void *stream);
 
+/* Test hook: f110_replay_sample's selection and weights over keys the caller
+ * chooses in place of the drawn ones, with no gather.  keys [n] u32 (device;
+ * the float32 patterns of the exponential-race keys lie in [0, 0x7F800000]),
+ * n == the buffer's length (the call waits for `stream` to read it) and
+ * batch <= n.  Selects the batch smallest by (key, index): idx [batch] in
+ * ascending order, weights as f110_replay_sample.  Counts as one sample (the
+ * next draw differs). */
+F110_API int f110_replay_select_keys(f110_replay *rb, const uint32_t *keys, int64_t n, int32_t batch, double beta,
+                                     int64_t *idx, float *weights, void *stream);
+
 /* update_priorities(idx, priorities) (:121-135): the priority of row idx[j]
  * becomes clip(p_j, 1e-8, FLT_MAX) in float32 with NaN -> 1e-6, where
  * p_j = values[j] (from_td == 0) or agent.replay's |values[j]| + add_eps
@@ -529,6 +540,17 @@ F110_API int f110_replay_length(f110_replay *rb, int64_t *length, int64_t *next_
  * may be NULL. */
 F110_API int f110_replay_arrays(f110_replay *rb, float **priority, float **obs, float **act, float **reward,
                                 float **next_obs, float **done);
+
+/* The last sample's select (read-only, for tests): the device pointers of its
+ * keys [capacity] u32 and of the sampling weights (priority + eps)^alpha
+ * [capacity] f64, and a host copy (waits for `stream`) of the threshold key
+ * (prefix), the rows still to take among the keys equal to it (kleft), the
+ * rows below it (n_lt), the sum of the weights (den) and the count of samples
+ * that met more equal keys at the threshold than the tie list holds
+ * (overflow).  Any out pointer may be NULL. */
+F110_API int f110_replay_select_state(f110_replay *rb, uint32_t **keys, double **wt, uint32_t *prefix,
+                                      uint32_t *kleft, uint32_t *n_lt, double *den, uint32_t *overflow,
+                                      void *stream);
 
 /* ---- n-step returns (no reference counterpart: agent.replay's targets are one-step) --
  * An accumulator in front of the replay ring: per env a window of at most n_step

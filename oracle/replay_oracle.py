@@ -12,10 +12,28 @@ draw itself:
   update_priorities :121-135
 Pinned bit-exact on tests/golden/per.npz (the reference object's own
 priority arrays, lengths, ring pointers, probabilities and weights).
+
+select_model restates the device sampler's selection rule over given keys (no
+reference counterpart: the reference draws with rng.choice); it is pinned on a
+brute-force sort in tests/test_oracle_replay.py.
 """
 from __future__ import annotations
 
 import numpy as np
+
+
+def select_model(keys, batch: int) -> np.ndarray:
+    """The sampler's selection over one key per stored row (f110_replay.hip, "sample"): the
+    ``batch`` smallest by (key, index) -- every key below the batch-th smallest key T, then the
+    lowest-index keys equal to T until the batch is full -- returned in ascending index order."""
+    keys = np.asarray(keys, dtype=np.uint32).reshape(-1)
+    batch = int(batch)
+    if not 0 < batch <= keys.size:
+        raise ValueError("select_model: 0 < batch <= len(keys)")
+    T = np.partition(keys, batch - 1)[batch - 1]
+    below = np.flatnonzero(keys < T)
+    ties = np.flatnonzero(keys == T)[:batch - below.size]  # flatnonzero is ascending
+    return np.sort(np.concatenate([below, ties])).astype(np.int64)
 
 
 class PEROracle:

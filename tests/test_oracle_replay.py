@@ -61,6 +61,34 @@ def test_per_sampling_statistics_fixture():
     assert d["stat_incl"].sum() == n * int(d["stat_batch"])
 
 
+def test_select_model_matches_brute_force_sort():
+    """replay_oracle.select_model against a sort of (key, index) pairs: distinct keys, a few
+    values repeated many times (ties below, at and above the threshold), all keys equal, the
+    extreme patterns 0 and 0x7F800000, and every batch from 1 to len on a short input."""
+    from replay_oracle import select_model
+
+    def brute(keys, B):
+        order = sorted(range(len(keys)), key=lambda i: (int(keys[i]), i))
+        return np.array(sorted(order[:B]), np.int64)
+
+    rng = np.random.default_rng(0)
+    cases = [rng.integers(0, 0x7F800001, 500, dtype=np.uint32),
+             rng.choice(np.array([0, 5, 0x3F800000, 0x7F800000], np.uint32), 500),
+             np.full(300, 0x3F000000, np.uint32),
+             np.concatenate([rng.integers(0, 1000, 200), np.full(100, 500)]).astype(np.uint32)]
+    for keys in cases:
+        for B in (1, 2, 63, 64, 65, 150, len(keys) - 1, len(keys)):
+            got = select_model(keys, B)
+            assert got.dtype == np.int64
+            np.testing.assert_array_equal(got, brute(keys, B))
+    short = np.array([7, 3, 3, 9, 3, 0, 7, 3], np.uint32)
+    for B in range(1, len(short) + 1):
+        np.testing.assert_array_equal(select_model(short, B), brute(short, B))
+    np.testing.assert_array_equal(select_model(short, 3), [1, 2, 5])  # 0, then the two lowest-index 3s
+    with pytest.raises(ValueError):
+        select_model(short, 9)
+
+
 # ---------------------------------------------------------------- DDPG ----
 def _load_state(net, d, prefix):
     sd = {k: torch.from_numpy(np.asarray(d[f"{prefix}/{k}"])) for k in net.state_dict().keys()}
