@@ -5,7 +5,7 @@
 
 Vertices are [.., 4, 2] float64 (get_vertices order: rl, rr, fr, fl), host
 arrays or tensors; results are device tensors on `device` (cuda:0 default).
-The kernels are the GJK of the batched step (f110_device.h gjk_collision)
+The kernels are the GJK of the batched step (f110_geometry.h gjk_collision)
 behind f110_collision_batch / f110_collision_multiple.
 """
 from __future__ import annotations

@@ -16,7 +16,7 @@
 // after both networks' steps, and neither network changes in between.
 #include <hip/hip_runtime.h>
 
-#include "f110_internal.h"
+#include "f110_learner_args.h"
 
 namespace f110 {
 

@@ -4,7 +4,16 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
-#include "f110_step_device.h"
+#include "../../include/f110.h"
+#include "f110_beam_runs.h"
+#include "f110_dynamics.h"
+#include "f110_env_rows.h"
+#include "f110_map.h"
+#include "f110_math.h"
+#include "f110_rng.h"
+#include "f110_sincos.h"
+#include "f110_sincos_table.h"
+#include "f110_step_args.h"
 
 namespace f110 {
 
@@ -302,7 +311,7 @@ __global__ void __launch_bounds__(64) k_agents(StepArgs a) {
     aphase(0);
     if (PENV) {
         f110_params lp = a.pa[ag];  // width, length, lidar_max stay the agent's
-        __builtin_memcpy(&lp, pv, kDynFields * sizeof(double));  // the leading doubles (f110_device.h)
+        __builtin_memcpy(&lp, pv, kDynFields * sizeof(double));  // the leading doubles (f110_env_rows.h)
         update_pose(s, b0, b1, cnt, raw_steer, vel, lp, a.dt, a.integrator, tab);
     } else {
         update_pose(s, b0, b1, cnt, raw_steer, vel, a.pa[ag], a.dt, a.integrator, tab);  // RaceCar.params (per agent)

@@ -3,7 +3,15 @@
 // f110_collision_batch, f110_collision_multiple).
 #include <hip/hip_runtime.h>
 
+#include "../../include/f110.h"
+#include "f110_beam_runs.h"
+#include "f110_dynamics.h"
+#include "f110_geometry.h"
+#include "f110_map.h"
+#include "f110_math.h"
+#include "f110_step_args.h"
 #include "f110_step_device.h"
+#include "f110_task_args.h"
 
 namespace f110 {
 

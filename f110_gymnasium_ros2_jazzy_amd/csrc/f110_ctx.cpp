@@ -16,7 +16,17 @@
 #include <string>
 #include <vector>
 
+#include "../../include/f110.h"
+#include "../../include/f110_debug.h"
+#include "f110_beam_runs.h"
 #include "f110_ctx.h"
+#include "f110_env_rows.h"
+#include "f110_host.h"
+#include "f110_host_util.h"
+#include "f110_map.h"
+#include "f110_math.h"
+#include "f110_step_args.h"
+#include "f110_task_args.h"
 
 using namespace f110;
 
@@ -190,7 +200,7 @@ extern "C" int f110_create(f110_ctx **out, int32_t device, const f110_config *cf
         return fail(F110_E_INVALID, "f110_create: fov must be in (0, 2*pi) (one index wrap per scan)");
     if (max_beam_runs((double)C.theta_dis * (C.fov / (double)(C.n_beams - 1)) / (2. * kPi), C.theta_dis) > kMaxSeg)
         return fail(F110_E_INVALID, "f110_create: theta_dis / (fov / n_beams) too large for the beam-index runs "
-                                    "(f110_device.h max_beam_runs <= 80)");
+                                    "(f110_beam_runs.h max_beam_runs <= 80)");
     if (C.ego_idx < 0 || C.ego_idx >= C.n_agents) return fail(F110_E_INVALID, "f110_create: bad ego_idx");
     if (C.integrator != F110_INTEGRATOR_RK4 && C.integrator != F110_INTEGRATOR_EULER)
         return fail(F110_E_INVALID, "f110_create: Invalid Integrator Specified (base_classes.py:399)");

@@ -5,7 +5,10 @@
 #include <string>
 #include <vector>
 
-#include "f110_host.h"
+#include "../../include/f110.h"
+#include "f110_beam_runs.h"
+#include "f110_host_util.h"
+#include "f110_step_args.h"
 
 // The EDT tables (row-major dt, the 4x4-tiled copy, the fixed-point kernel's
 // padded row-major table) are read-only after f110_create.  Contexts on one

@@ -6,7 +6,11 @@
 #include <string>
 #include <vector>
 
+#include "../../include/f110.h"
+#include "../../include/f110_debug.h"
 #include "f110_ctx.h"
+#include "f110_host_util.h"
+#include "f110_step_args.h"
 
 using namespace f110;
 

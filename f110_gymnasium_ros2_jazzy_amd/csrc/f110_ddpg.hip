@@ -22,9 +22,10 @@
 #include <string>
 #include <type_traits>
 
+#include "../../include/f110.h"
+#include "../../include/f110_debug.h"
 #include "f110_head_rows.h"
 #include "f110_host_util.h"
-#include "f110_internal.h"
 
 namespace f110 {
 namespace {
@@ -106,7 +107,7 @@ __global__ void __launch_bounds__(kHB) k_head_fwd(HeadArgs a) {
                         a.out0[row * a.out_stride + j + q] = v;
                     }
                 }
-            } else if (MODE == kExploreEnv) {  // per row: reset, eval or explore (explore_one, f110_device.h)
+            } else if (MODE == kExploreEnv) {  // per row: reset, eval or explore (explore_one, f110_head_rows.h)
                 const double sigma = a.nstate_in[0];
                 const uint64_t step = (uint64_t)a.nstate_in[1];
                 const bool ev = a.eval_mask && a.eval_mask[row] != 0;

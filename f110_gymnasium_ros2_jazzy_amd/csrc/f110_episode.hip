@@ -2,7 +2,7 @@
 // (f110_episode_stats, include/f110.h).  Context-free like f110_reward.hip: it reads a step's
 // rewards and flags, whoever produced them.
 //
-//   k_episode         one thread per env: episode_update (f110_device.h, shared with the host hook),
+//   k_episode         one thread per env: episode_update (f110_env_rows.h, shared with the host hook),
 //                     the per-env outputs, and the block's partial of the envs that finish, reduced
 //                     in LDS as a binary tree over the thread index (a fixed order);
 //   k_episode_finish  one block: the block partials in ascending block order, then into the totals.
@@ -12,7 +12,9 @@
 // the same bits.
 #include <hip/hip_runtime.h>
 
-#include "f110_internal.h"
+#include "../../include/f110.h"
+#include "f110_env_rows.h"
+#include "f110_task_args.h"
 
 namespace f110 {
 

@@ -29,8 +29,8 @@
 #include <algorithm>
 #include <string>
 
+#include "../../include/f110.h"
 #include "f110_host_util.h"
-#include "f110_internal.h"
 
 namespace f110 {
 namespace {

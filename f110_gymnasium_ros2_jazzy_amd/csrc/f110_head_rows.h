@@ -1,7 +1,9 @@
 // f110_head_rows.h — what the learner-head translation units share (private; f110_ddpg.hip,
 // f110_td3.hip and f110_selfplay.hip): the launch geometry of the row-per-half-wave kernels, the row dot product and
-// its backward, the deterministic sums, the exploration draw and the argument checks.  Everything
-// sits in an anonymous namespace: each translation unit gets its own copy, inlined into its kernels.
+// its backward, the deterministic sums, the exploration draw and the argument checks, and ahead of
+// them the row rules that the kernels share with the host hooks of these files (explore_one,
+// td3_smooth_one, td3_row).  All but the row rules sits in an anonymous namespace: each translation
+// unit gets its own copy, inlined into its kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,10 +11,78 @@
 #include <string>
 #include <type_traits>
 
+#include "../../include/f110.h"
 #include "f110_host_util.h"
-#include "f110_internal.h"
+#include "f110_math.h"
+#include "f110_rng.h"
 
 namespace f110 {
+
+// ---------------------------------------------------- exploration head rows --
+// One output of one row of f110_ddpg_actor_explore_env (include/f110.h; k_head_fwd's kExploreEnv
+// epilogue and f110_host_explore_rows both call it): act the deterministic action, n the N(0,1) draw,
+// x the OU state of (row, output) (kind 1; unused for kind 0).  sqdt = sqrt(dt), taken on the host
+// once (np.sqrt(self.dt)).  Returns the action.
+//   reset  zeroes x first, on every row;
+//   eval   the action is act, no draw used, x untouched (agent.py `if not training: return action`);
+//   kind 0 GaussianActionNoise.__call__ (agent.py:520-539) in f32, kExplore's operations;
+//   kind 1 OUActionNoise.__call__ (agent.py:490-505) in f64, left to right, no FMA: the state is
+//          float64 after its first call, the draw a float32 (mu = 0: the first call's float32 drift
+//          is an exact 0 either way).
+constexpr int kExploreGaussian = 0, kExploreOU = 1;
+
+F110_HD float explore_one(int kind, float act, float n, double sigma, double theta, double mu, double dt, double sqdt,
+                          bool reset, bool eval, float lo, float hi, double &x) {
+    if (reset) x = 0.0;
+    if (eval) return act;
+    if (kind == kExploreGaussian) {
+        float v = act + (float)sigma * n;
+        v = v < lo ? lo : v;
+        v = v > hi ? hi : v;
+        return v;
+    }
+    const double dx = theta * (mu - x) * dt + (sigma * sqdt) * (double)n;
+    x = x + dx;
+    return (float)clip((double)act + x, (double)lo, (double)hi);
+}
+
+// ---------------------------------------------------------------- TD3 rows --
+// The two row rules of the TD3 learner (include/f110.h, "TD3 heads"; k_td3_target_action /
+// k_td3_critic_step and f110_host_td3_smooth_rows / f110_host_td3_rows call them).  f32, left to
+// right, no FMA.
+//
+// Target-policy smoothing of one output: act the target actor's action, n the N(0,1) draw,
+// scale_j the actor's half-range 0.5 * (high - low) of this output, so policy_noise and noise_clip
+// are in units of the tanh output (the action box is asymmetric: steer +-0.4189, speed 0..20).
+// NaN stays NaN.
+F110_HD float td3_smooth_one(float act, float n, float policy_noise, float noise_clip, float scale_j, float lo,
+                             float hi) {
+    const float s = policy_noise * scale_j;
+    const float c = noise_clip * scale_j;
+    float e = s * n;
+    e = e < -c ? -c : e;
+    e = e > c ? c : e;
+    float v = act + e;
+    v = v < lo ? lo : v;
+    v = v > hi ? hi : v;
+    return v;
+}
+
+// One row of the twin critic update: clipped double-Q target (torch.minimum of the two target
+// critics, NaN propagates), the two TD errors and their loss gradients (k_critic_step's operations,
+// gb = g / B), the PER priority and the row's loss term.
+F110_HD void td3_row(float r, float d, float gamma, float q1t, float q2t, float q1, float q2, float w, float gb,
+                     float &td1, float &td2, float &dq1, float &dq2, float &prio, float &wl) {
+    const float m = (q2t < q1t || q2t != q2t) ? q2t : q1t;
+    const float y = r + (gamma * (1.0f - d)) * m;
+    td1 = y - q1;
+    td2 = y - q2;
+    dq1 = -((gb * w) * (2.0f * td1));
+    dq2 = -((gb * w) * (2.0f * td2));
+    prio = 0.5f * (fabsf(td1) + fabsf(td2));
+    wl = w * (td1 * td1) + w * (td2 * td2);
+}
+
 namespace {
 
 constexpr int kHB = 256;      // threads per block

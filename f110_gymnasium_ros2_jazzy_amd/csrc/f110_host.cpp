@@ -11,7 +11,19 @@
 #include <string>
 #include <vector>
 
+#include "../../include/f110.h"
+#include "../../include/f110_debug.h"
+#include "f110_beam_runs.h"
+#include "f110_env_rows.h"
+#include "f110_geometry.h"
 #include "f110_host.h"
+#include "f110_host_util.h"
+#include "f110_learner_args.h"
+#include "f110_map.h"
+#include "f110_math.h"
+#include "f110_sincos.h"
+#include "f110_step_args.h"
+#include "f110_task_args.h"
 
 using namespace f110;
 

@@ -6,8 +6,10 @@
 #include <string>
 #include <vector>
 
+#include "../../include/f110.h"
+#include "f110_env_rows.h"
 #include "f110_host_util.h"
-#include "f110_internal.h"
+#include "f110_map.h"
 
 namespace f110 {
 

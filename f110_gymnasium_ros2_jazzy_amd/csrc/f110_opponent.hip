@@ -20,7 +20,8 @@
 // enters its chunk, and each lane then measures the runs that end inside it.
 #include <hip/hip_runtime.h>
 
-#include "f110_internal.h"
+#include "f110_math.h"
+#include "f110_task_args.h"
 
 namespace f110 {
 

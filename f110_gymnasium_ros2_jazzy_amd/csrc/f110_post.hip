@@ -4,6 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include "../../include/f110.h"
+#include "f110_env_rows.h"
+#include "f110_geometry.h"
+#include "f110_math.h"
+#include "f110_sincos.h"
+#include "f110_step_args.h"
 #include "f110_step_device.h"
 
 namespace f110 {

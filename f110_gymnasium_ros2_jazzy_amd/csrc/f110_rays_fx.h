@@ -28,6 +28,8 @@
 // scan pose, speed, noise counter) is wave-uniform and read with scalar loads.
 #pragma once
 
+#include "f110_map.h"
+#include "f110_step_args.h"
 #include "f110_step_device.h"
 
 namespace f110 {
@@ -41,7 +43,7 @@ __device__ __forceinline__ uint32_t dhi(double v) { return (uint32_t)(__double_a
 __device__ __forceinline__ uint32_t dlo(double v) { return (uint32_t)__double_as_longlong(v); }
 
 // The fixed-point loop's EDT: the row-major table of k_rays_fx / k_rays_fxn
-// (FxTable, f110_internal.h), rows of k1 = wt * 8 bytes: row * k1 + col * 8, and off-map
+// (FxTable, f110_step_args.h), rows of k1 = wt * 8 bytes: row * k1 + col * 8, and off-map
 // indices are clamped into the padding, which holds dt[-1,-1], instead of
 // selected.  Measured at 65536 envs: 1.184 vs 1.210 ms for the
 // 4x4-tiled table; an inexact f32 8x4-tiled or u16 8x8-tiled table (4x the

@@ -2,7 +2,14 @@
 // index (f110_rays_fx.h) on one-wave blocks, for masked resets and A/B on axis-aligned maps.
 #include <hip/hip_runtime.h>
 
+#include "../../include/f110_debug.h"
+#include "f110_beam_runs.h"
+#include "f110_map.h"
+#include "f110_math.h"
 #include "f110_rays_fx.h"
+#include "f110_rng.h"
+#include "f110_step_args.h"
+#include "f110_step_device.h"
 
 namespace f110 {
 

@@ -4,7 +4,13 @@
 // the env its leading work items compute the (car, opponent) pair geometry for k_post_multi.
 #include <hip/hip_runtime.h>
 
+#include "../../include/f110.h"
+#include "f110_beam_runs.h"
+#include "f110_math.h"
 #include "f110_rays_fx.h"
+#include "f110_rng.h"
+#include "f110_step_args.h"
+#include "f110_step_device.h"
 
 namespace f110 {
 

@@ -3,6 +3,12 @@
 // scan noise, TTC test, obs / scan outputs.
 #include <hip/hip_runtime.h>
 
+#include "../../include/f110_debug.h"
+#include "f110_beam_runs.h"
+#include "f110_map.h"
+#include "f110_math.h"
+#include "f110_rng.h"
+#include "f110_step_args.h"
 #include "f110_step_device.h"
 
 namespace f110 {

@@ -38,7 +38,8 @@
 
 #include <cfloat>
 
-#include "f110_internal.h"
+#include "f110_learner_args.h"
+#include "f110_rng.h"
 
 namespace f110 {
 
@@ -234,7 +235,7 @@ __global__ void __launch_bounds__(kRB) k_add_copy(ReplayView v, ReplayRows in, i
 }
 
 // ------------------------------------------------------- n-step push -------
-// f110_nstep_push: k_nstep_update (one thread per env: nstep_update, f110_device.h) ->
+// f110_nstep_push: k_nstep_update (one thread per env: nstep_update, f110_learner_args.h) ->
 // k_prio_max -> k_nstep_scan (k_add_scan with a count per env in place of a 0/1 mask) ->
 // k_nstep_copy (one block per (env, emitted row), one more job per env for the window).
 __global__ void __launch_bounds__(kRB) k_nstep_update(NstepView w, NstepRows in) {

@@ -7,7 +7,10 @@
 
 #include <string>
 
+#include "../../include/f110.h"
 #include "f110_host.h"
+#include "f110_host_util.h"
+#include "f110_learner_args.h"
 
 using namespace f110;
 

@@ -19,7 +19,10 @@
 // distance (ties: lower index), the order the candidates are then tried in.
 #include <hip/hip_runtime.h>
 
-#include "f110_internal.h"
+#include "../../include/f110.h"
+#include "f110_math.h"
+#include "f110_sincos.h"
+#include "f110_task_args.h"
 
 namespace f110 {
 

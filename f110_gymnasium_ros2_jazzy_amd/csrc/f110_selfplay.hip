@@ -16,9 +16,11 @@
 #include <string>
 #include <type_traits>
 
+#include "../../include/f110.h"
+#include "f110_env_rows.h"
 #include "f110_head_rows.h"
 #include "f110_host_util.h"
-#include "f110_internal.h"
+#include "f110_step_args.h"
 
 namespace f110 {
 namespace {

@@ -9,13 +9,16 @@
 //  k_post_*    (f110_post.hip) TTC response, obs packing, _check_done.
 //
 // No kernel lives here: each stage's file exports its launcher or its table of instantiations
-// (f110_internal.h).  Measured-slower variants live in git history and DESIGN.md, not here.
+// (f110_step_args.h).  Measured-slower variants live in git history and DESIGN.md, not here.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <cmath>
 
+#include "../../include/f110_debug.h"
+#include "f110_map.h"
+#include "f110_step_args.h"
 #include "f110_step_device.h"
 
 namespace f110 {

@@ -1,14 +1,16 @@
-// f110_internal.h — kernel argument blocks and launchers shared by the .hip
-// files (device) and the host files of the C ABI: f110_host.cpp (pure host
-// code), f110_ctx.cpp / f110_ctx_debug.cpp (the context), f110_task_capi.cpp
-// and f110_replay_capi.cpp (the other handles).  Host-only helpers are in
-// f110_host_util.h (errors, DeviceArena) and f110_host.h.
+// f110_step_args.h — the env step's kernel argument blocks (StepArgs, RayArgs), the fixed-point
+// constants of the ray kernels, the ray launch's plan and the launchers of the step's stages,
+// shared by the step's .hip files (device) and the context (f110_ctx.cpp, f110_step.cpp).
+// Host-only helpers are in f110_host_util.h (errors, DeviceArena) and f110_host.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "f110_device.h"
+#include "../../include/f110.h"
+#include "../../include/f110_debug.h"
+#include "f110_beam_runs.h"
+#include "f110_map.h"
 
 namespace f110 {
 
@@ -257,189 +259,6 @@ struct RayLaunch {
     hipEvent_t gate_record;           //   recorded after it, or null
 };
 
-struct ScanArgs {
-    MapView map;
-    const double *sines, *cosines;
-    int32_t B, theta_dis;
-    double fov, eps, max_range, inc;
-    const double *poses;  // [M][3]
-    int64_t M;
-    double *scans;        // [M][B]
-    int32_t *lookups;     // [M][B] or null
-    int32_t *hit_rc;      // [M][B][2] or null
-    unsigned long long *ctr;
-};
-
-// gap_follow_action over M float32 scans (f110_gap_follow).
-struct GapFollowArgs {
-    const float *scans;   // scan m at scans + m * scan_stride
-    int64_t M, scan_stride, action_stride;
-    float *actions;       // (steer, speed) of scan m at actions + m * action_stride
-    int32_t *gaps;        // [M][2] chosen (start, end) or null
-    double angle_min, angle_increment;
-    int32_t B;
-};
-
-// CenterlineProgress arrays on the device (f110_track).
-struct TrackView {
-    const double *xy;   // [n][2]
-    const double *s;    // [n] arclength
-    const double *tan;  // [n-1][2]
-    const double *nrm;  // [n-1][2]
-    const double *mid;  // [n-1][2] segment midpoints
-    const double *wR, *wL;  // [n] lane widths or null
-    int32_t n, closed;
-    double L;
-    // uniform grid over the midpoints (kd.query acceleration): cell (i, j) of
-    // size gh at (gx0 + i*gh, gy0 + j*gh) holds midpoints cell_items[cell_start[c] ..
-    // cell_start[c+1]), c = j*gnx + i
-    const int32_t *cell_start, *cell_items;
-    const double *cell_mid;  // [n-1][2]: mid[cell_items[q]], in cell order (no indirection)
-    int32_t gnx, gny;
-    double gx0, gy0, gh;
-};
-
-struct RewardArgs {
-    TrackView track;
-    f110_reward_params p;
-    const float *obs;
-    int64_t E;
-    int32_t obs_len, B;
-    f110_reward_state *state;
-    const uint8_t *reset_mask;
-    double *rewards;
-};
-
-// ---- episode statistics (f110_episode.hip) ---------------------------------
-constexpr int kEpisodeBlock = 256;  // envs per block of k_episode (the documented reduction order, f110.h)
-struct EpisodeArgs {
-    const double *rewards;
-    const uint8_t *terminated, *truncated, *was_reset;  // truncated may be null
-    int64_t E;
-    f110_episode_state *state;
-    double *last_return;    // the three per-env outputs may be null
-    int32_t *last_length;
-    uint8_t *finished;
-    f110_episode_totals *totals;
-    EpisodePart *part;      // [episode_blocks(E)] block partials (the caller's scratch)
-};
-inline int64_t episode_blocks(int64_t E) { return (E + kEpisodeBlock - 1) / kEpisodeBlock; }
-hipError_t launch_episode_stats(const EpisodeArgs &a, hipStream_t s);
-
-// ---- prioritized replay (f110_replay.hip) ---------------------------------
-constexpr int kTieCap = 4096;        // keys equal to the selection threshold kept for the tie break
-constexpr int kReplayMaxGrid = 1024; // blocks of the streaming replay kernels
-constexpr int kReplayMaxBatch = 8192;
-// Copies of the radix select's global histograms: block b adds into copy b % kHistRep (consecutive
-// blocks land on different XCDs), so each bin's device-scope atomics are spread over 8 addresses;
-// the consumer sums the copies.  Layout hist[(copy * 4 + pass) * 256 + bin].
-constexpr int kHistRep = 8;
-
-// Device header of a replay buffer (one per f110_replay).
-struct ReplayHdr {
-    int64_t length;     // PrioritizedExperienceReplayBuffer._length
-    int64_t next;       // _next_idx
-    uint64_t draws;     // sample() calls so far (Philox counter)
-    double den;         // sum of (p + eps)^alpha at the last sample
-    int32_t replace;    // the last sample drew with replacement
-    int32_t pad0_;
-    uint32_t prefix;    // radix select: threshold key so far
-    uint32_t kleft;     //   rank still to select below/at the prefix
-    uint32_t n_lt, n_tie;  // keys below / equal to the threshold (n_tie zeroed by k_finish)
-    uint32_t overflow;  // samples whose tie list overflowed kTieCap (k_finish then walks the keys itself)
-    uint32_t pad_;
-    uint32_t sel_prefix[4], sel_kleft[4];  // the select through digit q (written by the kernel after
-                                           // pass q's histogram, read by the next one)
-};
-
-struct ReplayView {
-    ReplayHdr *hdr;
-    int64_t capacity;
-    int32_t obs_dim, act_dim;
-    float *obs, *next_obs, *act, *reward, *done, *prio;  // [cap][D], [cap][D], [cap][A], [cap] x3
-    double *wt;          // [cap] sampling weight (prio + eps)^alpha, written with prio (add, update)
-    uint32_t *keys;      // [cap] exponential-race keys
-    uint32_t *hist;      // [4][256]
-    double *den_part;    // [kReplayMaxGrid]
-    uint32_t *part;      // [kReplayMaxGrid] per-block max priority (add) / selected count (sample)
-    uint64_t *sel;       // [kReplayMaxBatch] indices of the keys below the threshold, in index order
-    uint32_t *tie;       // [kTieCap]
-    int64_t *pos;        // [max rows per add] ring slot of each added row (-1: not stored)
-    double alpha;
-    float eps;           // the buffer's priority_epsilon (replay_buffer.py:24, 88)
-    uint64_t seed;
-};
-
-struct ReplayRows {      // one add(): n transitions (device, f32 rows with strides in floats)
-    const float *obs, *next_obs, *act, *reward;
-    const double *reward64; // [n] f64 rewards instead of reward (rounded to f32 as .to(torch.float32))
-    const float *priority;  // [n] explicit priorities or null (= the max priority)
-    const uint8_t *done;
-    int64_t obs_stride, next_stride, act_stride;
-    int32_t vec4;        // rows 16-B aligned and obs_dim % 4 == 0
-};
-
-struct ReplayBatch {     // one sample(): the gathered batch (device, contiguous)
-    float *obs, *next_obs, *act, *reward, *done;
-    int32_t vec4;
-};
-
-hipError_t launch_replay_add_index(const ReplayView &v, const uint8_t *mask, int mask_skip, const float *priority,
-                                   int64_t n, hipStream_t s);  // ring slots, priorities, header
-hipError_t launch_replay_add_copy(const ReplayView &v, const ReplayRows &in, int64_t n, hipStream_t s);  // the rows
-hipError_t launch_replay_select(const ReplayView &v, int32_t batch, double beta, int64_t *idx, float *w,
-                                bool known_full, hipStream_t s);  // idx / weights (reads no row data)
-hipError_t launch_replay_select_keys(const ReplayView &v, int32_t batch, double beta, int64_t *idx, float *w,
-                                     hipStream_t s);  // the same select over given v.keys (length >= batch)
-hipError_t launch_replay_gather(const ReplayView &v, int32_t batch, const int64_t *idx, const ReplayBatch &out,
-                                hipStream_t s);
-hipError_t launch_replay_update(const ReplayView &v, const int64_t *idx, const float *val, int64_t n, float add_eps,
-                                int32_t from_td, int32_t serial, hipStream_t s);
-hipError_t prepare_replay(int32_t max_batch);
-int replay_grid(int64_t capacity);
-
-// ---- n-step accumulator in front of the ring (f110_replay.hip) -------------
-constexpr int kNstepMax = 16;
-struct NstepView {       // one f110_nstep (device)
-    int64_t n_envs;
-    int32_t n, obs_dim, act_dim;
-    const double *pw;    // [n + 1] gamma^i, sequential products
-    int32_t *len, *head; // [N] pending entries, slot of the oldest
-    double *ret;         // [N][n] running returns
-    int32_t *k;          // [N][n] rewards in ret
-    float *obs, *act;    // [N][n][D], [N][n][A] the pending entries' rows
-    // one push's scratch
-    int32_t *cnt;        // [N] rows the env emits
-    int32_t *store;      // [N] window slot this push's (s, a) goes to, or -1
-    int64_t *base;       // [N] ring slot of the env's first emitted row
-    int32_t *e_slot;     // [N][n] window slot of emitted row j (-1: this push's own row)
-    float *e_reward, *e_done;  // [N][n]
-};
-
-struct NstepRows {       // one push: n_envs raw step outputs (device)
-    const float *obs, *act, *next_obs;
-    const double *reward;
-    const uint8_t *terminated, *truncated, *was_reset;  // truncated may be null
-    int64_t obs_stride, act_stride, next_stride;
-    int32_t vec4;        // every row moved is 16-B aligned and obs_dim % 4 == 0
-};
-
-hipError_t launch_nstep_push(const ReplayView &v, const NstepView &w, const NstepRows &in, hipStream_t s);
-hipError_t launch_nstep_reset(const NstepView &w, const uint8_t *env_mask, hipStream_t s);
-
-// ---- flat Adam (f110_adam.hip) --------------------------------------------
-struct AdamArgs {
-    float *param, *exp_avg, *exp_avg_sq;
-    const float *grad;
-    int64_t n;
-    double lr, beta1, beta2, eps;
-    int64_t *step;     // device step counter
-    uint32_t *done;    // device: blocks finished (last one advances step)
-    float *target;     // the target network's flat buffer (soft update after the step) or null
-    float tau;
-};
-hipError_t launch_adam(const AdamArgs &a, hipStream_t s);
-
 // ---- the env step (f110_step.cpp) and its stages, one translation unit each --------------------
 hipError_t launch_env_step(const StepArgs &a, const RayLaunch &r, hipStream_t s,
                            hipEvent_t *ev = nullptr);  // ev: 6 events or null
@@ -453,17 +272,5 @@ using RayKernel = void (*)(RayArgs);
 RayKernel tiled_ray_kernel(const RayPlan &p);  // f110_rays_tiled.hip
 RayKernel fx_ray_kernel(const RayPlan &p);     // f110_rays_fx.hip: k_rays_fx, k_rays_fxn
 RayKernel fxs_ray_kernel(const RayPlan &p);    // f110_rays_fxs.hip
-// ---- the C-ABI batch kernels (f110_batch.hip) and the task kernels ----------------------------
-hipError_t launch_scan_batch(const ScanArgs &a, hipStream_t s);
-hipError_t launch_gap_follow(const GapFollowArgs &a, hipStream_t s);
-hipError_t launch_reward(const RewardArgs &a, hipStream_t s);
-size_t gap_follow_lds_bytes(int B);
-hipError_t launch_dynamics_ks_batch(const double *x, const double *u, double *f, int64_t M, const f110_params &p,
-                                    hipStream_t s);
-hipError_t launch_collision_batch(const double *v1, const double *v2, int64_t M, uint8_t *out, hipStream_t s);
-hipError_t launch_collision_multiple(const double *verts, int64_t M, int32_t N, double *collisions, double *idx,
-                                     hipStream_t s);
-hipError_t launch_dynamics_batch(const double *x, const double *u, double *f, int64_t M, const f110_params &p,
-                                 hipStream_t s);
 
 }  // namespace f110

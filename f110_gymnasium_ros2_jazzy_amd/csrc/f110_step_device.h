@@ -6,7 +6,11 @@
 
 #include <hip/hip_runtime.h>
 
-#include "f110_internal.h"
+#include "f110_beam_runs.h"
+#include "f110_env_rows.h"
+#include "f110_geometry.h"
+#include "f110_sincos.h"
+#include "f110_step_args.h"
 
 namespace f110 {
 
@@ -38,7 +42,7 @@ __host__ __device__ __forceinline__ int64_t obs_row(const StepArgs &a) {
 }
 
 // F110Env._pack_flat_obs's scan entry (f110_env.py:557-560): f32, NaN ->
-// lidar_max, +-inf -> lidar_max / 0, clip, / lidar_max in f32 (the f32 part: f110_device.h).
+// lidar_max, +-inf -> lidar_max / 0, clip, / lidar_max in f32 (the f32 part: f110_env_rows.h).
 __device__ __forceinline__ float obs_scan_value(double r, float lmax) { return obs_scan_value((float)r, lmax); }
 
 // check_ttc_jit's per-beam test (laser_models.py:188-217):

@@ -1,0 +1,97 @@
+// f110_task_args.h — the argument blocks and launchers of the kernels beside the env step: the
+// C-ABI batch kernels, gap-follow, the track and the reward, the episode statistics.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/f110.h"
+#include "f110_env_rows.h"
+#include "f110_map.h"
+
+namespace f110 {
+
+struct ScanArgs {
+    MapView map;
+    const double *sines, *cosines;
+    int32_t B, theta_dis;
+    double fov, eps, max_range, inc;
+    const double *poses;  // [M][3]
+    int64_t M;
+    double *scans;        // [M][B]
+    int32_t *lookups;     // [M][B] or null
+    int32_t *hit_rc;      // [M][B][2] or null
+    unsigned long long *ctr;
+};
+
+// gap_follow_action over M float32 scans (f110_gap_follow).
+struct GapFollowArgs {
+    const float *scans;   // scan m at scans + m * scan_stride
+    int64_t M, scan_stride, action_stride;
+    float *actions;       // (steer, speed) of scan m at actions + m * action_stride
+    int32_t *gaps;        // [M][2] chosen (start, end) or null
+    double angle_min, angle_increment;
+    int32_t B;
+};
+
+// CenterlineProgress arrays on the device (f110_track).
+struct TrackView {
+    const double *xy;   // [n][2]
+    const double *s;    // [n] arclength
+    const double *tan;  // [n-1][2]
+    const double *nrm;  // [n-1][2]
+    const double *mid;  // [n-1][2] segment midpoints
+    const double *wR, *wL;  // [n] lane widths or null
+    int32_t n, closed;
+    double L;
+    // uniform grid over the midpoints (kd.query acceleration): cell (i, j) of
+    // size gh at (gx0 + i*gh, gy0 + j*gh) holds midpoints cell_items[cell_start[c] ..
+    // cell_start[c+1]), c = j*gnx + i
+    const int32_t *cell_start, *cell_items;
+    const double *cell_mid;  // [n-1][2]: mid[cell_items[q]], in cell order (no indirection)
+    int32_t gnx, gny;
+    double gx0, gy0, gh;
+};
+
+struct RewardArgs {
+    TrackView track;
+    f110_reward_params p;
+    const float *obs;
+    int64_t E;
+    int32_t obs_len, B;
+    f110_reward_state *state;
+    const uint8_t *reset_mask;
+    double *rewards;
+};
+
+// ---- episode statistics (f110_episode.hip) ---------------------------------
+constexpr int kEpisodeBlock = 256;  // envs per block of k_episode (the documented reduction order, f110.h)
+struct EpisodeArgs {
+    const double *rewards;
+    const uint8_t *terminated, *truncated, *was_reset;  // truncated may be null
+    int64_t E;
+    f110_episode_state *state;
+    double *last_return;    // the three per-env outputs may be null
+    int32_t *last_length;
+    uint8_t *finished;
+    f110_episode_totals *totals;
+    EpisodePart *part;      // [episode_blocks(E)] block partials (the caller's scratch)
+};
+inline int64_t episode_blocks(int64_t E) { return (E + kEpisodeBlock - 1) / kEpisodeBlock; }
+hipError_t launch_episode_stats(const EpisodeArgs &a, hipStream_t s);
+
+// ---- the C-ABI batch kernels (f110_batch.hip) and the task kernels ----------------------------
+hipError_t launch_scan_batch(const ScanArgs &a, hipStream_t s);
+hipError_t launch_gap_follow(const GapFollowArgs &a, hipStream_t s);
+hipError_t launch_reward(const RewardArgs &a, hipStream_t s);
+size_t gap_follow_lds_bytes(int B);
+hipError_t launch_dynamics_ks_batch(const double *x, const double *u, double *f, int64_t M, const f110_params &p,
+                                    hipStream_t s);
+hipError_t launch_collision_batch(const double *v1, const double *v2, int64_t M, uint8_t *out, hipStream_t s);
+hipError_t launch_collision_multiple(const double *verts, int64_t M, int32_t N, double *collisions, double *idx,
+                                     hipStream_t s);
+hipError_t launch_dynamics_batch(const double *x, const double *u, double *f, int64_t M, const f110_params &p,
+                                 hipStream_t s);
+
+}  // namespace f110

@@ -8,7 +8,12 @@
 #include <string>
 #include <vector>
 
+#include "../../include/f110.h"
+#include "f110_env_rows.h"
 #include "f110_host.h"
+#include "f110_host_util.h"
+#include "f110_step_args.h"
+#include "f110_task_args.h"
 
 using namespace f110;
 

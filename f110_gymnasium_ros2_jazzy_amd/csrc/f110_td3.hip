@@ -2,12 +2,15 @@
 // layer with target-policy smoothing, and the twin critics' TD-target / loss / backward head in
 // one launch.  Same launch shape as f110_ddpg.hip's heads (f110_head_rows.h: one row per
 // half-wave, the epilogue in registers, deterministic block sums); the per-row arithmetic is
-// td3_smooth_one / td3_row (f110_device.h), which the host hooks of this file run too.
+// td3_smooth_one / td3_row (f110_head_rows.h), which the host hooks of this file run too.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
+#include "../../include/f110.h"
+#include "../../include/f110_debug.h"
 #include "f110_head_rows.h"
+#include "f110_host_util.h"
 
 namespace f110 {
 namespace {

@@ -269,7 +269,7 @@ F110_API int f110_host_episode_stats(const double *rewards, const uint8_t *termi
                                      f110_episode_totals *totals);
 
 /* f110_ddpg_actor_explore_env's per-row epilogue over HOST arrays: the same function the kernel runs
- * (explore_one, csrc/f110_device.h), on given actions act [n_rows][nout] f32 (f110_ddpg_actor_head's
+ * (explore_one, csrc/f110_head_rows.h), on given actions act [n_rows][nout] f32 (f110_ddpg_actor_head's
  * act) and given draws normals [n_rows][nout] f32.  ou_x, reset, eval_mask, kind, theta / mu / dt,
  * low / high, the {sigma, call index} pair state_in and decay / sigma_min as there; writes out
  * [n_rows][nout] (packed), updates ou_x and, when state_out is not NULL, writes the decayed pair.
@@ -282,7 +282,7 @@ F110_API int f110_host_explore_rows(const float *act, const float *normals, int6
                                     const float *high, float *out);
 
 /* The TD3 heads' row rules over HOST arrays: the same functions the kernels run (td3_smooth_one,
- * td3_row, csrc/f110_device.h).  f110_host_td3_smooth_rows: f110_td3_target_action's epilogue on
+ * td3_row, csrc/f110_head_rows.h).  f110_host_td3_smooth_rows: f110_td3_target_action's epilogue on
  * given actions act and draws normals ([n_rows][nout] f32), scale / low / high [nout]; writes out
  * [n_rows][nout].  f110_host_td3_rows: f110_td3_critic_step's row rule on given head outputs q1t,
  * q2t, q1, q2 and r, d, w ([B] f32), g the loss gradient (a host scalar; gb = g / B); writes td1,
@@ -297,7 +297,7 @@ F110_API int f110_host_td3_rows(const float *r, const float *d, float gamma, con
                                 float *td2, float *dq1, float *dq2, float *prio, float *wl);
 
 /* One f110_nstep_push over HOST arrays: the same per-env function the kernel runs (nstep_update,
- * csrc/f110_device.h), envs in ascending order.  len / head [n_envs], ret / k [n_envs][n_step],
+ * csrc/f110_learner_args.h), envs in ascending order.  len / head [n_envs], ret / k [n_envs][n_step],
  * win_obs [n_envs][n_step][obs_dim] and win_act [n_envs][n_step][act_dim] are the windows
  * (f110_nstep_arrays' layout; zero = fresh), updated in place; obs / act / next_obs are packed
  * rows.  Writes the emitted rows, in the order the device appends them, to out_obs / out_next_obs
@@ -313,7 +313,7 @@ F110_API int f110_host_nstep(int64_t n_envs, int32_t n_step, double gamma, int32
                              float *out_next_obs, float *out_done, int64_t *out_count);
 
 /* f110_agent_obs over HOST arrays (same arguments, no stream): the same scan entry the kernels run
- * (obs_scan_value, csrc/f110_device.h) and the same pose-group order.  Same validation
+ * (obs_scan_value, csrc/f110_env_rows.h) and the same pose-group order.  Same validation
  * (F110_E_INVALID).  Host test hook: the CPU suite and the GPU tests share one statement of the
  * semantics. */
 F110_API int f110_host_agent_obs(const float *scans, int64_t scan_env_stride, const float *obs, int64_t obs_stride,

@@ -8,7 +8,10 @@ device function has no such record and may exist once per file: its line ends wi
 With two file lists (separated by --) the kernels whose lines differ are printed, then the counts.
 
     python scripts/kernel_digests.py csrc/f110_post.hip
-    python scripts/kernel_digests.py old/csrc/f110_kernels.hip -- csrc/f110_agents.hip csrc/f110_post.hip
+    python scripts/kernel_digests.py parent/csrc/*.hip -- csrc/*.hip
+
+The second form, over a checkout of the parent commit and this tree, is the proof that a change of
+the headers alone (moving text between csrc/*.h, changing includes) left every kernel as it was.
 """
 import hashlib
 import os

@@ -10,6 +10,8 @@
 #include <vector>
 
 #include "../../f110_gymnasium_ros2_jazzy_amd/csrc/f110_host.h"
+#include "../../include/f110.h"
+#include "../../include/f110_debug.h"
 
 using namespace f110;
 

@@ -240,7 +240,7 @@ def test_create_validates_without_gpu(L):
                        origin, None, 0)
     assert rc == -1
     # a scan so fine against theta_dis that its beam-index runs could overflow the 80-run table
-    # (f110_device.h max_beam_runs): rejected before any device call
+    # (f110_beam_runs.h max_beam_runs): rejected before any device call
     c.fov, c.theta_dis, c.n_beams = 0.001, 2, 2048
     rc = L.f110_create(ctypes.byref(ctx), 0, ctypes.byref(c), ctypes.byref(p), k.ctypes.data, 4, 4, 0.05,
                        origin, None, 0)
@@ -352,7 +352,7 @@ def test_window_ranges_contain_window_beams():
 
 
 def test_np_float32_sincos_matches_numpy():
-    """The device's float32 start_rot trig (f110_device.h np_sincosf,
+    """The device's float32 start_rot trig (f110_sincos.h np_sincosf,
     F110Env.reset with float32 options, f110_env.py:448-451) against the
     installed NumPy's float32 np.cos / np.sin, bit for bit: yaw range, wider
     arguments, quadrant boundaries, signed zeros, NaN."""
@@ -392,7 +392,7 @@ def _dec_sincos(v):
 
 
 def test_cr_sincos_matches_numpy():
-    """f110_device.h cr_sincos (the ray_cast beam direction, box vertices,
+    """f110_sincos.h cr_sincos (the ray_cast beam direction, box vertices,
     dynamics and start_rot sin / cos, double-double + one rounding) against
     NumPy's float64 np.sin / np.cos (glibc here), the reference's own trig:
     bit-exact but on a small rest (< 0.3 % of arguments over scan / yaw
@@ -593,14 +593,17 @@ def test_ray_size_rules(L, own, device, contexts, kernel, pad, want):
 
 def test_sources_on_disk_and_launchers_defined_once():
     """_build.SOURCES is exactly the csrc/*.hip and csrc/*.cpp on disk, and every launch_* /
-    *_ray_kernel that f110_internal.h declares is defined in exactly one of them (a text scan: a
+    *_ray_kernel that a csrc/*.h declares is defined in exactly one of them (a text scan: a
     definition is the name at the start of a line's declarator followed by its body's brace)."""
     from f110_gymnasium_ros2_jazzy_amd import _build
 
     on_disk = sorted(f for f in os.listdir(_build.CSRC) if f.endswith((".hip", ".cpp")))
     assert sorted(_build.SOURCES) == on_disk
-    with open(os.path.join(_build.CSRC, "f110_internal.h")) as fh:
-        names = sorted(set(re.findall(r"\b(launch_\w+|\w+_ray_kernel)\s*\(", fh.read())))
+    names = set()
+    for h in sorted(f for f in os.listdir(_build.CSRC) if f.endswith(".h")):
+        with open(os.path.join(_build.CSRC, h)) as fh:
+            names |= set(re.findall(r"\b(launch_\w+|\w+_ray_kernel)\s*\(", fh.read()))
+    names = sorted(names)
     assert len(names) >= 20 and {"launch_agents", "launch_post", "launch_env_step", "fxs_ray_kernel"} <= set(names)
     text = {}
     for f in on_disk:
@@ -609,3 +612,28 @@ def test_sources_on_disk_and_launchers_defined_once():
     for n in names:
         defined = [f for f, t in text.items() if re.search(r"^[A-Za-z_][\w:<> \*&]*\b%s\s*\([^;{]*\)\s*\{" % n, t, re.M)]
         assert len(defined) == 1, (n, defined)
+
+
+def test_every_header_compiles_on_its_own():
+    """Each csrc/*.h includes what it uses: hipcc parses it alone (-fsyntax-only, the package's
+    offload arch) with exit status 0."""
+    import subprocess
+    from concurrent.futures import ThreadPoolExecutor
+
+    from f110_gymnasium_ros2_jazzy_amd import _build
+
+    try:
+        hipcc = _build.hipcc()
+    except RuntimeError:
+        pytest.skip("no hipcc (the library could not be built either)")
+    headers = sorted(f for f in os.listdir(_build.CSRC) if f.endswith(".h"))
+    assert len(headers) >= 15
+
+    def check(h):
+        r = subprocess.run([hipcc, "-std=c++17", "-x", "hip", "-fsyntax-only", f"--offload-arch={_build.ARCH}",
+                            os.path.join(_build.CSRC, h)], capture_output=True, text=True)
+        return h, r.returncode, r.stderr
+
+    with ThreadPoolExecutor(max_workers=4) as pool:
+        failed = [(h, err) for h, rc, err in pool.map(check, headers) if rc != 0]
+    assert not failed, failed

@@ -2,7 +2,7 @@
 F110Env._pack_flat_obs divides the clipped float32 scan by lidar_max in
 float32 (f110_env.py:557-560).  The kernel computes q = v * y, r = fma(-q,
 lm, v), q' = fma(r, y, q) with y = RN(1 / lm) (obs_reciprocal,
-f110_internal.h) and takes the IEEE divide for v < 2^-60 or lm outside
+f110_step_args.h) and takes the IEEE divide for v < 2^-60 or lm outside
 [2^-30, 2^30].  Here the same formula, compiled with gcc (fmaf is correctly
 rounded), is compared with the IEEE divide for EVERY float32 v in
 [2^-60, lm] at the reference's lidar_max = 30 (f110_env.py:156), and on a
