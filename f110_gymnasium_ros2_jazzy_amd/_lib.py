@@ -47,6 +47,11 @@ class F110RewardParams(ctypes.Structure):
                                              "use_progress")]
 
 
+class F110PursuitParams(ctypes.Structure):  # f110_pursuit_params
+    _fields_ = [(n, ctypes.c_double) for n in ("lookahead", "wheelbase", "speed", "a_lat", "v_floor", "steer_limit")] + \
+               [("direction", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
 class F110GemmOp(ctypes.Structure):  # f110_gemm_op
     _fields_ = [(n, _P) for n in ("A", "B", "bias", "amask", "omask", "x2", "w2", "C")] + \
                [(n, ctypes.c_int32) for n in ("N", "K", "lda", "ldb", "ldc", "ldx2", "ldw2", "nx2", "relu", "nn")]
@@ -224,6 +229,9 @@ _API = {
     "f110_agent_obs": (_i, [_P, _i64, _P, _i64, _i64, _i32, _i32, _i32, _f32, _P, _i64, _P]),
     "f110_policy_head_rows": (_i, [_P] * 5 + [_i64, _i32, _i32, _P, _P, _i64, _P]),
     "f110_host_agent_obs": (_i, [_P, _i64, _P, _i64, _i64, _i32, _i32, _i32, _f32, _P, _i64]),
+    "f110_default_pursuit_params": (None, [ctypes.POINTER(F110PursuitParams)]),
+    "f110_pure_pursuit": (_i, [_P, ctypes.POINTER(F110PursuitParams), _P, _i64, _i64, _P, _P, _P, _i64, _P, _P]),
+    "f110_host_pure_pursuit": (_i, [_P, ctypes.POINTER(F110PursuitParams), _P, _i64, _i64, _P, _P, _P, _i64, _P]),
 }
 EXPORTS = list(_API)
 

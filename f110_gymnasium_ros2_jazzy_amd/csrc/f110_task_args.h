@@ -1,5 +1,6 @@
 // f110_task_args.h — the argument blocks and launchers of the kernels beside the env step: the
-// C-ABI batch kernels, gap-follow, the track and the reward, the episode statistics.
+// C-ABI batch kernels, gap-follow, the track, the reward and the pure-pursuit opponent, the episode
+// statistics.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -65,6 +66,18 @@ struct RewardArgs {
     double *rewards;
 };
 
+// f110_pure_pursuit over M cars (k_pursuit, f110_pursuit.hip).
+struct PursuitArgs {
+    TrackView track;
+    f110_pursuit_params p;
+    const float *poses;        // (x, y, yaw) of row m at poses + m * pose_stride
+    int64_t M, pose_stride, action_stride;
+    const double *row_speed;   // [M] or null
+    const uint8_t *row_mask;   // [M] or null: rows with 0 keep their bytes
+    float *actions;            // (steer, speed) of row m at actions + m * action_stride
+    double *aux;               // [M][4] s_proj, t, target x, y, or null
+};
+
 // ---- episode statistics (f110_episode.hip) ---------------------------------
 constexpr int kEpisodeBlock = 256;  // envs per block of k_episode (the documented reduction order, f110.h)
 struct EpisodeArgs {
@@ -85,6 +98,7 @@ hipError_t launch_episode_stats(const EpisodeArgs &a, hipStream_t s);
 hipError_t launch_scan_batch(const ScanArgs &a, hipStream_t s);
 hipError_t launch_gap_follow(const GapFollowArgs &a, hipStream_t s);
 hipError_t launch_reward(const RewardArgs &a, hipStream_t s);
+hipError_t launch_pursuit(const PursuitArgs &a, hipStream_t s);
 size_t gap_follow_lds_bytes(int B);
 hipError_t launch_dynamics_ks_batch(const double *x, const double *u, double *f, int64_t M, const f110_params &p,
                                     hipStream_t s);

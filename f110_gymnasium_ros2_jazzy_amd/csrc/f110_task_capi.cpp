@@ -1,17 +1,22 @@
 // f110_task_capi.cpp — the context-free training entry points of include/f110.h: the track of the
-// progress reward (f110_track_*), f110_reward, f110_gap_follow, the collision batches and the
-// episode statistics.  Argument checks and launches; the kernels are in f110_reward.hip,
-// f110_opponent.hip, f110_batch.hip and f110_episode.hip.
+// progress reward (f110_track_*), f110_reward, f110_gap_follow, f110_pure_pursuit with its host
+// statement, the collision batches and the episode statistics.  Argument checks and launches; the
+// kernels are in f110_reward.hip, f110_opponent.hip, f110_pursuit.hip, f110_batch.hip and
+// f110_episode.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <limits>
 #include <string>
 #include <vector>
 
 #include "../../include/f110.h"
+#include "../../include/f110_debug.h"
 #include "f110_env_rows.h"
 #include "f110_host.h"
 #include "f110_host_util.h"
+#include "f110_pursuit.h"
 #include "f110_step_args.h"
 #include "f110_task_args.h"
 
@@ -21,7 +26,7 @@ using namespace f110;
 struct f110_track {
     DeviceArena arena;  // empty for a host-only track
     TrackView v{};
-    std::vector<double> s, tan, nrm, mid;
+    std::vector<double> xy, s, tan, nrm, mid;  // host copies (f110_track_arrays, f110_host_pure_pursuit)
 };
 
 extern "C" int f110_track_create(f110_track **out, int32_t device, const double *xy, const double *w_right,
@@ -33,6 +38,7 @@ extern "C" int f110_track_create(f110_track **out, int32_t device, const double 
         return fail(F110_E_NODEVICE, "f110_track_create: no such HIP device");
     auto *t = new f110_track();
     t->arena.device = device;
+    t->xy.assign(xy, xy + 2 * (size_t)n);
     track_arrays(xy, n, t->s, t->tan, t->nrm, t->mid);
     if (!host_only) {
         const TrackGrid g = track_grid(xy, n, t->mid);
@@ -100,6 +106,156 @@ extern "C" int f110_reward(const f110_track *track, const f110_reward_params *pa
     a.reset_mask = reset_mask;
     a.rewards = rewards;
     HIP_TRY(launch_reward(a, (hipStream_t)stream));
+    return F110_OK;
+}
+
+// ---- pure-pursuit opponent (f110_pursuit.hip; the row rule: f110_pursuit.h) ------------------
+extern "C" void f110_default_pursuit_params(f110_pursuit_params *p) {
+    if (!p) return;
+    f110_params car;
+    f110_default_params(&car);
+    *p = f110_pursuit_params{};
+    p->lookahead = 1.2;
+    p->wheelbase = car.lf + car.lr;
+    p->speed = 4.0;
+    p->a_lat = 0.0;
+    p->v_floor = 1.0;
+    p->steer_limit = 0.4189;
+    p->direction = 1;
+}
+
+extern "C" int f110_pure_pursuit(const f110_track *track, const f110_pursuit_params *params, const float *poses,
+                                 int64_t n_rows, int64_t pose_stride, const double *row_speed,
+                                 const uint8_t *row_mask, float *actions, int64_t action_stride, double *aux,
+                                 void *stream) {
+    if (!track || pursuit_bad_args(params, track->v.L, poses, n_rows, pose_stride, actions, action_stride))
+        return fail(F110_E_INVALID, "f110_pure_pursuit: bad arguments (0 < lookahead < L, wheelbase and steer_limit "
+                                    "> 0, speed and a_lat >= 0, direction +-1, pose_stride >= 3, action_stride >= 2)");
+    if (!track->v.mid) return fail(F110_E_INVALID, "f110_pure_pursuit: needs a device track");
+    PursuitArgs a{};
+    a.track = track->v;
+    a.p = *params;
+    a.poses = poses;
+    a.M = n_rows;
+    a.pose_stride = pose_stride;
+    a.action_stride = action_stride;
+    a.row_speed = row_speed;
+    a.row_mask = row_mask;
+    a.actions = actions;
+    a.aux = aux;
+    HIP_TRY(launch_pursuit(a, (hipStream_t)stream));
+    return F110_OK;
+}
+
+namespace {
+
+struct HostProj {
+    double s, t;
+};
+
+// CenterlineProgress.project_xy (track_progress.py:58-97) over host arrays: the 5 midpoints of
+// smallest squared distance by a full scan (ties: lower index), then project_xy's operations
+// (f110_track_device.h) one for one.
+HostProj host_project_xy(const TrackView &T, double x, double y) {
+    constexpr int kTop5 = 5;
+    double bd[kTop5];
+    int32_t bi[kTop5];
+    int have5 = 0;
+    for (int32_t m = 0; m < T.n - 1; ++m) {
+        const double dx = T.mid[2 * m] - x, dy = T.mid[2 * m + 1] - y;
+        const double d2 = dx * dx + dy * dy;
+        int k = have5;  // ascending index: an equal distance stays behind the earlier one
+        while (k > 0 && d2 < bd[k - 1]) --k;
+        if (k >= kTop5) continue;
+        for (int j = std::min(have5, kTop5 - 1); j > k; --j) {
+            bd[j] = bd[j - 1];
+            bi[j] = bi[j - 1];
+        }
+        bd[k] = d2;
+        bi[k] = m;
+        if (have5 < kTop5) ++have5;
+    }
+    auto bdot = [](double a0, double a1, double b0, double b1) { return std::fma(a1, b1, a0 * b0); };
+    bool have = false;
+    double bn = 0.0, bs = 0.0, bt = 0.0;
+    for (int r = 0; r < have5; ++r) {
+        const int32_t idx = bi[r];
+        const double a0 = T.xy[2 * idx], a1 = T.xy[2 * idx + 1];
+        const double ab0 = T.xy[2 * idx + 2] - a0, ab1 = T.xy[2 * idx + 3] - a1;
+        const double L2 = bdot(ab0, ab1, ab0, ab1);
+        if (L2 <= 1e-12) continue;
+        const double ap0 = x - a0, ap1 = y - a1;
+        double tp = bdot(ap0, ap1, ab0, ab1) / L2;
+        tp = tp < 0.0 ? 0.0 : (tp > 1.0 ? 1.0 : tp);
+        const double pr0 = a0 + tp * ab0, pr1 = a1 + tp * ab1;
+        const double s_proj = T.s[idx] + tp * std::sqrt(L2);
+        const double d0 = x - pr0, d1 = y - pr1;
+        const double t_signed = bdot(d0, d1, T.nrm[2 * idx], T.nrm[2 * idx + 1]);
+        const double nrm = std::sqrt(bdot(d0, d1, d0, d1));
+        if (!have || nrm < bn) {
+            have = true;
+            bn = nrm;
+            bs = s_proj;
+            bt = t_signed;
+        }
+    }
+    if (!have) {  // degenerate fallback: nearest node (:93-95)
+        double best = INFINITY;
+        int32_t bj = 0;
+        for (int32_t j = 0; j < T.n; ++j) {
+            const double d0 = T.xy[2 * j] - x, d1 = T.xy[2 * j + 1] - y;
+            const double d = std::sqrt(d0 * d0 + d1 * d1);
+            if (d < best) {
+                best = d;
+                bj = j;
+            }
+        }
+        return HostProj{T.s[bj], 0.0};
+    }
+    return HostProj{bs, bt};
+}
+
+}  // namespace
+
+extern "C" int f110_host_pure_pursuit(const f110_track *track, const f110_pursuit_params *params, const float *poses,
+                                      int64_t n_rows, int64_t pose_stride, const double *row_speed,
+                                      const uint8_t *row_mask, float *actions, int64_t action_stride, double *aux) {
+    if (!track || pursuit_bad_args(params, track->v.L, poses, n_rows, pose_stride, actions, action_stride))
+        return fail(F110_E_INVALID, "f110_host_pure_pursuit: bad arguments (0 < lookahead < L, wheelbase and "
+                                    "steer_limit > 0, speed and a_lat >= 0, direction +-1, pose_stride >= 3, "
+                                    "action_stride >= 2)");
+    TrackView T = track->v;  // n, closed, L; the arrays on the host
+    T.xy = track->xy.data();
+    T.s = track->s.data();
+    T.nrm = track->nrm.data();
+    T.mid = track->mid.data();
+    const f110_pursuit_params &P = *params;
+    for (int64_t m = 0; m < n_rows; ++m) {
+        if (row_mask && row_mask[m] == 0) continue;
+        const float *p = poses + m * pose_stride;
+        const double x = (double)p[0], y = (double)p[1], yaw = (double)p[2];
+        float *act = actions + m * action_stride;
+        double *ax = aux ? aux + 4 * m : nullptr;
+        if (!(std::isfinite(x) && std::isfinite(y) && std::isfinite(yaw))) {
+            act[0] = act[1] = 0.0f;
+            if (ax) ax[0] = ax[1] = ax[2] = ax[3] = std::numeric_limits<double>::quiet_NaN();
+            continue;
+        }
+        const HostProj pj = host_project_xy(T, x, y);
+        const double sq = pursuit_query(P, pj.s, T.closed, T.L);
+        // np.searchsorted(s, sq, side="right") - 1 clipped to [0, n-2]
+        int64_t i = (std::upper_bound(T.s, T.s + T.n, sq) - T.s) - 1;
+        i = std::max<int64_t>(0, std::min<int64_t>(i, T.n - 2));
+        const PursuitAction r = pursuit_action(P, T.xy, T.s, (int32_t)i, sq, x, y, yaw, row_speed ? row_speed[m] : P.speed);
+        act[0] = (float)r.steer;
+        act[1] = (float)r.v;
+        if (ax) {
+            ax[0] = pj.s;
+            ax[1] = pj.t + 0.0;  // (a zero as +0, as the kernel writes it)
+            ax[2] = r.tx;
+            ax[3] = r.ty;
+        }
+    }
     return F110_OK;
 }
 

@@ -6,6 +6,11 @@ reference's NumPy float32 arithmetic.  train_ddpg.py:168 computes it on the
 host from the previous step's info["scans"][1];
 F110VectorEnv(opponent="gap_follow") keeps that loop on the GPU.
 
+``pure_pursuit`` is the other rule: a waypoint follower on a CenterlineTrack (f110_pure_pursuit; no
+reference counterpart), each car aiming one lookahead ahead of its projection onto the centerline;
+``host_pure_pursuit`` is its host statement over NumPy arrays.
+F110VectorEnv(opponent="pure_pursuit") runs it on the opponent's pose group of every step's obs.
+
 Self-play (no reference counterpart): ``agent_obs`` packs the flat observation
 from any agent's seat (f110_agent_obs), ``PolicyOpponent`` holds a frozen copy
 of an Actor and writes its actions into the opponent's rows of the env's action
@@ -50,9 +55,99 @@ def gap_follow(scans: torch.Tensor, out: torch.Tensor | None = None, angle_min: 
     return (out, gaps) if return_gaps else out
 
 
-# ---------------------------------------------------------------- self-play --
 def _vp(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+# ------------------------------------------------------------- pure pursuit --
+PURSUIT_FIELDS = ("lookahead", "wheelbase", "speed", "a_lat", "v_floor", "steer_limit", "direction")
+
+
+def pursuit_params(**params) -> "_lib.F110PursuitParams":
+    """f110_default_pursuit_params with ``params`` (lookahead, wheelbase, speed, a_lat, v_floor,
+    steer_limit, direction) on top; an unknown name is a ValueError.  The values themselves are
+    checked by the library at the call."""
+    p = _lib.F110PursuitParams()
+    _lib.load().f110_default_pursuit_params(ctypes.byref(p))
+    for k, v in params.items():
+        if k not in PURSUIT_FIELDS:
+            raise ValueError(f"unknown pure-pursuit parameter {k!r} (known: {', '.join(PURSUIT_FIELDS)})")
+        if k == "direction":
+            if v not in (1, -1):
+                raise ValueError(f"direction must be +1 or -1; got {v!r}")
+            p.direction = int(v)
+        else:
+            setattr(p, k, float(v))
+    return p
+
+
+def pure_pursuit(poses: torch.Tensor, track, out: torch.Tensor | None = None, row_speed: torch.Tensor | None = None,
+                 row_mask: torch.Tensor | None = None, return_aux: bool = False, stream=None, **params):
+    """Pure-pursuit actions for M cars (f110_pure_pursuit).  poses: float32 device tensor [M, >= 3]
+    whose rows start with (x, y, yaw) (rows may be strided, e.g. ``obs[:, B + 4:B + 8]``, agent 1's
+    pose group of a step's obs); track: a device reward.CenterlineTrack.  Returns actions [M, 2]
+    float32 (steer, speed), written into ``out`` if given (rows may be strided, e.g. ``act[:, 1]`` of
+    an [M, A, 2] action buffer), plus aux [M, 4] float64 (s_proj, t, target x, y) when
+    ``return_aux``.  row_speed: float64 [M] per-row speeds (None: ``speed`` for all); row_mask:
+    uint8 [M], rows with 0 keep their values (None: every row); params: see pursuit_params."""
+    if (poses.dim() != 2 or poses.dtype != torch.float32 or poses.device.type != "cuda" or poses.shape[1] < 3
+            or poses.stride(1) != 1):
+        raise ValueError("poses must be a float32 cuda tensor [M, >= 3] with unit stride along the pose")
+    M = poses.shape[0]
+    if getattr(track, "device", None) != poses.device or not getattr(track, "handle", None):
+        raise ValueError("track must be an open reward.CenterlineTrack on the poses' device")
+    if out is None:
+        out = torch.empty(M, 2, dtype=torch.float32, device=poses.device)
+    if out.shape != (M, 2) or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != poses.device:
+        raise ValueError("out must be a float32 [M, 2] tensor on the poses' device with unit column stride")
+    for name, t, dt in (("row_speed", row_speed, torch.float64), ("row_mask", row_mask, torch.uint8)):
+        if t is not None and (t.dtype != dt or t.shape != (M,) or not t.is_contiguous() or t.device != poses.device):
+            raise ValueError(f"{name} must be a contiguous {dt} [M] tensor on the poses' device")
+    aux = torch.empty(M, 4, dtype=torch.float64, device=poses.device) if return_aux else None
+    p = pursuit_params(**params)
+    s = stream if stream is not None else torch.cuda.current_stream(poses.device).cuda_stream
+    _lib.check(_lib.load().f110_pure_pursuit(track.handle, ctypes.byref(p), _vp(poses), M,
+                                             poses.stride(0) if M > 1 else poses.shape[1], _vp(row_speed),
+                                             _vp(row_mask), _vp(out), out.stride(0) if M > 1 else 2, _vp(aux),
+                                             ctypes.c_void_p(s)), "f110_pure_pursuit")
+    return (out, aux) if return_aux else out
+
+
+def host_pure_pursuit(poses: np.ndarray, track, out: np.ndarray | None = None, row_speed=None, row_mask=None,
+                      return_aux: bool = False, **params):
+    """f110_host_pure_pursuit over NumPy arrays: the host statement of pure_pursuit, for tests
+    without a GPU (track: any CenterlineTrack, ``device=None`` included).  poses: float32 [M, >= 3]
+    and out: float32 [M, 2] may be strided along rows (unit stride inside a row)."""
+    poses = np.asarray(poses)
+    if poses.ndim != 2 or poses.dtype != np.float32 or poses.shape[1] < 3 or (poses.size and poses.strides[1] != 4):
+        raise ValueError("poses must be a float32 array [M, >= 3] with unit stride along the pose")
+    M = poses.shape[0]
+    if not getattr(track, "handle", None):
+        raise ValueError("track must be an open reward.CenterlineTrack")
+    if out is None:
+        out = np.empty((M, 2), dtype=np.float32)
+    if out.shape != (M, 2) or out.dtype != np.float32 or (out.size and out.strides[1] != 4):
+        raise ValueError("out must be a float32 [M, 2] array with unit column stride")
+    if M and (poses.strides[0] % 4 or out.strides[0] % 4 or poses.strides[0] < 0 or out.strides[0] < 0):
+        raise ValueError("poses and out rows must be a whole, non-negative number of floats apart")
+    if row_speed is not None:
+        row_speed = np.ascontiguousarray(row_speed, dtype=np.float64)
+    if row_mask is not None:
+        row_mask = np.ascontiguousarray(row_mask, dtype=np.uint8)
+    for name, t in (("row_speed", row_speed), ("row_mask", row_mask)):
+        if t is not None and t.shape != (M,):
+            raise ValueError(f"{name} must have shape [M]")
+    aux = np.empty((M, 4), dtype=np.float64) if return_aux else None
+    p = pursuit_params(**params)
+    P = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+    _lib.check(_lib.load().f110_host_pure_pursuit(track.handle, ctypes.byref(p), P(poses), M,
+                                                  poses.strides[0] // 4 if M > 1 else poses.shape[1], P(row_speed),
+                                                  P(row_mask), P(out), out.strides[0] // 4 if M > 1 else 2, P(aux)),
+               "f110_host_pure_pursuit")
+    return (out, aux) if return_aux else out
+
+
+# ---------------------------------------------------------------- self-play --
 
 
 def agent_obs(scans: torch.Tensor, obs: torch.Tensor, agent: int, lidar_max: float, out: torch.Tensor | None = None):

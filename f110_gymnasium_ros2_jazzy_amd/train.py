@@ -8,7 +8,9 @@ Per vector step, everything on the device:
   opponent      gap_follow_action on its previous scan (:168), inside F110VectorEnv; with
                 --opponent self a frozen snapshot of the learner's actor instead (its own seat's
                 observation, noise-free), refreshed every --selfplay-sync learner updates, in the
-                --selfplay-fraction of the envs picked by opponent.selfplay_mask
+                --selfplay-fraction of the envs picked by opponent.selfplay_mask (the others race
+                the --opponent-rule); with --opponent pure_pursuit a waypoint follower on the
+                reward's centerline at --opponent-speed, aiming --opponent-lookahead ahead
   env.step      (:174) with device autoreset (gymnasium NEXT_STEP)
   reward        CenterlineSafetyProgressReward (:127-146, :179) on the device
   remember      (:184) every transition except the reset rows of autoreset steps;
@@ -49,10 +51,20 @@ class VectorTrainer:
                  max_episode_steps: int | None = None, stall_speed: float = 0.0, stall_steps: int | None = None,
                  noise_type: str = "gaussian", eval_envs: int = 0, ou_reset: bool = False, n_step: int = 1,
                  algo: str = "ddpg", policy_delay: int = 2, policy_noise: float = 0.2, noise_clip: float = 0.5,
-                 opponent: str = "gap_follow", selfplay_sync: int = 1000, selfplay_fraction: float = 1.0):
-        # the self-play arguments: ValueError before anything is built
-        if opponent not in ("gap_follow", "self"):
-            raise ValueError(f"opponent must be 'gap_follow' or 'self'; got {opponent!r}")
+                 opponent: str = "gap_follow", selfplay_sync: int = 1000, selfplay_fraction: float = 1.0,
+                 opponent_speed=None, opponent_lookahead: float | None = None, opponent_rule: str = "gap_follow"):
+        # the opponent arguments: ValueError before anything is built
+        if opponent not in ("gap_follow", "self", "pure_pursuit"):
+            raise ValueError(f"opponent must be 'gap_follow', 'self' or 'pure_pursuit'; got {opponent!r}")
+        if opponent_rule not in ("gap_follow", "pure_pursuit"):
+            raise ValueError(f"opponent_rule must be 'gap_follow' or 'pure_pursuit'; got {opponent_rule!r}")
+        if opponent_lookahead is not None and not float(opponent_lookahead) > 0.0:
+            raise ValueError(f"opponent_lookahead must be > 0; got {opponent_lookahead!r}")
+        if opponent_speed is not None:
+            sp = np.asarray(opponent_speed, dtype=np.float64)
+            if sp.shape not in ((), (int(envs_per_rank),)) or not (np.isfinite(sp).all() and (sp >= 0.0).all()):
+                raise ValueError(f"opponent_speed must be one finite number >= 0 or an array [{int(envs_per_rank)}] "
+                                 "of them")
         if int(selfplay_sync) != selfplay_sync or selfplay_sync < 1:
             raise ValueError(f"selfplay_sync must be an integer >= 1; got {selfplay_sync!r}")
         if not 0.0 <= float(selfplay_fraction) <= 1.0:
@@ -93,6 +105,12 @@ class VectorTrainer:
             priority_epsilon=1e-5, noise_sigma_start=0.20, noise_sigma_min=0.02, noise_decay=0.9995, seed=seed,
             device=self.device, max_add=self.N, graphs=graphs, noise_type=noise_type, n_step=n_step, algo=algo,
             policy_delay=policy_delay, policy_noise=policy_noise, noise_clip=noise_clip)
+        # the waypoint follower drives on the reward's centerline (self.track)
+        pursuit = opponent == "pure_pursuit" or (self.selfplay and selfplay_fraction < 1.0
+                                                 and opponent_rule == "pure_pursuit")
+        pursuit_kw = dict(opponent_track=self.track, opponent_speed=opponent_speed,
+                          opponent_params={} if opponent_lookahead is None else
+                          {"lookahead": float(opponent_lookahead)}) if pursuit else {}
         self.opp = None
         if self.selfplay:
             # the snapshot needs the learner's actor, the env the snapshot: the learner comes first (its
@@ -107,11 +125,11 @@ class VectorTrainer:
             mixed = self.selfplay_fraction < 1.0
             self.env = F110VectorEnv(self.N, opponent="mixed" if mixed else "policy", opponent_policy=self.opp,
                                      opponent_mask=selfplay_mask(self.N, env_offset, self.selfplay_fraction)
-                                     if mixed else None, **env_kw)
+                                     if mixed else None, opponent_rule=opponent_rule, **pursuit_kw, **env_kw)
             if self.env.single_observation_space.shape[0] != self.agent.obs_dim:
                 raise ValueError("the env's observation size differs from the learner's")
         else:
-            self.env = F110VectorEnv(self.N, opponent="gap_follow", **env_kw)
+            self.env = F110VectorEnv(self.N, opponent=opponent, **pursuit_kw, **env_kw)
         self._synced_at = 0  # the learner update index of the snapshot's last load
         self.train_stats = self.eval_stats = self._eval_mask = None
         if self.eval_envs:
@@ -346,8 +364,15 @@ def main():
     ap.add_argument("--policy-noise", type=float, default=0.2,
                     help="td3: target smoothing noise, in units of the action half-range")
     ap.add_argument("--noise-clip", type=float, default=0.5, help="td3: clip of the smoothing noise, same units")
-    ap.add_argument("--opponent", choices=("gap_follow", "self"), default="gap_follow",
-                    help="the car the learner races: the rule-based gap follower, or a frozen copy of its own actor")
+    ap.add_argument("--opponent", choices=("gap_follow", "self", "pure_pursuit"), default="gap_follow",
+                    help="the car the learner races: the rule-based gap follower, a frozen copy of its own actor, "
+                         "or a pure-pursuit waypoint follower on the centerline")
+    ap.add_argument("--opponent-speed", type=float, default=None,
+                    help="pure_pursuit: the follower's speed in m/s (default: the library's 4.0)")
+    ap.add_argument("--opponent-lookahead", type=float, default=None,
+                    help="pure_pursuit: metres of centerline it aims ahead (default: the library's 1.2)")
+    ap.add_argument("--opponent-rule", choices=("gap_follow", "pure_pursuit"), default="gap_follow",
+                    help="self with --selfplay-fraction < 1: the rule opponent of the other envs")
     ap.add_argument("--selfplay-sync", type=int, default=1000,
                     help="self: refresh the frozen copy every K learner updates")
     ap.add_argument("--selfplay-fraction", type=float, default=1.0,
@@ -363,7 +388,9 @@ def main():
                        stall_steps=args.stall_steps, noise_type=args.noise, eval_envs=args.eval_envs,
                        ou_reset=args.ou_reset, n_step=args.n_step, algo=args.algo, policy_delay=args.policy_delay,
                        policy_noise=args.policy_noise, noise_clip=args.noise_clip, opponent=args.opponent,
-                       selfplay_sync=args.selfplay_sync, selfplay_fraction=args.selfplay_fraction)
+                       selfplay_sync=args.selfplay_sync, selfplay_fraction=args.selfplay_fraction,
+                       opponent_speed=args.opponent_speed, opponent_lookahead=args.opponent_lookahead,
+                       opponent_rule=args.opponent_rule)
     best = -float("inf")
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)

@@ -27,6 +27,12 @@ opponent.PolicyOpponent: a frozen Actor's noise-free action from the
 opponent's own seat, same timing), ``opponent="mixed"`` with the policy in the
 envs where ``opponent_mask`` (uint8 [N]) is set and gap_follow in the others;
 the infos and the action rows are the same for all three.
+``opponent="pure_pursuit"`` drives it with the waypoint follower of opponent.pure_pursuit on
+``opponent_track`` (a device reward.CenterlineTrack): its action for step t comes from its pose in
+step t-1's observation (same timing), with ``opponent_params`` (lookahead, speed, ... see
+opponent.pursuit_params) and, for a population of opponents, ``opponent_speed`` (one speed for
+all, or one per env).  ``opponent="mixed"`` takes ``opponent_rule="gap_follow" | "pure_pursuit"``
+for the envs the policy does not drive.
 
 ``param_ranges`` ({field: (lo, hi)}, or one such dict per agent) turns on the
 device's domain randomization of the vehicle dynamics: every reset and
@@ -76,12 +82,14 @@ class F110VectorEnv:
                  opponent_idx: int = 1, reward_fn=None, infos: str = "full", options_dtype=np.float32,
                  param_ranges=None, param_seed: int | None = None, max_episode_steps: int | None = None,
                  stall_speed: float = 0.0, stall_steps: int | None = None, episode_stats: bool = False,
-                 opponent_policy=None, opponent_mask=None, **kwargs):
+                 opponent_policy=None, opponent_mask=None, opponent_track=None, opponent_params: dict | None = None,
+                 opponent_speed=None, opponent_rule: str = "gap_follow", **kwargs):
         self.num_envs = int(num_envs)
         self.num_agents = int(num_agents)
         self.params = dict(params or DEFAULT_PARAMS)
         # a bad opponent argument: ValueError before anything is built
-        self._check_opponent(opponent, int(opponent_idx), opponent_policy, opponent_mask)
+        self._check_opponent(opponent, int(opponent_idx), opponent_policy, opponent_mask, opponent_track,
+                             opponent_params, opponent_speed, opponent_rule, device)
         if param_ranges is not None:  # an unknown field: ValueError before anything is built
             param_range_rows(param_ranges, [{**DEFAULT_PARAMS, **self.params}] * self.num_agents)
         # a bad episode limit: ValueError before anything is built
@@ -140,6 +148,15 @@ class F110VectorEnv:
         if self.opponent_policy is not None and (self.opponent_policy.obs_dim != B + 4 * A
                                                  or self.opponent_policy.device != self.device):
             raise ValueError(f"opponent_policy must take {B + 4 * A} observations on {self.device}")
+        # the rule opponent: of every env ("gap_follow", "pure_pursuit"), of the unmasked ones ("mixed")
+        self.opponent_rule = {None: None, "policy": None, "mixed": opponent_rule}.get(opponent, opponent)
+        self.opponent_track = self._pursuit_params = self._pursuit_speed = None
+        if self.opponent_rule == "pure_pursuit":
+            self.opponent_track = opponent_track
+            self._pursuit_params = dict(opponent_params or {})
+            if opponent_speed is not None:
+                sp = np.broadcast_to(np.asarray(opponent_speed, dtype=np.float64), (self.num_envs,))
+                self._pursuit_speed = torch.as_tensor(np.array(sp), device=self.device)  # (a writable copy)
         if opponent is not None:
             if opponent == "mixed":
                 m = torch.as_tensor(opponent_mask)
@@ -152,18 +169,25 @@ class F110VectorEnv:
             o = self._others
             self._others_sl = slice(o[0], o[-1] + 1) if o and o == list(range(o[0], o[-1] + 1)) else o
 
-    OPPONENTS = ("gap_follow", "policy", "mixed")
+    OPPONENTS = ("gap_follow", "policy", "mixed", "pure_pursuit")
+    RULES = ("gap_follow", "pure_pursuit")
 
-    def _check_opponent(self, opponent, idx, policy, mask):
+    def _check_opponent(self, opponent, idx, policy, mask, track=None, params=None, speed=None, rule="gap_follow",
+                        device=0):
         """The opponent arguments against each other and the env's shape (host values only)."""
         if opponent is None:
             return
         N, A = self.num_envs, self.num_agents
         if opponent not in self.OPPONENTS:
-            raise ValueError(f"unknown opponent policy {opponent!r} (supported: 'gap_follow', 'policy', 'mixed')")
+            raise ValueError(f"unknown opponent policy {opponent!r} (supported: 'gap_follow', 'policy', 'mixed', "
+                             "'pure_pursuit')")
         if not (0 <= idx < A) or A < 2:
             raise ValueError("opponent needs num_agents >= 2 and 0 <= opponent_idx < num_agents")
-        if opponent == "gap_follow":
+        if opponent == "mixed" and rule not in self.RULES:
+            raise ValueError(f"unknown opponent_rule {rule!r} (supported: 'gap_follow', 'pure_pursuit')")
+        if opponent == "pure_pursuit" or (opponent == "mixed" and rule == "pure_pursuit"):
+            self._check_pursuit(track, params, speed, device)
+        if opponent in self.RULES:
             return
         if policy is None:
             raise ValueError(f"opponent={opponent!r} needs opponent_policy (an opponent.PolicyOpponent)")
@@ -176,18 +200,46 @@ class F110VectorEnv:
             if tuple(mask.shape) != (N,) or str(mask.dtype).split(".")[-1] not in ("uint8", "bool"):
                 raise ValueError(f"opponent_mask must be a uint8 [{N}] array or tensor")
 
+    def _check_pursuit(self, track, params, speed, device):
+        """The pure-pursuit arguments: a device track on the env's device, known parameter names,
+        one speed or one per env (host values only)."""
+        from .opponent import PURSUIT_FIELDS
+        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        tdev = getattr(track, "device", None)
+        if track is None or tdev is None or not getattr(track, "handle", None):
+            raise ValueError("opponent 'pure_pursuit' needs opponent_track (a device reward.CenterlineTrack)")
+        if tdev.type != dev.type or (tdev.index or 0) != (dev.index or 0):
+            raise ValueError(f"opponent_track is on {tdev}, the env on {dev}")
+        unknown = sorted(set(params or {}) - set(PURSUIT_FIELDS))
+        if unknown:
+            raise ValueError(f"unknown opponent_params {unknown} (known: {', '.join(PURSUIT_FIELDS)})")
+        if speed is not None:
+            sp = np.asarray(speed, dtype=np.float64)
+            if sp.shape not in ((), (self.num_envs,)):
+                raise ValueError(f"opponent_speed must be one number or an array [{self.num_envs}]")
+            if not (np.isfinite(sp).all() and (sp >= 0.0).all()):
+                raise ValueError("opponent_speed must be finite and >= 0")
+
     def _opponent_next(self, out, obs=None):
         """Next step's opponent action from this step's outputs: gap_follow from its scan
         (train_ddpg.py:168); "policy": the PolicyOpponent's forward from the opponent's seat (obs: the
         step's obs when the simulator wrote it elsewhere than out.obs); "mixed": gap_follow writes
         every row, then the policy head overwrites the rows with opponent_mask != 0 -- the policy's
-        hidden layers still run over all N rows (one fixed-shape GEMM pair, whatever the mask)."""
+        hidden layers still run over all N rows (one fixed-shape GEMM pair, whatever the mask).
+        "pure_pursuit" (alone, or as the rule of "mixed"): the waypoint follower on the opponent's
+        pose group of the step's obs."""
         if self.opponent is None:
             return
         rows = self._act[:, self.opponent_idx]
-        if self.opponent != "policy":
+        if self.opponent_rule == "gap_follow":
             from .opponent import gap_follow
             gap_follow(out.scans[:, self.opponent_idx], out=rows)
+        elif self.opponent_rule == "pure_pursuit":
+            from .opponent import pure_pursuit
+            o = out.obs if obs is None else obs
+            g = self.sim.B + 4 * self.opponent_idx  # the obs row's pose groups are in agent order
+            pure_pursuit(o[:, g:g + 3], self.opponent_track, out=rows, row_speed=self._pursuit_speed,
+                         **self._pursuit_params)
         if self.opponent_policy is not None:
             self.opponent_policy.act(out, self.opponent_idx, rows, row_mask=self.opponent_mask, obs=obs)
 

@@ -424,6 +424,50 @@ F110_API int f110_reward(const f110_track *track, const f110_reward_params *para
                          int32_t obs_len, int32_t n_beams, f110_reward_state *state, const uint8_t *reset_mask,
                          double *rewards, void *stream);
 
+/* ---- pure-pursuit opponent ----------------------------------------------------
+ * A waypoint follower on the track's centerline (the pure-pursuit planner of the upstream
+ * f1tenth_gym examples; the reference races gap_follow_action only): a scripted driver that laps
+ * the track at a chosen speed.  One car per row; everything in f64, a*b+c rounded twice:
+ *   (s_proj, t, seg) = CenterlineProgress.project_xy(x, y)        -- f110_reward's projection, same bits
+ *   sq = s_proj + direction*lookahead; closed track: if sq > L: sq -= L; if sq < 0: sq += L;
+ *        open track: sq clamped to [0, L]
+ *   i = searchsorted(s, sq, side="right") - 1 clipped to [0, n-2]
+ *   u = (sq - s[i]) / (s[i+1] - s[i])  (0 for a zero-length segment); target = xy[i] + u*(xy[i+1] - xy[i])
+ *   (dx, dy) = target - (x, y); d2 = dx*dx + dy*dy; ly = -sin(yaw)*dx + cos(yaw)*dy  (cr_sincos)
+ *   kappa = 2*ly/d2; steer = clip(atan(wheelbase*kappa), -steer_limit, steer_limit)
+ *   v = row_speed ? row_speed[m] : speed;
+ *   a_lat > 0: v = min(max(sqrt(a_lat / max(|kappa|, 1e-9)), v_floor), v)   (a NaN |kappa| counts as 1e-9)
+ *   d2 <= 1e-12: steer = 0 (v as computed);  a non-finite x, y or yaw: the action is (0, 0)
+ * The only operation whose last bit a platform's libm may round differently is the f64 atan. */
+typedef struct f110_pursuit_params {
+    double lookahead;    /* m along the centerline (1.2); 0 < lookahead < L */
+    double wheelbase;    /* lf + lr of f110_default_params (0.3302) */
+    double speed;        /* m/s (4.0) */
+    double a_lat;        /* m/s^2; 0: constant speed (the default), > 0: the curvature speed profile, which
+                          * needs a car with v_min < 0 (the default car's PID turns braking into throttle) */
+    double v_floor;      /* the profile's lowest speed (1.0) */
+    double steer_limit;  /* rad (0.4189) */
+    int32_t direction;   /* +1: ascending arclength, -1: descending */
+    int32_t pad_;
+} f110_pursuit_params;
+
+F110_API void f110_default_pursuit_params(f110_pursuit_params *p);
+
+/* Row m: pose (x, y, yaw) = the three float32 at poses + m*pose_stride (e.g. agent k's pose group of
+ * the step's obs: obs + n_beams + 4*k, stride f110_outputs.obs_stride); (steer, v) as float32 to
+ * actions[m*action_stride + 0/1] (e.g. agent k's slot of the next f110_step's action array: stride
+ * 2*A).  row_speed: f64 [n_rows] or NULL (params->speed for all); row_mask: u8 [n_rows] or NULL as
+ * f110_policy_head_rows takes it (rows with 0 keep their action and aux bytes); aux: f64 [n_rows][4]
+ * or NULL, receives s_proj, t (a zero as +0), target_x, target_y (four NaNs for a non-finite pose).  Device
+ * pointers; no allocation, no host synchronisation, no atomics (capturable); async on stream.
+ * F110_E_INVALID: a null track / params / poses / actions, a host-only track, pose_stride < 3,
+ * action_stride < 2, lookahead <= 0 or >= L, wheelbase <= 0, steer_limit <= 0, speed < 0,
+ * a_lat < 0, a NaN among them, direction other than +1 / -1. */
+F110_API int f110_pure_pursuit(const f110_track *track, const f110_pursuit_params *params, const float *poses,
+                               int64_t n_rows, int64_t pose_stride, const double *row_speed,
+                               const uint8_t *row_mask, float *actions, int64_t action_stride, double *aux,
+                               void *stream);
+
 /* ---- episode statistics (no reference counterpart: train_ddpg.py sums one
  * env's rewards in its Python loop) ------------------------------------------------
  * Per-env episode return and length of an autoresetting batch, and running

@@ -320,6 +320,16 @@ F110_API int f110_host_agent_obs(const float *scans, int64_t scan_env_stride, co
                                  int64_t n_envs, int32_t n_agents, int32_t n_beams, int32_t agent, float lidar_max,
                                  float *out, int64_t out_stride);
 
+/* f110_pure_pursuit over HOST arrays (same arguments, no stream): the 5 nearest midpoints by a full
+ * scan (ties: lower index), then the device's f64 operations in the device's order, the same
+ * cr_sincos and the same row rule (csrc/f110_pursuit.h); atan is the host libm's.  Needs only the
+ * track's host arrays, so a track built with device < 0 will do.  Same validation
+ * (F110_E_INVALID).  Host test hook: the CPU suite and the GPU tests share one statement of the
+ * semantics. */
+F110_API int f110_host_pure_pursuit(const f110_track *track, const f110_pursuit_params *params, const float *poses,
+                                    int64_t n_rows, int64_t pose_stride, const double *row_speed,
+                                    const uint8_t *row_mask, float *actions, int64_t action_stride, double *aux);
+
 #ifdef __cplusplus
 }
 #endif
