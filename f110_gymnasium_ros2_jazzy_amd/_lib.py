@@ -226,6 +226,14 @@ _API = {
     "f110_nstep_reset": (_i, [_P, _P, _P]),
     "f110_nstep_arrays": (_i, [_P] + _PTRS6),
     "f110_host_nstep": (_i, [_i64, _i32, _f64, _i32, _i32, _i64] + [_P] * 18 + [ctypes.POINTER(_i64)]),
+    "f110_repeat_create": (_i, [ctypes.POINTER(_P), _i32, _i64, _i32, _f64, _i32, _i32]),
+    "f110_repeat_destroy": (_i, [_P]),
+    "f110_repeat_hold": (_i, [_P, _P, _i64, _P, _i64, _P, _P]),
+    "f110_repeat_push": (_i, [_P, _P, _P, _P, _i64, _P, _P, _P, _P]),
+    "f110_repeat_reset": (_i, [_P, _P, _P]),
+    "f110_repeat_arrays": (_i, [_P] + [ctypes.POINTER(_P)] * 4),
+    "f110_host_repeat_hold": (_i, [_i64, _i32, _i32] + [_P] * 6),
+    "f110_host_repeat_push": (_i, [_i64, _i32, _f64, _i32, _i32, _i64] + [_P] * 14 + [ctypes.POINTER(_i64)]),
     "f110_agent_obs": (_i, [_P, _i64, _P, _i64, _i64, _i32, _i32, _i32, _f32, _P, _i64, _P]),
     "f110_policy_head_rows": (_i, [_P] * 5 + [_i64, _i32, _i32, _P, _P, _i64, _P]),
     "f110_host_agent_obs": (_i, [_P, _i64, _P, _i64, _i64, _i32, _i32, _i32, _f32, _P, _i64]),

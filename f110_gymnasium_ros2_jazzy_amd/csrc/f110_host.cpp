@@ -698,7 +698,74 @@ void nstep_powers(double gamma, int n, double *pw) {  // sequential products
     for (int i = 1; i <= n; ++i) pw[i] = pw[i - 1] * gamma;
 }
 
+// ---- action repeat ------------------------------------------------------------
+int check_repeat_args(const char *fn, int64_t n_envs, int32_t repeat, double gamma, int32_t obs_dim, int32_t act_dim) {
+    if (repeat < 1 || repeat > kRepeatMax) return fail(F110_E_INVALID, std::string(fn) + ": repeat must be in [1, 64]");
+    if (!std::isfinite(gamma) || gamma < 0.0 || gamma > 1.0)
+        return fail(F110_E_INVALID, std::string(fn) + ": gamma must be finite and in [0, 1]");
+    if (n_envs <= 0 || n_envs >= (int64_t)1 << 31)
+        return fail(F110_E_INVALID, std::string(fn) + ": n_envs must be positive (and below 2^31)");
+    if (obs_dim <= 0 || act_dim <= 0 || act_dim > 256)
+        return fail(F110_E_INVALID, std::string(fn) + ": obs_dim > 0 and 0 < act_dim <= 256");
+    return F110_OK;
+}
+
+int check_repeat_capacity(const char *fn, int64_t n_envs, int64_t capacity) {
+    if (n_envs > capacity)
+        return fail(F110_E_INVALID, std::string(fn) + ": n_envs must not exceed the replay's capacity");
+    return F110_OK;
+}
+
 }  // namespace f110
+
+extern "C" int f110_host_repeat_hold(int64_t n_envs, int32_t obs_dim, int32_t act_dim, const int32_t *k, float *s_obs,
+                                     float *s_act, const float *obs, float *act, uint8_t *decision) {
+    if (n_envs <= 0 || obs_dim <= 0 || act_dim <= 0 || act_dim > 256)
+        return fail(F110_E_INVALID, "f110_host_repeat_hold: n_envs > 0, obs_dim > 0 and 0 < act_dim <= 256");
+    if (!k || !s_obs || !s_act || !obs || !act) return fail(F110_E_INVALID, "f110_host_repeat_hold: null argument");
+    const size_t D = (size_t)obs_dim, A = (size_t)act_dim;
+    for (int64_t e = 0; e < n_envs; ++e) {
+        if (k[e] == 0) {
+            std::copy(obs + e * D, obs + (e + 1) * D, s_obs + e * D);
+            std::copy(act + e * A, act + (e + 1) * A, s_act + e * A);
+        } else {
+            std::copy(s_act + e * A, s_act + (e + 1) * A, act + e * A);
+        }
+        if (decision) decision[e] = k[e] == 0 ? 1 : 0;
+    }
+    return F110_OK;
+}
+
+extern "C" int f110_host_repeat_push(int64_t n_envs, int32_t repeat, double gamma, int32_t obs_dim, int32_t act_dim,
+                                     int64_t capacity, int32_t *k, double *ret, const float *s_obs, const float *s_act,
+                                     const double *reward, const float *next_obs, const uint8_t *terminated,
+                                     const uint8_t *truncated, const uint8_t *was_reset, float *out_obs, float *out_act,
+                                     float *out_reward, float *out_next_obs, float *out_done, int64_t *out_count) {
+    int rc = check_repeat_args("f110_host_repeat_push", n_envs, repeat, gamma, obs_dim, act_dim);
+    if (rc == F110_OK && capacity > 0) rc = check_repeat_capacity("f110_host_repeat_push", n_envs, capacity);
+    if (rc != F110_OK) return rc;
+    if (!k || !ret || !s_obs || !s_act || !reward || !next_obs || !terminated || !was_reset || !out_obs || !out_act ||
+        !out_reward || !out_next_obs || !out_done || !out_count)
+        return fail(F110_E_INVALID, "f110_host_repeat_push: null argument");
+    const size_t D = (size_t)obs_dim, A = (size_t)act_dim;
+    double pw[kRepeatMax + 1];
+    nstep_powers(gamma, repeat, pw);
+    int64_t row = 0;
+    for (int64_t e = 0; e < n_envs; ++e) {
+        float e_reward = 0.0f, e_done = 0.0f;
+        if (!repeat_update(repeat, pw, reward[e], terminated[e], truncated ? truncated[e] : 0, was_reset[e], k[e], ret[e],
+                           e_reward, e_done))
+            continue;
+        std::copy(s_obs + e * D, s_obs + (e + 1) * D, out_obs + row * D);
+        std::copy(s_act + e * A, s_act + (e + 1) * A, out_act + row * A);
+        std::copy(next_obs + e * D, next_obs + (e + 1) * D, out_next_obs + row * D);
+        out_reward[row] = e_reward;
+        out_done[row] = e_done;
+        ++row;
+    }
+    *out_count = row;
+    return F110_OK;
+}
 
 extern "C" int f110_host_nstep(int64_t n_envs, int32_t n_step, double gamma, int32_t obs_dim, int32_t act_dim,
                                int64_t capacity, int32_t *len, int32_t *head, double *ret, int32_t *k, float *win_obs,

@@ -107,4 +107,8 @@ int check_nstep_args(const char *fn, int64_t n_envs, int32_t n_step, double gamm
 int check_nstep_capacity(const char *fn, int64_t n_envs, int32_t n_step, int64_t capacity);
 void nstep_powers(double gamma, int n, double *pw);  // pw[0..n], sequential products
 
+// ---- action repeat ----------------------------------------------------------------
+int check_repeat_args(const char *fn, int64_t n_envs, int32_t repeat, double gamma, int32_t obs_dim, int32_t act_dim);
+int check_repeat_capacity(const char *fn, int64_t n_envs, int64_t capacity);
+
 }  // namespace f110

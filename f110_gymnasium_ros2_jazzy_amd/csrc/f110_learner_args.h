@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "f110_math.h"
+#include "f110_repeat.h"
 
 namespace f110 {
 
@@ -166,6 +167,48 @@ struct NstepRows {       // one push: n_envs raw step outputs (device)
 
 hipError_t launch_nstep_push(const ReplayView &v, const NstepView &w, const NstepRows &in, hipStream_t s);
 hipError_t launch_nstep_reset(const NstepView &w, const uint8_t *env_mask, hipStream_t s);
+
+// ---- action repeat around the env step (f110_replay.hip) -------------------
+// What the ring-slot scan reads and writes (k_count_scan, f110_replay.hip): a row count per env in,
+// the ring slot of each env's first row out.  NstepView and RepeatView both supply one.
+struct CountView {
+    int64_t n_envs;
+    const int32_t *cnt;  // [N] rows the env emits
+    int64_t *base;       // [N] ring slot of the env's first emitted row
+};
+
+struct RepeatView {      // one f110_repeat (device)
+    int64_t n_envs;
+    int32_t repeat, obs_dim, act_dim;
+    const double *pw;    // [repeat + 1] gamma^i, sequential products
+    int32_t *k;          // [N] phase
+    double *ret;         // [N] running return
+    float *obs, *act;    // [N][D], [N][A] the block's first observation and its action
+    // one push's scratch
+    int32_t *cnt;        // [N] 1: the env's block leaves
+    int64_t *base;       // [N] its ring slot
+    float *e_reward, *e_done;  // [N]
+};
+
+struct RepeatHold {      // one hold: the policy's inputs and outputs of n_envs envs (device)
+    const float *obs;
+    float *act;          // in / out
+    uint8_t *decision;   // [N] or null
+    int64_t obs_stride, act_stride;
+    int32_t vec4;        // obs rows 16-B aligned and obs_dim % 4 == 0
+};
+
+struct RepeatRows {      // one push: n_envs raw step outputs (device)
+    const float *next_obs;
+    const double *reward;
+    const uint8_t *terminated, *truncated, *was_reset;  // truncated may be null
+    int64_t next_stride;
+    int32_t vec4;        // next_obs rows 16-B aligned and obs_dim % 4 == 0
+};
+
+hipError_t launch_repeat_hold(const RepeatView &w, const RepeatHold &in, hipStream_t s);
+hipError_t launch_repeat_push(const ReplayView &v, const RepeatView &w, const RepeatRows &in, hipStream_t s);
+hipError_t launch_repeat_reset(const RepeatView &w, const uint8_t *env_mask, hipStream_t s);
 
 // ---- flat Adam (f110_adam.hip) --------------------------------------------
 struct AdamArgs {

@@ -12,6 +12,9 @@
 //   n-step  (no reference counterpart)  f110_nstep_push: a per-env window of
 //           pending (s, a, running return) entries in front of the ring; a
 //           push emits 0..n rows per env, placed by a scan over the counts.
+//   repeat  (no reference counterpart)  f110_repeat_hold / f110_repeat_push: per
+//           env a phase, a latched (s, a) and a running return around the env
+//           step; a push emits 0 or 1 row per env through the same scan.
 //   sample  (replay_buffer.py:76-116)  Sampling WITHOUT replacement from
 //           p_i = (prio_i + eps)^alpha / sum_j (...) by the exponential race
 //           (Efraimidis-Spirakis): key_i = E_i / w_i with E_i ~ Exp(1); the B
@@ -236,7 +239,7 @@ __global__ void __launch_bounds__(kRB) k_add_copy(ReplayView v, ReplayRows in, i
 
 // ------------------------------------------------------- n-step push -------
 // f110_nstep_push: k_nstep_update (one thread per env: nstep_update, f110_learner_args.h) ->
-// k_prio_max -> k_nstep_scan (k_add_scan with a count per env in place of a 0/1 mask) ->
+// k_prio_max -> k_count_scan (k_add_scan with a count per env in place of a 0/1 mask) ->
 // k_nstep_copy (one block per (env, emitted row), one more job per env for the window).
 __global__ void __launch_bounds__(kRB) k_nstep_update(NstepView w, NstepRows in) {
     const int64_t e = (int64_t)blockIdx.x * kRB + threadIdx.x;
@@ -254,8 +257,9 @@ __global__ void __launch_bounds__(kRB) k_nstep_update(NstepView w, NstepRows in)
 
 // Ring slots of the emitted rows, by env ascending and oldest first within an env, as that many
 // add(priority=None) calls in this order would fill them: base[e] is the env's first slot, its
-// rows take consecutive ones (mod capacity).  Total rows <= n_envs * n <= capacity: no slot twice.
-__global__ void __launch_bounds__(kOneBlock) k_nstep_scan(ReplayView v, NstepView w, int n_part) {
+// rows take consecutive ones (mod capacity).  Total rows <= capacity (n-step: n_envs * n, action
+// repeat: n_envs): no slot twice.  Shared by the n-step and the action-repeat push (CountView).
+__global__ void __launch_bounds__(kOneBlock) k_count_scan(ReplayView v, CountView w, int n_part) {
     __shared__ int64_t part[kOneBlock];
     __shared__ uint32_t wmx[kOneBlock / 64];
     __shared__ uint32_t mx;
@@ -379,6 +383,65 @@ __global__ void __launch_bounds__(kRB) k_nstep_reset(NstepView w, const uint8_t 
     if (e >= w.n_envs || (env_mask && !env_mask[e])) return;
     w.len[e] = 0;
     w.head[e] = 0;
+}
+
+// ----------------------------------------------------- action repeat -------
+// f110_repeat_hold (before the env step): one block per env, the grid shape of k_nstep_copy.  The
+// block reads k[e] once, so the branch is block-uniform.  A decision block (k == 0) latches the obs
+// row and the policy's action; a hold block writes the latched action over the policy's.
+// Hold of step t + 1 overwrites s_obs[e] / s_act[e], which k_repeat_copy of step t reads: both run
+// on the caller's one stream, in that order, so the rows need no second copy and no atomics.
+__global__ void __launch_bounds__(kRB) k_repeat_hold(RepeatView w, RepeatHold in) {
+    const int64_t e = blockIdx.x;
+    if (e >= w.n_envs) return;
+    const int D = w.obs_dim, A = w.act_dim;
+    float *a_io = in.act + e * in.act_stride;
+    if (w.k[e] == 0) {
+        copy_rows(in.obs + e * in.obs_stride, w.obs + e * D, nullptr, nullptr, D, in.vec4);
+        if ((int)threadIdx.x < A) w.act[e * A + threadIdx.x] = a_io[threadIdx.x];
+        if (in.decision && threadIdx.x == 0) in.decision[e] = 1;
+    } else {
+        if ((int)threadIdx.x < A) a_io[threadIdx.x] = w.act[e * A + threadIdx.x];
+        if (in.decision && threadIdx.x == 0) in.decision[e] = 0;
+    }
+}
+
+// f110_repeat_push (after the env step): k_repeat_update (one thread per env: repeat_update,
+// f110_repeat.h) -> k_prio_max -> k_count_scan -> k_repeat_copy (one block per env).
+__global__ void __launch_bounds__(kRB) k_repeat_update(RepeatView w, RepeatRows in) {
+    const int64_t e = (int64_t)blockIdx.x * kRB + threadIdx.x;
+    if (e >= w.n_envs) return;
+    int32_t k = w.k[e];
+    double ret = w.ret[e];
+    float er = 0.0f, ed = 0.0f;
+    const int cnt = repeat_update(w.repeat, w.pw, in.reward[e], in.terminated[e], in.truncated ? in.truncated[e] : 0,
+                                  in.was_reset[e], k, ret, er, ed);
+    w.k[e] = k;
+    w.ret[e] = ret;
+    w.cnt[e] = cnt;
+    w.e_reward[e] = er;
+    w.e_done[e] = ed;
+}
+
+// Block e: the env's block, where it leaves, into its ring slot -- obs / act as latched at the
+// block's decision step, next_obs from the caller's row e.
+__global__ void __launch_bounds__(kRB) k_repeat_copy(ReplayView v, RepeatView w, RepeatRows in) {
+    const int64_t e = blockIdx.x;
+    if (e >= w.n_envs || w.cnt[e] == 0) return;
+    const int D = w.obs_dim, A = w.act_dim;
+    const int64_t slot = w.base[e];  // (k_count_scan: already in [0, capacity))
+    copy_rows(w.obs + e * D, v.obs + slot * D, in.next_obs + e * in.next_stride, v.next_obs + slot * D, D, in.vec4);
+    if ((int)threadIdx.x < A) v.act[slot * A + threadIdx.x] = w.act[e * A + threadIdx.x];
+    if (threadIdx.x == 0) {
+        v.reward[slot] = w.e_reward[e];
+        v.done[slot] = w.e_done[e];
+    }
+}
+
+__global__ void __launch_bounds__(kRB) k_repeat_reset(RepeatView w, const uint8_t *env_mask) {
+    const int64_t e = (int64_t)blockIdx.x * kRB + threadIdx.x;
+    if (e >= w.n_envs || (env_mask && !env_mask[e])) return;
+    w.k[e] = 0;
 }
 
 // ------------------------------------------------------------- sample ------
@@ -858,7 +921,7 @@ hipError_t launch_nstep_push(const ReplayView &v, const NstepView &w, const Nste
     const unsigned eb = (unsigned)((w.n_envs + kRB - 1) / kRB);
     hipLaunchKernelGGL(k_nstep_update, dim3(eb), dim3(kRB), 0, s, w, in);
     hipLaunchKernelGGL(k_prio_max, dim3(grid), dim3(kRB), 0, s, v);
-    hipLaunchKernelGGL(k_nstep_scan, dim3(1), dim3(kOneBlock), 0, s, v, w, grid);
+    hipLaunchKernelGGL(k_count_scan, dim3(1), dim3(kOneBlock), 0, s, v, CountView{w.n_envs, w.cnt, w.base}, grid);
     hipLaunchKernelGGL(k_nstep_copy, dim3((unsigned)(w.n_envs * w.n)), dim3(kRB), 0, s, v, w, in);
     return hipGetLastError();
 }
@@ -866,6 +929,27 @@ hipError_t launch_nstep_push(const ReplayView &v, const NstepView &w, const Nste
 hipError_t launch_nstep_reset(const NstepView &w, const uint8_t *env_mask, hipStream_t s) {
     const unsigned eb = (unsigned)((w.n_envs + kRB - 1) / kRB);
     hipLaunchKernelGGL(k_nstep_reset, dim3(eb), dim3(kRB), 0, s, w, env_mask);
+    return hipGetLastError();
+}
+
+hipError_t launch_repeat_hold(const RepeatView &w, const RepeatHold &in, hipStream_t s) {
+    hipLaunchKernelGGL(k_repeat_hold, dim3((unsigned)w.n_envs), dim3(kRB), 0, s, w, in);
+    return hipGetLastError();
+}
+
+hipError_t launch_repeat_push(const ReplayView &v, const RepeatView &w, const RepeatRows &in, hipStream_t s) {
+    const int grid = replay_grid(v.capacity);
+    const unsigned eb = (unsigned)((w.n_envs + kRB - 1) / kRB);
+    hipLaunchKernelGGL(k_repeat_update, dim3(eb), dim3(kRB), 0, s, w, in);
+    hipLaunchKernelGGL(k_prio_max, dim3(grid), dim3(kRB), 0, s, v);
+    hipLaunchKernelGGL(k_count_scan, dim3(1), dim3(kOneBlock), 0, s, v, CountView{w.n_envs, w.cnt, w.base}, grid);
+    hipLaunchKernelGGL(k_repeat_copy, dim3((unsigned)w.n_envs), dim3(kRB), 0, s, v, w, in);
+    return hipGetLastError();
+}
+
+hipError_t launch_repeat_reset(const RepeatView &w, const uint8_t *env_mask, hipStream_t s) {
+    const unsigned eb = (unsigned)((w.n_envs + kRB - 1) / kRB);
+    hipLaunchKernelGGL(k_repeat_reset, dim3(eb), dim3(kRB), 0, s, w, env_mask);
     return hipGetLastError();
 }
 

@@ -1,8 +1,9 @@
 // f110_replay_capi.cpp — host side of the learner's device components
-// (include/f110.h, "prioritized experience replay", "n-step returns" and
-// "learner optimizer"): argument checks, the device allocation at create, the
-// launches of f110_replay.hip / f110_adam.hip.  (The n-step host model,
-// f110_host_nstep, and the argument checks it shares are in f110_host.cpp.)
+// (include/f110.h, "prioritized experience replay", "n-step returns", "action
+// repeat" and "learner optimizer"): argument checks, the device allocation at
+// create, the launches of f110_replay.hip / f110_adam.hip.  (The n-step and
+// action-repeat host models, f110_host_nstep and f110_host_repeat_*, and the
+// argument checks they share are in f110_host.cpp.)
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -347,6 +348,128 @@ extern "C" int f110_nstep_arrays(f110_nstep *ns, int32_t **len, int32_t **head, 
     if (k) *k = ns->w.k;
     if (obs) *obs = ns->w.obs;
     if (act) *act = ns->w.act;
+    return F110_OK;
+}
+
+// ---- action repeat --------------------------------------------------------------
+struct f110_repeat {
+    DeviceArena arena;
+    RepeatView w{};
+
+    // n elements and 16 bytes of slack (the vectorised row copies), all zero
+    template <class T>
+    hipError_t alloc(T **p, size_t n) {
+        return arena.alloc(p, n, /*zero=*/true, 16);
+    }
+};
+
+extern "C" int f110_repeat_create(f110_repeat **out, int32_t device, int64_t n_envs, int32_t repeat, double gamma,
+                                  int32_t obs_dim, int32_t act_dim) {
+    if (!out) return fail(F110_E_INVALID, "f110_repeat_create: null out");
+    const int rc = check_repeat_args("f110_repeat_create", n_envs, repeat, gamma, obs_dim, act_dim);
+    if (rc != F110_OK) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
+        return fail(F110_E_NODEVICE, "f110_repeat_create: no such HIP device");
+    if (hipSetDevice(device) != hipSuccess) return fail(F110_E_NODEVICE, "f110_repeat_create: hipSetDevice");
+    auto *rp = new f110_repeat();
+    rp->arena.device = device;
+    RepeatView &w = rp->w;
+    w.n_envs = n_envs;
+    w.repeat = repeat;
+    w.obs_dim = obs_dim;
+    w.act_dim = act_dim;
+    const size_t N = (size_t)n_envs;
+    double pw[kRepeatMax + 1];
+    nstep_powers(gamma, repeat, pw);
+    double *dpw = nullptr;
+    hipError_t e = rp->alloc(&dpw, (size_t)repeat + 1);
+    w.pw = dpw;
+    if (e == hipSuccess) e = rp->alloc(&w.k, N);
+    if (e == hipSuccess) e = rp->alloc(&w.ret, N);
+    if (e == hipSuccess) e = rp->alloc(&w.obs, N * obs_dim);
+    if (e == hipSuccess) e = rp->alloc(&w.act, N * act_dim);
+    if (e == hipSuccess) e = rp->alloc(&w.cnt, N);
+    if (e == hipSuccess) e = rp->alloc(&w.base, N);
+    if (e == hipSuccess) e = rp->alloc(&w.e_reward, N);
+    if (e == hipSuccess) e = rp->alloc(&w.e_done, N);
+    if (e == hipSuccess) e = hipMemcpy(dpw, pw, ((size_t)repeat + 1) * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        delete rp;  // (the arena frees what was allocated)
+        return hip_fail("f110_repeat_create", e, F110_E_ALLOC);
+    }
+    *out = rp;
+    return F110_OK;
+}
+
+extern "C" int f110_repeat_destroy(f110_repeat *rp) {
+    delete rp;
+    return F110_OK;
+}
+
+extern "C" int f110_repeat_hold(f110_repeat *rp, const float *obs, int64_t obs_stride, float *act, int64_t act_stride,
+                                uint8_t *decision, void *stream) {
+    if (!rp) return fail(F110_E_INVALID, "f110_repeat_hold: null handle");
+    const RepeatView &w = rp->w;
+    if (!obs || !act || obs_stride < w.obs_dim || act_stride < w.act_dim)
+        return fail(F110_E_INVALID, "f110_repeat_hold: null row pointer or stride below the row length");
+    if (hipSetDevice(rp->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_repeat_hold: hipSetDevice");
+    RepeatHold in{};
+    in.obs = obs;
+    in.act = act;
+    in.decision = decision;
+    in.obs_stride = obs_stride;
+    in.act_stride = act_stride;
+    // (the latched rows start 16-B aligned whenever obs_dim % 4 == 0)
+    in.vec4 = (w.obs_dim % 4 == 0 && obs_stride % 4 == 0 && aligned16(obs)) ? 1 : 0;
+    hipError_t e = launch_repeat_hold(w, in, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail("f110_repeat_hold", e);
+    return F110_OK;
+}
+
+extern "C" int f110_repeat_push(f110_repeat *rp, f110_replay *rb, const double *reward, const float *next_obs,
+                                int64_t next_stride, const uint8_t *terminated, const uint8_t *truncated,
+                                const uint8_t *was_reset, void *stream) {
+    if (!rp || !rb) return fail(F110_E_INVALID, "f110_repeat_push: null handle or buffer");
+    const RepeatView &w = rp->w;
+    const ReplayView &v = rb->v;
+    if (rp->arena.device != rb->arena.device) return fail(F110_E_INVALID, "f110_repeat_push: handle and buffer on different devices");
+    if (w.obs_dim != v.obs_dim || w.act_dim != v.act_dim)
+        return fail(F110_E_INVALID, "f110_repeat_push: obs_dim / act_dim differ from the replay's");
+    const int rc = check_repeat_capacity("f110_repeat_push", w.n_envs, v.capacity);
+    if (rc != F110_OK) return rc;
+    if (!reward || !next_obs || !terminated || !was_reset || next_stride < v.obs_dim)
+        return fail(F110_E_INVALID, "f110_repeat_push: null pointer or stride below the row length");
+    if (hipSetDevice(rp->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_repeat_push: hipSetDevice");
+    RepeatRows in{};
+    in.next_obs = next_obs;
+    in.reward = reward;
+    in.terminated = terminated;
+    in.truncated = truncated;
+    in.was_reset = was_reset;
+    in.next_stride = next_stride;
+    // (the latched and the ring's rows start 16-B aligned whenever obs_dim % 4 == 0)
+    in.vec4 = (v.obs_dim % 4 == 0 && next_stride % 4 == 0 && aligned16(next_obs)) ? 1 : 0;
+    hipError_t e = launch_repeat_push(v, w, in, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail("f110_repeat_push", e);
+    return F110_OK;
+}
+
+extern "C" int f110_repeat_reset(f110_repeat *rp, const uint8_t *env_mask, void *stream) {
+    if (!rp) return fail(F110_E_INVALID, "f110_repeat_reset: null handle");
+    if (hipSetDevice(rp->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_repeat_reset: hipSetDevice");
+    hipError_t e = launch_repeat_reset(rp->w, env_mask, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail("f110_repeat_reset", e);
+    return F110_OK;
+}
+
+extern "C" int f110_repeat_arrays(f110_repeat *rp, int32_t **k, double **ret, float **obs, float **act) {
+    if (!rp) return fail(F110_E_INVALID, "f110_repeat_arrays: null handle");
+    if (k) *k = rp->w.k;
+    if (ret) *ret = rp->w.ret;
+    if (obs) *obs = rp->w.obs;
+    if (act) *act = rp->w.act;
     return F110_OK;
 }
 

@@ -345,8 +345,22 @@ class DDPGLearner:
                  check_finite: bool = False, path: str | None = None, graphs: bool = False,
                  noise_type: str = "gaussian", ou_theta: float = 0.15, ou_mu: float = 0.0, ou_dt: float = 1.0,
                  n_step: int = 1, algo: str = "ddpg", policy_delay: int = 2, policy_noise: float = 0.2,
-                 noise_clip: float = 0.5):
+                 noise_clip: float = 0.5, action_repeat: int = 1):
         self.device = torch.device(device)
+        # action_repeat K > 1: the policy's action is held for blocks of up to K simulator steps
+        # (hold_env) and remember_env stores one row per block (replay.ActionRepeat); checked here,
+        # before any network is built
+        if isinstance(action_repeat, bool) or not isinstance(action_repeat, (int, np.integer)) or \
+                not 1 <= action_repeat <= 64:
+            raise ValueError(f"action_repeat must be an integer in 1..64; got {action_repeat!r}")
+        self.action_repeat = int(action_repeat)
+        if self.action_repeat > 1:
+            from .replay import DeviceReplayBuffer
+            if replay != "device" and not isinstance(replay, DeviceReplayBuffer):
+                raise ValueError("action_repeat > 1 needs the device replay buffer")
+            if int(n_step) > 1:
+                raise ValueError("action_repeat > 1 with n_step > 1 is not supported: blocks of variable length "
+                                 "would have to go through the n-step windows; use one of the two")
         # algo "td3": twin critics with the clipped double-Q target, target-policy smoothing and the
         # actor / target updates every policy_delay-th update; the three TD3 arguments are checked
         # and otherwise unused for "ddpg"
@@ -449,6 +463,13 @@ class DDPGLearner:
                 raise ValueError("n_step > 1 needs the device replay buffer")
             self.nstep = NStepAccumulator(self.memory.max_add, self.n_step, self.gamma, obs_dim=self.obs_dim,
                                           act_dim=self.act_dim, device=self.device)
+        # action_repeat > 1: a phase, a latched (s, a) and a running return per env; self.gamma stays
+        # the one-step gamma and the update kernels are the one-step ones, as with n_step
+        self.repeat = None
+        if self.action_repeat > 1:
+            from .replay import ActionRepeat
+            self.repeat = ActionRepeat(self.memory.max_add, self.action_repeat, self.gamma, obs_dim=self.obs_dim,
+                                       act_dim=self.act_dim, device=self.device)
         # GaussianActionNoise (agent.py:507-539) on the device
         self.sigma = float(noise_sigma_start)
         self.sigma_min, self.noise_decay = float(noise_sigma_min), float(noise_decay)
@@ -498,13 +519,26 @@ class DDPGLearner:
         """agent.py:223-237 for a batch of transitions (rows with mask == 0 skipped)."""
         self.memory.add(state, action, reward, next_state, done, mask=mask)
 
+    def hold_env(self, state, action):
+        """Before the env step: with action_repeat > 1, latch (state, action) of the envs whose
+        decision is due and overwrite the other envs' action rows, in place, with their held action
+        (replay.ActionRepeat.hold).  Returns ``action``; a no-op without action repeat."""
+        if self.repeat is not None:
+            self.repeat.hold(state, action)
+        return action
+
     def remember_env(self, state, action, reward, next_state, terminated, was_reset, truncated=None):
         """remember() of a vector env's raw outputs (float64 rewards, uint8
         terminated / was_reset flags; reset rows skipped) without torch-side
         conversions (DeviceReplayBuffer.add_env).  With n_step > 1 the step goes
         into the n-step windows instead, which also end at ``truncated`` rows
-        (uint8 or None); with n_step == 1 truncated is not used."""
-        if self.nstep is None:
+        (uint8 or None); with n_step == 1 truncated is not used.  With
+        action_repeat > 1 the step goes into the action-repeat blocks
+        (replay.ActionRepeat.push), which take state and action from the
+        preceding hold_env and end at ``truncated`` rows too."""
+        if self.repeat is not None:
+            self.repeat.push(self.memory, reward, next_state, terminated, truncated, was_reset)
+        elif self.nstep is None:
             self.memory.add_env(state, action, reward, next_state, terminated, was_reset)
         else:
             self.nstep.push(self.memory, state, action, reward, next_state, terminated, truncated, was_reset)

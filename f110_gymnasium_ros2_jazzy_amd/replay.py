@@ -356,6 +356,170 @@ class NStepAccumulator:
             pass
 
 
+class ActionRepeat:
+    """Action repeat around a vector env's step (include/f110.h, "action repeat"): per env a device
+    phase, the block's first observation and action, and a running return.  ``hold`` runs before the
+    env step: envs whose decision is due keep the policy's action and latch it with the observation;
+    the others get their held action written over the policy's.  ``push`` runs after it and appends
+    one row per finished block to the ring -- a block is finished after ``repeat`` steps or when its
+    episode ends -- with the effective done 1 - gamma^(k-1) (1 - done), so the one-step learner
+    bootstraps it with gamma^k.  All on the current torch stream; nothing goes through the host."""
+
+    def __init__(self, n_envs: int, repeat: int, gamma: float, obs_dim: int = 1088, act_dim: int = 2, device=0):
+        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        self.L = _lib.load()
+        self.n_envs, self.repeat, self.gamma = int(n_envs), int(repeat), float(gamma)
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        self.handle = None
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise _lib.F110Error("ActionRepeat runs on a HIP device only (no CPU path)")
+        self.device = dev
+        h = ctypes.c_void_p()
+        _lib.check(self.L.f110_repeat_create(ctypes.byref(h), dev.index or 0, self.n_envs, self.repeat, self.gamma,
+                                             self.obs_dim, self.act_dim), "f110_repeat_create")
+        self.handle = h
+        self.decision = torch.zeros(self.n_envs, dtype=torch.uint8, device=dev)  # written by the last hold
+        self._keep = self._keep_h = None
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _rows(self, x, width, what):
+        """x as [n_envs, width] float32 rows of unit inner stride, WITHOUT a copy (hold writes in place)."""
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device.type != "cuda" or \
+                (x.device.index or 0) != (self.device.index or 0):
+            raise TypeError(f"{what}: a float32 tensor on {self.device}")
+        if x.dim() != 2 or x.shape[1] != width or x.stride(1) != 1 or x.stride(0) < width:
+            raise ValueError(f"{what}: [n_envs, {width}] rows of unit inner stride (views are fine, copies are not)")
+        if x.shape[0] != self.n_envs:
+            raise ValueError(f"{what}: every input needs n_envs = {self.n_envs} rows")
+        return x
+
+    def hold(self, obs, act):
+        """Before the env step.  obs [n_envs, obs_dim], act [n_envs, act_dim]: float32 device
+        tensors or strided row views of them; act is rewritten in place and returned.
+        ``decision`` [n_envs] uint8 is 1 where the policy's action was kept."""
+        s = self._rows(obs, self.obs_dim, "hold: obs")
+        a = self._rows(act, self.act_dim, "hold: act")
+        self._keep_h = (s, a)  # alive until the stream has consumed them
+        _lib.check(self.L.f110_repeat_hold(self.handle, _p(s), s.stride(0), _p(a), a.stride(0), _p(self.decision),
+                                           self._stream()), "f110_repeat_hold")
+        return act
+
+    def push(self, memory: DeviceReplayBuffer, rewards, next_obs, terminated, truncated, was_reset):
+        """After the env step: one vector step into the blocks; the finished blocks into ``memory``.
+        rewards float64, terminated / truncated / was_reset uint8 device tensors as the simulator
+        writes them (truncated may be None: no episode limits); ``n_envs`` rows each."""
+        ns = memory._rows(next_obs, self.obs_dim)
+        r, d, m = rewards.reshape(-1), terminated.reshape(-1), was_reset.reshape(-1)
+        t = None if truncated is None else truncated.reshape(-1)
+        if r.dtype != torch.float64 or d.dtype != torch.uint8 or m.dtype != torch.uint8 or \
+                (t is not None and t.dtype != torch.uint8):
+            raise TypeError("push: rewards float64, terminated, truncated and was_reset uint8")
+        if not (r.is_contiguous() and d.is_contiguous() and m.is_contiguous() and (t is None or t.is_contiguous())):
+            raise ValueError("push: contiguous rewards / flags")
+        n = self.n_envs
+        if any(x.shape[0] != n for x in (ns, r, d, m)) or (t is not None and t.shape[0] != n):
+            raise ValueError(f"push: every input needs n_envs = {n} rows")
+        self._keep = (ns, r, d, t, m)  # alive until the stream has consumed them
+        _lib.check(self.L.f110_repeat_push(self.handle, memory.handle, _p(r), _p(ns), ns.stride(0), _p(d), _p(t), _p(m),
+                                           self._stream()), "f110_repeat_push")
+        memory.note_added(n)  # an upper bound: at most one row per env and push
+
+    def reset(self, env_mask=None):
+        """A decision is due at the next hold for the envs with env_mask != 0 (None: all); their
+        running blocks are dropped and nothing is emitted."""
+        m = None if env_mask is None else _as_u8(torch.as_tensor(env_mask, device=self.device))
+        if m is not None and m.shape[0] != self.n_envs:
+            raise ValueError("reset: env_mask needs n_envs entries")
+        self._keep_m = m
+        _lib.check(self.L.f110_repeat_reset(self.handle, _p(m), self._stream()), "f110_repeat_reset")
+
+    def arrays(self):
+        """Device copies of the state (tests): k [N] int32, ret [N] float64, obs [N, D], act [N, A]."""
+        ptrs = [ctypes.c_void_p() for _ in range(4)]
+        _lib.check(self.L.f110_repeat_arrays(self.handle, *[ctypes.byref(p) for p in ptrs]), "f110_repeat_arrays")
+        N = self.n_envs
+        spec = [("k", (N,), torch.int32), ("ret", (N,), torch.float64), ("obs", (N, self.obs_dim), torch.float32),
+                ("act", (N, self.act_dim), torch.float32)]
+        out = {}
+        for (name, shape, dt), p in zip(spec, ptrs):
+            t = torch.empty(shape, dtype=dt, device=self.device)
+            _d2d(t, p.value, self._stream())
+            out[name] = t
+        return out
+
+    def phase(self) -> torch.Tensor:
+        """[n_envs] int32 copy of the phases (0: a decision is due)."""
+        p = ctypes.c_void_p()
+        _lib.check(self.L.f110_repeat_arrays(self.handle, ctypes.byref(p), None, None, None), "f110_repeat_arrays")
+        t = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        _d2d(t, p.value, self._stream())
+        return t
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize(self.device)
+            self.L.f110_repeat_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def host_repeat_state(n_envs: int, obs_dim: int, act_dim: int) -> dict:
+    """Fresh host action-repeat state in f110_repeat_arrays' layout."""
+    import numpy as np
+    N = int(n_envs)
+    return {"k": np.zeros(N, np.int32), "ret": np.zeros(N, np.float64), "obs": np.zeros((N, obs_dim), np.float32),
+            "act": np.zeros((N, act_dim), np.float32)}
+
+
+def host_repeat_hold(state: dict, obs, act):
+    """One hold on the host (f110_host_repeat_hold) over NumPy arrays; ``state`` as
+    ``host_repeat_state`` makes it, updated in place.  Returns (act, decision): the action rows the
+    env is to step with (a new array) and the uint8 decision mask."""
+    import numpy as np
+    L = _lib.load()
+    N, D = state["obs"].shape
+    A = state["act"].shape[1]
+    obs = np.ascontiguousarray(obs, np.float32).reshape(N, D)
+    act = np.array(act, np.float32, order="C").reshape(N, A)  # (a copy: the caller's rows stay)
+    decision = np.empty(N, np.uint8)
+    _lib.check(L.f110_host_repeat_hold(N, D, A, *[ctypes.c_void_p(x.ctypes.data) for x in
+                                                  (state["k"], state["obs"], state["act"], obs, act, decision)]),
+               "f110_host_repeat_hold")
+    return act, decision
+
+
+def host_repeat_push(state: dict, repeat, gamma, reward, next_obs, terminated, truncated, was_reset,
+                     capacity: int = 0):
+    """One push on the host (f110_host_repeat_push) over NumPy arrays.  Returns the emitted rows
+    (obs, act, reward, next_obs, done) in the order the device appends them."""
+    import numpy as np
+    L = _lib.load()
+    N, D = state["obs"].shape
+    A = state["act"].shape[1]
+    next_obs = np.ascontiguousarray(next_obs, np.float32).reshape(N, D)
+    reward = np.ascontiguousarray(reward, np.float64).reshape(N)
+    flags = [None if f is None else np.ascontiguousarray(f, np.uint8).reshape(N)
+             for f in (terminated, truncated, was_reset)]
+    out = [np.empty((N, D), np.float32), np.empty((N, A), np.float32), np.empty(N, np.float32),
+           np.empty((N, D), np.float32), np.empty(N, np.float32)]
+    cnt = ctypes.c_int64()
+
+    def ptr(x):
+        return None if x is None else ctypes.c_void_p(x.ctypes.data)
+    _lib.check(L.f110_host_repeat_push(N, int(repeat), float(gamma), D, A, int(capacity),
+                                       *[ptr(state[q]) for q in ("k", "ret", "obs", "act")], ptr(reward),
+                                       ptr(next_obs), *[ptr(f) for f in flags], *[ptr(x) for x in out],
+                                       ctypes.byref(cnt)), "f110_host_repeat_push")
+    return tuple(x[:cnt.value] for x in out)
+
+
 def host_nstep(state: dict, gamma, obs, act, reward, next_obs, terminated, truncated, was_reset, capacity: int = 0):
     """One push on the host (f110_host_nstep) over NumPy arrays.  ``state``: the windows, as
     ``host_nstep_state`` makes them, updated in place.  Returns the emitted rows

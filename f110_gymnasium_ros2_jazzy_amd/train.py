@@ -11,10 +11,21 @@ Per vector step, everything on the device:
                 --selfplay-fraction of the envs picked by opponent.selfplay_mask (the others race
                 the --opponent-rule); with --opponent pure_pursuit a waypoint follower on the
                 reward's centerline at --opponent-speed, aiming --opponent-lookahead ahead
+  hold          with --action-repeat K > 1 (a control interval of K simulator steps; no reference
+                counterpart) the action is a decision only where the env's block is over: every
+                other env's row is overwritten with the action its block began with, on the device,
+                whatever wrote it (warm-up draw, actor + noise, eval row).  The actor and the noise
+                still run at every simulator step (sigma decays and the OU state advances per step;
+                a held row's draw is discarded), as do the opponent, the reward, the episode
+                statistics and the eval bookkeeping
   env.step      (:174) with device autoreset (gymnasium NEXT_STEP)
   reward        CenterlineSafetyProgressReward (:127-146, :179) on the device
   remember      (:184) every transition except the reset rows of autoreset steps;
-                with --n-step N as N-step returns (device windows in front of the ring)
+                with --n-step N as N-step returns (device windows in front of the ring);
+                with --action-repeat K one row per block: the block's first observation and
+                action, its discounted return, the observation after its last step, and the
+                effective done 1 - gamma^(k-1) (1 - done) of its k <= K steps (a block ends early
+                with its episode; a reset row drops the block and a decision is due right after)
   replay        (:187-188) `updates_per_step` learner updates after warm-up,
                 gradients averaged over ranks by RCCL; with --algo td3 the TD3 rule
                 (twin critics, target smoothing, delayed actor / target updates)
@@ -52,8 +63,14 @@ class VectorTrainer:
                  noise_type: str = "gaussian", eval_envs: int = 0, ou_reset: bool = False, n_step: int = 1,
                  algo: str = "ddpg", policy_delay: int = 2, policy_noise: float = 0.2, noise_clip: float = 0.5,
                  opponent: str = "gap_follow", selfplay_sync: int = 1000, selfplay_fraction: float = 1.0,
-                 opponent_speed=None, opponent_lookahead: float | None = None, opponent_rule: str = "gap_follow"):
-        # the opponent arguments: ValueError before anything is built
+                 opponent_speed=None, opponent_lookahead: float | None = None, opponent_rule: str = "gap_follow",
+                 action_repeat: int = 1):
+        # action_repeat and the opponent arguments: ValueError before anything is built
+        if isinstance(action_repeat, bool) or not isinstance(action_repeat, (int, np.integer)) or \
+                not 1 <= action_repeat <= 64:
+            raise ValueError(f"action_repeat must be an integer in 1..64; got {action_repeat!r}")
+        if action_repeat > 1 and int(n_step) > 1:
+            raise ValueError("action_repeat > 1 with n_step > 1 is not supported; use one of the two")
         if opponent not in ("gap_follow", "self", "pure_pursuit"):
             raise ValueError(f"opponent must be 'gap_follow', 'self' or 'pure_pursuit'; got {opponent!r}")
         if opponent_rule not in ("gap_follow", "pure_pursuit"):
@@ -104,7 +121,8 @@ class VectorTrainer:
             actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size, alpha=0.6, beta=0.4,
             priority_epsilon=1e-5, noise_sigma_start=0.20, noise_sigma_min=0.02, noise_decay=0.9995, seed=seed,
             device=self.device, max_add=self.N, graphs=graphs, noise_type=noise_type, n_step=n_step, algo=algo,
-            policy_delay=policy_delay, policy_noise=policy_noise, noise_clip=noise_clip)
+            policy_delay=policy_delay, policy_noise=policy_noise, noise_clip=noise_clip,
+            action_repeat=int(action_repeat))
         # the waypoint follower drives on the reward's centerline (self.track)
         pursuit = opponent == "pure_pursuit" or (self.selfplay and selfplay_fraction < 1.0
                                                  and opponent_rule == "pure_pursuit")
@@ -225,7 +243,10 @@ class VectorTrainer:
                                         reset=reset)
 
     def _transition(self, obs_in, act, obs_out):
-        """env.step, the episode statistics of the two row ranges (eval_envs > 0) and remember."""
+        """hold (action_repeat > 1: held actions over the rows whose decision is not due, in place
+        -- in the env's own action rows when act is that view, so the step still copies nothing),
+        env.step, the episode statistics of the two row ranges (eval_envs > 0) and remember."""
+        act = self.agent.hold_env(obs_in, act)
         nxt, rew, term, was_reset = self.env.step_transition(act, obs_out=obs_out)
         if self.eval_envs:
             k = self.N - self.eval_envs
@@ -236,7 +257,8 @@ class VectorTrainer:
         # observation and its next_obs the new episode's first -- not a transition
         # (remember_env skips the rows with was_reset != 0); eval transitions are stored like any
         # other (train_ddpg.py:184 remembers unconditionally).  n_step > 1: the step goes into the
-        # learner's n-step windows, which also end at this step's truncated rows
+        # learner's n-step windows, which also end at this step's truncated rows; action_repeat > 1:
+        # into its action-repeat blocks (obs_in and act were latched by the hold where a block began)
         self.agent.remember_env(obs_in, act, rew, nxt, term, was_reset, truncated=self.env.truncated)
         return nxt, rew, term, was_reset
 
@@ -359,6 +381,8 @@ def main():
     ap.add_argument("--eval-envs", type=int, default=0, help="noise-free evaluation envs per GPU (the last K)")
     ap.add_argument("--ou-reset", action="store_true", help="zero an env's OU state when its episode resets")
     ap.add_argument("--n-step", type=int, default=1, help="n-step returns in the replay (1: one-step targets)")
+    ap.add_argument("--action-repeat", type=int, default=1,
+                    help="hold each action for K simulator steps and store one replay row per block (1: off)")
     ap.add_argument("--algo", choices=("ddpg", "td3"), default="ddpg", help="the learner's update rule")
     ap.add_argument("--policy-delay", type=int, default=2, help="td3: actor / target update every N-th update")
     ap.add_argument("--policy-noise", type=float, default=0.2,
@@ -390,7 +414,7 @@ def main():
                        policy_noise=args.policy_noise, noise_clip=args.noise_clip, opponent=args.opponent,
                        selfplay_sync=args.selfplay_sync, selfplay_fraction=args.selfplay_fraction,
                        opponent_speed=args.opponent_speed, opponent_lookahead=args.opponent_lookahead,
-                       opponent_rule=args.opponent_rule)
+                       opponent_rule=args.opponent_rule, action_repeat=args.action_repeat)
     best = -float("inf")
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)

@@ -641,6 +641,55 @@ F110_API int f110_nstep_reset(f110_nstep *ns, const uint8_t *env_mask /* NULL = 
 F110_API int f110_nstep_arrays(f110_nstep *ns, int32_t **len, int32_t **head, double **ret, int32_t **k,
                                float **obs, float **act);
 
+/* ---- action repeat (no reference counterpart: agent.act runs at every simulator step) --
+ * A control interval of `repeat` simulator steps around the env step: the policy's
+ * action is held for a block of up to `repeat` steps and the block is stored as ONE
+ * replay row.  An f110_repeat handle holds per env a phase k (int32; 0: a decision is
+ * due), a running return ret (f64), the block's first observation s_obs[obs_dim] and
+ * its action s_act[act_dim] (f32), and a power table pw[i] = gamma^i (f64, sequential
+ * products, pw[0] = 1, as the n-step table).
+ * f110_repeat_hold runs BEFORE the env step.  Per env:
+ *   k == 0:  s_obs = the obs row, s_act = the act row, decision = 1; the act row stays
+ *            as the policy wrote it;
+ *   k > 0:   the act row = s_act, decision = 0.
+ * f110_repeat_push runs AFTER the env step.  Per env:
+ *   was_reset != 0:  k = 0, nothing is emitted (a NEXT_STEP reset row, or an env reset
+ *                    from outside mid-block: the block is dropped, as the n-step
+ *                    window is);
+ *   otherwise:       ret = (k == 0) ? r : ret + pw[k] * r (product and sum rounded
+ *                    separately; a lone -0.0 survives), k += 1; then, if terminated ||
+ *                    truncated || k == repeat, the row (s_obs, s_act, (float)ret, this
+ *                    push's next_obs row, done) is emitted with done = 1.0f if
+ *                    terminated, else (float)(1.0 - pw[k - 1]), and k = 0.
+ * The done column is the effective done of the n-step section, so the one-step TD
+ * kernels bootstrap a block of k steps with gamma^k.  Envs keep their own phase: an
+ * episode that ends mid-block ends the block, and the env's next decision is due at
+ * the first step of its next episode.
+ * The emitted rows of one push are appended by env ascending, each with the ring's
+ * current max priority: what one f110_replay_add (priority NULL) of those rows would
+ * store.  With repeat == 1 a hold changes no action and a push stores exactly
+ * f110_replay_add_env's rows.  Async on `stream`, no host read and no allocation
+ * after create (capturable in a HIP graph); hold and push of one handle must be
+ * issued on one stream (the next hold overwrites the rows a push reads).
+ * 1 <= repeat <= 64, gamma finite in [0, 1], n_envs >= 1; at push obs_dim / act_dim
+ * must equal the replay's and n_envs must not exceed its capacity (its max_add does
+ * not apply).  decision (u8 [n_envs]) and truncated may be NULL.  The handle takes
+ * n_envs * (obs_dim + act_dim) * 4 bytes plus the small per-env arrays. */
+typedef struct f110_repeat f110_repeat;
+F110_API int f110_repeat_create(f110_repeat **out, int32_t device, int64_t n_envs, int32_t repeat, double gamma,
+                                int32_t obs_dim, int32_t act_dim);
+F110_API int f110_repeat_destroy(f110_repeat *rp);
+F110_API int f110_repeat_hold(f110_repeat *rp, const float *obs, int64_t obs_stride, float *act /* in/out */,
+                              int64_t act_stride, uint8_t *decision /* [n_envs], may be NULL */, void *stream);
+F110_API int f110_repeat_push(f110_repeat *rp, f110_replay *rb, const double *reward, const float *next_obs,
+                              int64_t next_stride, const uint8_t *terminated, const uint8_t *truncated,
+                              const uint8_t *was_reset, void *stream);
+/* Sets k = 0 for the envs with env_mask != 0 (NULL = all); emits nothing. */
+F110_API int f110_repeat_reset(f110_repeat *rp, const uint8_t *env_mask /* NULL = all */, void *stream);
+/* Device views for tests: k [n_envs], ret [n_envs], obs [n_envs][obs_dim],
+ * act [n_envs][act_dim].  Any out pointer may be NULL. */
+F110_API int f110_repeat_arrays(f110_repeat *rp, int32_t **k, double **ret, float **obs, float **act);
+
 /* ---- learner optimizer ----------------------------------------------------------
  * One torch.optim.Adam step (agent.py:187-188: Adam(params, lr), betas
  * (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad) over a network whose

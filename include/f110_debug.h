@@ -312,6 +312,23 @@ F110_API int f110_host_nstep(int64_t n_envs, int32_t n_step, double gamma, int32
                              const uint8_t *was_reset, float *out_obs, float *out_act, float *out_reward,
                              float *out_next_obs, float *out_done, int64_t *out_count);
 
+/* f110_repeat_hold and f110_repeat_push over HOST arrays: the same per-env function the kernel runs
+ * (repeat_update, csrc/f110_repeat.h), envs in ascending order.  k / ret [n_envs], s_obs
+ * [n_envs][obs_dim] and s_act [n_envs][act_dim] are the handle's state (f110_repeat_arrays' layout;
+ * zero = fresh), updated in place; obs / act / next_obs are packed rows.  The hold rewrites act in
+ * place and writes decision [n_envs] (may be NULL).  The push writes the emitted rows, in the order
+ * the device appends them, to out_obs / out_next_obs [.][obs_dim], out_act [.][act_dim], out_reward
+ * / out_done [.] (room for n_envs rows) and their number to out_count.  Same validation
+ * (F110_E_INVALID); capacity > 0 also checks n_envs <= capacity as a push into such a ring would.
+ * Host test hooks: the CPU suite and the GPU tests share one statement of the semantics. */
+F110_API int f110_host_repeat_hold(int64_t n_envs, int32_t obs_dim, int32_t act_dim, const int32_t *k, float *s_obs,
+                                   float *s_act, const float *obs, float *act, uint8_t *decision);
+F110_API int f110_host_repeat_push(int64_t n_envs, int32_t repeat, double gamma, int32_t obs_dim, int32_t act_dim,
+                                   int64_t capacity, int32_t *k, double *ret, const float *s_obs, const float *s_act,
+                                   const double *reward, const float *next_obs, const uint8_t *terminated,
+                                   const uint8_t *truncated, const uint8_t *was_reset, float *out_obs, float *out_act,
+                                   float *out_reward, float *out_next_obs, float *out_done, int64_t *out_count);
+
 /* f110_agent_obs over HOST arrays (same arguments, no stream): the same scan entry the kernels run
  * (obs_scan_value, csrc/f110_env_rows.h) and the same pose-group order.  Same validation
  * (F110_E_INVALID).  Host test hook: the CPU suite and the GPU tests share one statement of the

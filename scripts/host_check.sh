@@ -1,6 +1,6 @@
 #!/bin/bash
-# Build tests/host_check/host_check.cpp with the library's pure host code (csrc/f110_host.cpp) under
-# AddressSanitizer and UBSan, and run it.  CPU only: no offload arch, no device, nothing preloaded.
+# Build tests/host_check/host_check.cpp and tests/host_check/repeat_check.cpp, each with the library's
+# pure host code (csrc/f110_host.cpp), under AddressSanitizer and UBSan, and run them.  CPU only: no offload arch, no device, nothing preloaded.
 #
 #   bash scripts/host_check.sh
 set -euo pipefail
@@ -8,7 +8,9 @@ REPO=$(cd "$(dirname "$0")/.." && pwd)
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 OUT=$(mktemp -d /tmp/f110_host_check_XXXXXX)
 trap 'rm -rf "$OUT"' EXIT
-"$HIPCC" -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wno-option-ignored \
-    "$REPO/tests/host_check/host_check.cpp" "$REPO/f110_gymnasium_ros2_jazzy_amd/csrc/f110_host.cpp" \
-    -o "$OUT/host_check"
-"$OUT/host_check"
+for prog in host_check repeat_check; do
+    "$HIPCC" -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wno-option-ignored \
+        "$REPO/tests/host_check/$prog.cpp" "$REPO/f110_gymnasium_ros2_jazzy_amd/csrc/f110_host.cpp" \
+        -o "$OUT/$prog"
+    "$OUT/$prog"
+done
