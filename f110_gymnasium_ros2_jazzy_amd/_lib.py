@@ -74,6 +74,25 @@ class F110EpisodeTotals(ctypes.Structure):  # f110_episode_totals (zero bytes = 
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class F110RaceParams(ctypes.Structure):  # f110_race_params
+    _fields_ = [("pass_margin", ctypes.c_double), ("direction", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+class F110RaceState(ctypes.Structure):  # f110_race_state (zero bytes = fresh)
+    _fields_ = [("s_prev", ctypes.c_double * 2), ("prog", ctypes.c_double * 2), ("lead0", ctypes.c_double),
+                ("t_max", ctypes.c_double)] + \
+               [(n, ctypes.c_int32) for n in ("len", "passes", "passed", "flags")]
+
+
+class F110RaceTotals(ctypes.Structure):  # f110_race_totals (zero bytes = fresh)
+    _fields_ = [(n, ctypes.c_int64) for n in ("episodes", "ego_crashes", "completed", "truncated", "opp_crashes",
+                                             "ahead_at_end", "passes", "passed", "length_sum")] + \
+               [(n, ctypes.c_double) for n in ("progress_sum", "progress_min", "progress_max", "lead_sum", "t_max")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class F110RayKnobs(ctypes.Structure):  # f110_ray_knobs (include/f110_debug.h)
     _fields_ = [(n, ctypes.c_int32) for n in
                 ("kernel", "lanes", "refill", "fxs_lds", "count_slots", "wtrace", "heavy_list", "heavy_on",
@@ -93,6 +112,10 @@ RAY_TABLES = ("tiled", "rowmajor", "padded")  # F110_TABLE_*
 REWARD_STATE_BYTES = 8 * 12 + 4 * 4   # f110_reward_state
 EPISODE_STATE_BYTES = 16              # f110_episode_state
 EPISODE_TOTALS_BYTES = 56             # f110_episode_totals
+RACE_STATE_BYTES = 64                 # f110_race_state
+RACE_TOTALS_BYTES = 112               # f110_race_totals
+RACE_FLAGS = dict(STARTED=1, CLOSED=2, S0=4, S1=8, AHEAD=16, OPP_CRASHED=32)  # f110_race_state.flags
+RACE_RESULT = dict(finished=1, ego_crash=2, completed=4, truncated=8, opp_crashed=16, ahead_at_end=32)  # result bits
 
 PARAM_FIELDS = tuple(n for n, _ in F110Params._fields_)
 DYN_FIELDS = PARAM_FIELDS[:16]  # the fields a context may hold per env (f110_set_env_params)
@@ -240,6 +263,10 @@ _API = {
     "f110_default_pursuit_params": (None, [ctypes.POINTER(F110PursuitParams)]),
     "f110_pure_pursuit": (_i, [_P, ctypes.POINTER(F110PursuitParams), _P, _i64, _i64, _P, _P, _P, _i64, _P, _P]),
     "f110_host_pure_pursuit": (_i, [_P, ctypes.POINTER(F110PursuitParams), _P, _i64, _i64, _P, _P, _P, _i64, _P]),
+    "f110_default_race_params": (None, [ctypes.POINTER(F110RaceParams)]),
+    "f110_race_scratch_bytes": (_i64, [_i64]),
+    "f110_race_stats": (_i, [_P, ctypes.POINTER(F110RaceParams), _P, _P, _i64, _P, _P, _P, _i64] + [_P] * 9),
+    "f110_host_race_stats": (_i, [_P, ctypes.POINTER(F110RaceParams), _P, _P, _i64, _P, _P, _P, _i64] + [_P] * 7),
 }
 EXPORTS = list(_API)
 

@@ -1,6 +1,6 @@
 // f110_task_args.h — the argument blocks and launchers of the kernels beside the env step: the
 // C-ABI batch kernels, gap-follow, the track, the reward and the pure-pursuit opponent, the episode
-// statistics.
+// and the race statistics.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include "../../include/f110.h"
 #include "f110_env_rows.h"
 #include "f110_map.h"
+#include "f110_race.h"
 
 namespace f110 {
 
@@ -93,6 +94,27 @@ struct EpisodeArgs {
 };
 inline int64_t episode_blocks(int64_t E) { return (E + kEpisodeBlock - 1) / kEpisodeBlock; }
 hipError_t launch_episode_stats(const EpisodeArgs &a, hipStream_t s);
+
+// ---- race statistics (f110_race.hip; the row rule: f110_race.h) --------------
+constexpr int kRaceBlock = 256;    // envs per block of k_race (the documented reduction order, f110.h)
+constexpr int kRaceProjEnvs = 4;   // envs (= waves) per block of k_race_project
+struct RaceArgs {
+    TrackView track;
+    f110_race_params p;
+    const float *ego, *opp;  // (x, y, yaw, col) of env e at ego / opp + e * stride; opp may be null
+    int64_t stride, E;
+    const uint8_t *terminated, *truncated, *was_reset;  // truncated may be null
+    f110_race_state *state;
+    double *cur;             // [E][2] progress, lead, or null
+    double *last_progress, *last_lead;  // the three last_* may be null
+    int32_t *last_length;
+    uint8_t *result;
+    f110_race_totals *totals;
+    RaceProj *proj;          // [E] the call's projections (the caller's scratch)
+    RacePart *part;          // [race_blocks(E)] block partials (the caller's scratch, after proj)
+};
+inline int64_t race_blocks(int64_t E) { return (E + kRaceBlock - 1) / kRaceBlock; }
+hipError_t launch_race_stats(const RaceArgs &a, hipStream_t s);
 
 // ---- the C-ABI batch kernels (f110_batch.hip) and the task kernels ----------------------------
 hipError_t launch_scan_batch(const ScanArgs &a, hipStream_t s);

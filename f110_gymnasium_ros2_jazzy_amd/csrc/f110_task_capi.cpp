@@ -1,8 +1,8 @@
 // f110_task_capi.cpp — the context-free training entry points of include/f110.h: the track of the
 // progress reward (f110_track_*), f110_reward, f110_gap_follow, f110_pure_pursuit with its host
-// statement, the collision batches and the episode statistics.  Argument checks and launches; the
-// kernels are in f110_reward.hip, f110_opponent.hip, f110_pursuit.hip, f110_batch.hip and
-// f110_episode.hip.
+// statement, the race statistics with theirs, the collision batches and the episode statistics.
+// Argument checks and launches; the kernels are in f110_reward.hip, f110_opponent.hip,
+// f110_pursuit.hip, f110_race.hip, f110_batch.hip and f110_episode.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -256,6 +256,104 @@ extern "C" int f110_host_pure_pursuit(const f110_track *track, const f110_pursui
             ax[3] = r.ty;
         }
     }
+    return F110_OK;
+}
+
+// ---- race statistics (f110_race.hip; the row rule: f110_race.h) ------------------------------
+extern "C" void f110_default_race_params(f110_race_params *p) {
+    if (!p) return;
+    f110_params car;
+    f110_default_params(&car);
+    *p = f110_race_params{};
+    p->pass_margin = car.length;
+    p->direction = 1;
+}
+
+extern "C" int64_t f110_race_scratch_bytes(int64_t n_envs) {
+    const int64_t n = n_envs > 0 ? n_envs : 1;
+    return n * (int64_t)sizeof(RaceProj) + race_blocks(n) * (int64_t)sizeof(RacePart);
+}
+
+extern "C" int f110_race_stats(const f110_track *track, const f110_race_params *params, const float *ego,
+                               const float *opp, int64_t stride, const uint8_t *terminated, const uint8_t *truncated,
+                               const uint8_t *was_reset, int64_t n_envs, f110_race_state *state, double *cur,
+                               double *last_progress, double *last_lead, int32_t *last_length, uint8_t *result,
+                               f110_race_totals *totals, void *scratch, void *stream) {
+    if (!track || !scratch || race_bad_args(params, ego, stride, terminated, was_reset, n_envs, state, result, totals))
+        return fail(F110_E_INVALID, "f110_race_stats: bad arguments (a null pointer, stride < 4, n_envs < 0, "
+                                    "pass_margin < 0 or NaN, direction other than +-1)");
+    if (!track->v.mid) return fail(F110_E_INVALID, "f110_race_stats: needs a device track");
+    RaceArgs a{};
+    a.track = track->v;
+    a.p = *params;
+    a.ego = ego;
+    a.opp = opp;
+    a.stride = stride;
+    a.E = n_envs;
+    a.terminated = terminated;
+    a.truncated = truncated;
+    a.was_reset = was_reset;
+    a.state = state;
+    a.cur = cur;
+    a.last_progress = last_progress;
+    a.last_lead = last_lead;
+    a.last_length = last_length;
+    a.result = result;
+    a.totals = totals;
+    a.proj = static_cast<RaceProj *>(scratch);
+    a.part = reinterpret_cast<RacePart *>(a.proj + (n_envs > 0 ? n_envs : 1));
+    HIP_TRY(launch_race_stats(a, (hipStream_t)stream));
+    return F110_OK;
+}
+
+extern "C" int f110_host_race_stats(const f110_track *track, const f110_race_params *params, const float *ego,
+                                    const float *opp, int64_t stride, const uint8_t *terminated,
+                                    const uint8_t *truncated, const uint8_t *was_reset, int64_t n_envs,
+                                    f110_race_state *state, double *cur, double *last_progress, double *last_lead,
+                                    int32_t *last_length, uint8_t *result, f110_race_totals *totals) {
+    if (!track || race_bad_args(params, ego, stride, terminated, was_reset, n_envs, state, result, totals))
+        return fail(F110_E_INVALID, "f110_host_race_stats: bad arguments (a null pointer, stride < 4, n_envs < 0, "
+                                    "pass_margin < 0 or NaN, direction other than +-1)");
+    TrackView T = track->v;  // n, closed, L; the arrays on the host
+    T.xy = track->xy.data();
+    T.s = track->s.data();
+    T.nrm = track->nrm.data();
+    T.mid = track->mid.data();
+    const int has_opp = opp != nullptr;
+    RacePart call = race_part_empty();
+    for (int64_t e = 0; e < n_envs; ++e) {
+        RaceRow r{};
+        const float *cars[2] = {ego + e * stride, has_opp ? opp + e * stride : nullptr};
+        for (int k = 0; k < 2; ++k) {
+            if (!cars[k]) continue;
+            const double x = (double)cars[k][0], y = (double)cars[k][1];
+            r.col[k] = cars[k][3] != 0.0f;
+            if (!(std::isfinite(x) && std::isfinite(y))) continue;
+            const HostProj pj = host_project_xy(T, x, y);
+            r.ok[k] = 1;
+            r.s[k] = pj.s;
+            if (k == 0) r.t0 = pj.t;
+        }
+        r.term = terminated[e];
+        r.trunc = truncated ? truncated[e] : 0;
+        r.was_reset = was_reset[e];
+        r.has_opp = has_opp;
+        f110_race_state &st = state[e];
+        const int res = race_update(*params, T.closed, T.L, r, st);
+        result[e] = (uint8_t)res;
+        const double lead = race_lead(st, has_opp);
+        if (cur) {
+            cur[2 * e] = st.prog[0];
+            cur[2 * e + 1] = lead;
+        }
+        if (res) {
+            if (last_progress) last_progress[e] = st.prog[0];
+            if (last_lead) last_lead[e] = lead;
+            if (last_length) last_length[e] = st.len;
+        }
+        race_merge(call, race_part(res, st, has_opp));
+    }
+    race_totals_add(*totals, call);
     return F110_OK;
 }
 

@@ -1,5 +1,5 @@
 // f110_track_device.h — the centerline projection on the device, shared by the kernels that need
-// a car's place on the track (private; f110_reward.hip, f110_pursuit.hip): the 5 nearest segment
+// a car's place on the track (private; f110_reward.hip, f110_pursuit.hip, f110_race.hip): the 5 nearest segment
 // midpoints of a point (full scan or through the track's grid), CenterlineProgress.project_xy over
 // them, and the searchsorted lookup of an arclength.
 //

@@ -20,6 +20,11 @@ Per vector step, everything on the device:
                 statistics and the eval bookkeeping
   env.step      (:174) with device autoreset (gymnasium NEXT_STEP)
   reward        CenterlineSafetyProgressReward (:127-146, :179) on the device
+  race          with --race-stats (no reference counterpart) the race outcomes per episode on the
+                reward's centerline: progress, lead over the opponent, passes, crash / completed /
+                truncated (race.RaceStats, three launches inside the step graphs); the report gains
+                progress_mean, lead_mean, win_rate, crash_rate and passes_per_episode, and
+                --best-by progress picks best.pt by eval_progress_mean
   remember      (:184) every transition except the reset rows of autoreset steps;
                 with --n-step N as N-step returns (device windows in front of the ring);
                 with --action-repeat K one row per block: the block's first observation and
@@ -64,7 +69,7 @@ class VectorTrainer:
                  algo: str = "ddpg", policy_delay: int = 2, policy_noise: float = 0.2, noise_clip: float = 0.5,
                  opponent: str = "gap_follow", selfplay_sync: int = 1000, selfplay_fraction: float = 1.0,
                  opponent_speed=None, opponent_lookahead: float | None = None, opponent_rule: str = "gap_follow",
-                 action_repeat: int = 1):
+                 action_repeat: int = 1, race_stats: bool = False):
         # action_repeat and the opponent arguments: ValueError before anything is built
         if isinstance(action_repeat, bool) or not isinstance(action_repeat, (int, np.integer)) or \
                 not 1 <= action_repeat <= 64:
@@ -111,11 +116,16 @@ class VectorTrainer:
         # statistics on the device (one kernel pair per step, inside the step graphs)
         # With evaluation envs the trainer keeps the statistics itself, one EpisodeStats over the
         # training rows and one over the eval rows (contiguous row ranges of the step's buffers)
+        # race_stats: the race outcomes beside them (race.RaceStats on the reward's centerline, three
+        # more launches per step, kept the same way: the env's own, or one per row range)
+        self.race_stats = bool(race_stats)
         self.episode_stats = bool(max_episode_steps or stall_steps or self.eval_envs)
         env_kw = dict(map=map_name, num_agents=2, seed=seed, device=self.device, env_offset=env_offset,
                       reward_fn=self.reward_fn, infos="minimal", max_episode_steps=max_episode_steps,
                       stall_speed=stall_speed, stall_steps=stall_steps,
                       episode_stats=self.episode_stats and not self.eval_envs)
+        if self.race_stats and not self.eval_envs:
+            env_kw["race_stats"] = True
         learner = lambda obs_dim: DDPGLearner(  # noqa: E731
             obs_dim=obs_dim, act_dim=2, action_low=ACTION_LOW, action_high=ACTION_HIGH, gamma=0.99, tau=0.005,
             actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size, alpha=0.6, beta=0.4,
@@ -156,6 +166,12 @@ class VectorTrainer:
             self.eval_stats = EpisodeStats(self.eval_envs, device=self.device)
             self._eval_mask = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
             self._eval_mask[self.N - self.eval_envs:] = 1
+        self.train_race = self.eval_race = None
+        if self.eval_envs and self.race_stats:
+            from .race import RaceStats
+            race_kw = dict(ego_idx=0, opponent_idx=self.env.opponent_idx, device=self.device)
+            self.train_race = RaceStats(self.N - self.eval_envs, self.track, self.env.sim.B, **race_kw)
+            self.eval_race = RaceStats(self.eval_envs, self.track, self.env.sim.B, **race_kw)
         if not self.selfplay:
             self.agent = learner(self.env.single_observation_space.shape[0])
         self.warmup = int(warmup_steps)
@@ -175,6 +191,10 @@ class VectorTrainer:
         self._low = torch.tensor(ACTION_LOW, device=self.device)
         self._high = torch.tensor(ACTION_HIGH, device=self.device)
         self.obs, self.info = self.env.reset(seed=seed + rank_seed)
+        if self.train_race is not None:  # the reset observation starts every env's race
+            k = self.N - self.eval_envs
+            self.train_race.begin(self.obs[:k])
+            self.eval_race.begin(self.obs[k:])
         self.global_step = 0
         self.last = None
 
@@ -253,6 +273,9 @@ class VectorTrainer:
             trunc = self.env.truncated
             self.train_stats.update(rew[:k], term[:k], None if trunc is None else trunc[:k], was_reset[:k])
             self.eval_stats.update(rew[k:], term[k:], None if trunc is None else trunc[k:], was_reset[k:])
+            if self.train_race is not None:  # on the obs buffer the reward saw
+                self.train_race.update(nxt[:k], term[:k], None if trunc is None else trunc[:k], was_reset[:k])
+                self.eval_race.update(nxt[k:], term[k:], None if trunc is None else trunc[k:], was_reset[k:])
         # NEXT_STEP autoreset: a reset row's obs is the previous episode's last
         # observation and its next_obs the new episode's first -- not a transition
         # (remember_env skips the rows with was_reset != 0); eval transitions are stored like any
@@ -334,20 +357,39 @@ class VectorTrainer:
         self.track.close()
 
 
+RACE_REPORT_SUMS = ("episodes", "progress_sum", "lead_sum", "ahead_at_end", "ego_crashes", "passes")
+
+
 def episode_report(tr: VectorTrainer, world: int = 1) -> dict:
     """The episodes finished since the last report, summed over ranks on the host (print time only),
     then cleared: episodes, episode_return_mean, episode_length_mean.  With evaluation envs these
-    three cover the training rows, and eval_episodes, eval_return_mean, eval_length_mean the eval rows."""
+    three cover the training rows, and eval_episodes, eval_return_mean, eval_length_mean the eval rows.
+    With race_stats also race_episodes, progress_mean, lead_mean, win_rate, crash_rate and
+    passes_per_episode (and their eval_ twins), from the race totals in the same all-reduce; a
+    trainer that keeps race statistics only (no limits, no evaluation envs) reports those alone."""
+    t = te = None
     if tr.eval_envs:
         t, te = tr.train_stats.totals(), tr.eval_stats.totals()
         tr.train_stats.reset_totals()
         tr.eval_stats.reset_totals()
-    else:
-        t, te = tr.env.episode_totals(), None
+    elif tr.episode_stats:
+        t = tr.env.episode_totals()
         tr.env.reset_episode_totals()
-    v = [float(t["episodes"]), float(t["return_sum"]), float(t["length_sum"])]
-    if te is not None:
-        v += [float(te["episodes"]), float(te["return_sum"]), float(te["length_sum"])]
+    v = []
+    for tot in (t, te):
+        if tot is not None:
+            v += [float(tot["episodes"]), float(tot["return_sum"]), float(tot["length_sum"])]
+    n_ep = len(v)
+    if tr.race_stats:  # the race totals ride in the same vector, after the episode entries
+        if tr.eval_envs:
+            races = [tr.train_race.totals(), tr.eval_race.totals()]
+            tr.train_race.reset_totals()
+            tr.eval_race.reset_totals()
+        else:
+            races = [tr.env.race_totals()]
+            tr.env.reset_race_totals()
+        for r in races:
+            v += [float(r[k]) for k in RACE_REPORT_SUMS]
     if world > 1:
         import torch.distributed as dist
         w = torch.tensor(v, dtype=torch.float64)
@@ -355,13 +397,26 @@ def episode_report(tr: VectorTrainer, world: int = 1) -> dict:
             w = w.to(tr.device)
         dist.all_reduce(w)
         v = w.tolist()
-    n = int(v[0])
-    rep = {"episodes": n, "episode_return_mean": v[1] / n if n else None,
-           "episode_length_mean": v[2] / n if n else None}
+    rep = {}
+    if t is not None:
+        n = int(v[0])
+        rep = {"episodes": n, "episode_return_mean": v[1] / n if n else None,
+               "episode_length_mean": v[2] / n if n else None}
     if te is not None:
         m = int(v[3])
         rep.update(eval_episodes=m, eval_return_mean=v[4] / m if m else None,
                    eval_length_mean=v[5] / m if m else None)
+    if tr.race_stats:
+        w = len(RACE_REPORT_SUMS)
+        for j, prefix in enumerate(("", "eval_") if te is not None else ("",)):
+            ne, prog, lead, ahead, crashes, passes = v[n_ep + j * w:n_ep + (j + 1) * w]
+            ne = int(ne)
+            rep.update({prefix + "race_episodes": ne,
+                        prefix + "progress_mean": prog / ne if ne else None,
+                        prefix + "lead_mean": lead / ne if ne else None,
+                        prefix + "win_rate": ahead / ne if ne else None,
+                        prefix + "crash_rate": crashes / ne if ne else None,
+                        prefix + "passes_per_episode": passes / ne if ne else None})
     return rep
 
 
@@ -401,8 +456,15 @@ def main():
                     help="self: refresh the frozen copy every K learner updates")
     ap.add_argument("--selfplay-fraction", type=float, default=1.0,
                     help="self: share of the envs that race the copy (the others race gap_follow)")
-    ap.add_argument("--save-dir", default=None, help="rank 0 saves best.pt here when eval_return_mean improves")
+    ap.add_argument("--save-dir", default=None, help="rank 0 saves best.pt here when the --best-by figure improves")
+    ap.add_argument("--race-stats", action="store_true",
+                    help="race outcomes on the device: progress, lead, passes, win and crash rates in the report")
+    ap.add_argument("--best-by", choices=("return", "progress"), default="return",
+                    help="what picks best.pt: eval_return_mean, or eval_progress_mean (needs --race-stats and "
+                         "--eval-envs)")
     args = ap.parse_args()
+    if args.best_by == "progress" and not (args.race_stats and args.eval_envs > 0):
+        ap.error("--best-by progress needs --race-stats and --eval-envs")
     rank, world, local = D.init()
     torch.cuda.set_device(D.local_device_index(local))
     shard = D.shard_range(args.envs_per_gpu * world, world, rank)
@@ -414,7 +476,8 @@ def main():
                        policy_noise=args.policy_noise, noise_clip=args.noise_clip, opponent=args.opponent,
                        selfplay_sync=args.selfplay_sync, selfplay_fraction=args.selfplay_fraction,
                        opponent_speed=args.opponent_speed, opponent_lookahead=args.opponent_lookahead,
-                       opponent_rule=args.opponent_rule, action_repeat=args.action_repeat)
+                       opponent_rule=args.opponent_rule, action_repeat=args.action_repeat,
+                       race_stats=args.race_stats)
     best = -float("inf")
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)
@@ -422,8 +485,9 @@ def main():
         rew, term = tr.step()
         ret += rew
         if (k + 1) % 500 == 0:
-            ep = episode_report(tr, world) if tr.episode_stats else {}  # (every rank: a host all-reduce)
-            ev = ep.get("eval_return_mean")
+            # (every rank: a host all-reduce)
+            ep = episode_report(tr, world) if tr.episode_stats or tr.race_stats else {}
+            ev = ep.get("eval_progress_mean" if args.best_by == "progress" else "eval_return_mean")
             if rank == 0 and args.save_dir and ev is not None and ev > best:  # train_ddpg.py:213-216, batched
                 best = ev
                 tr.agent.path = args.save_dir

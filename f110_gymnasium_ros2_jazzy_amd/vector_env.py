@@ -58,6 +58,15 @@ off (the default) truncations stay zeros and the infos keys are unchanged.
 ``infos["episode"]`` = {"r": last finished return, "l": its length, "finished":
 the envs that finished in this step}, ``episode_totals()`` the running totals.
 
+``race_stats=True`` keeps per-env race outcomes on the device (race.RaceStats, three small launches
+per step on the obs buffer the reward sees): ``infos["race"]`` = {"progress": the running episode's
+centerline progress of the ego in m, "lead": its lead over the opponent, "result": the result byte
+of the envs that finished in this step (include/f110.h, "race statistics"), "finished": its bit 0},
+``race_totals()`` the running totals (progress, lead, passes, crashes, win rate).  The centerline is
+``race_track`` (a device reward.CenterlineTrack), by default ``reward_fn.progress``, then
+``opponent_track``; the opponent is agent ``opponent_idx`` when ``num_agents >= 2``; ``race_params``
+= {"pass_margin", "direction"}.  Off (the default) the infos keys are unchanged.
+
 Multi-GPU: give each rank its block of envs (distributed.shard_range) and
 ``env_offset`` = the block's first global id; RNG streams are keyed by global
 env id, so results do not depend on the GPU count.
@@ -83,7 +92,8 @@ class F110VectorEnv:
                  param_ranges=None, param_seed: int | None = None, max_episode_steps: int | None = None,
                  stall_speed: float = 0.0, stall_steps: int | None = None, episode_stats: bool = False,
                  opponent_policy=None, opponent_mask=None, opponent_track=None, opponent_params: dict | None = None,
-                 opponent_speed=None, opponent_rule: str = "gap_follow", **kwargs):
+                 opponent_speed=None, opponent_rule: str = "gap_follow", race_stats: bool = False, race_track=None,
+                 race_params: dict | None = None, **kwargs):
         self.num_envs = int(num_envs)
         self.num_agents = int(num_agents)
         self.params = dict(params or DEFAULT_PARAMS)
@@ -92,6 +102,9 @@ class F110VectorEnv:
                              opponent_params, opponent_speed, opponent_rule, device)
         if param_ranges is not None:  # an unknown field: ValueError before anything is built
             param_range_rows(param_ranges, [{**DEFAULT_PARAMS, **self.params}] * self.num_agents)
+        # race statistics without a usable centerline: ValueError before anything is built
+        race_track = self._check_race(race_stats, race_track, race_params, reward_fn, opponent_track, device,
+                                      int(ego_idx), int(opponent_idx))
         # a bad episode limit: ValueError before anything is built
         limits = BatchSim.check_episode_limits(max_episode_steps, stall_speed, stall_steps)
         self.timestep = timestep
@@ -116,6 +129,12 @@ class F110VectorEnv:
         if episode_stats:
             from .episode import EpisodeStats
             self._episode = EpisodeStats(self.num_envs, device=self.device)
+        self._race = None
+        if race_stats:
+            from .race import RaceStats
+            self._race = RaceStats(self.num_envs, race_track, self.sim.B, ego_idx=ego_idx,
+                                   opponent_idx=int(opponent_idx) if self.num_agents >= 2 else None,
+                                   device=self.device, **(race_params or {}))
         # F110Env.reset computes start_rot in the dtype of its options
         # (f110_env.py:448-451): autoresets and option-less resets follow
         # options_dtype (train_ddpg passes float32 poses); an explicit
@@ -220,6 +239,31 @@ class F110VectorEnv:
             if not (np.isfinite(sp).all() and (sp >= 0.0).all()):
                 raise ValueError("opponent_speed must be finite and >= 0")
 
+    def _check_race(self, race_stats, track, params, reward_fn, opponent_track, device, ego_idx, opponent_idx):
+        """The race-statistics arguments (host values only): the centerline to use, or None when off."""
+        if not race_stats:
+            return None
+        for cand in (track, getattr(reward_fn, "progress", None), opponent_track):
+            if cand is not None:
+                track = cand
+                break
+        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        tdev = getattr(track, "device", None)
+        if track is None or tdev is None or not getattr(track, "handle", None):
+            raise ValueError("race_stats=True needs a centerline: race_track, reward_fn.progress or opponent_track "
+                             "(a device reward.CenterlineTrack)")
+        if tdev.type != dev.type or (tdev.index or 0) != (dev.index or 0):
+            raise ValueError(f"the race track is on {tdev}, the env on {dev}")
+        unknown = sorted(set(params or {}) - {"pass_margin", "direction"})
+        if unknown:
+            raise ValueError(f"unknown race_params {unknown} (known: pass_margin, direction)")
+        pm, d = (params or {}).get("pass_margin"), (params or {}).get("direction", 1)
+        if (pm is not None and not float(pm) >= 0.0) or d not in (1, -1):
+            raise ValueError("race_params: pass_margin must be >= 0 and direction +1 or -1")
+        if self.num_agents >= 2 and (opponent_idx == ego_idx or not 0 <= opponent_idx < self.num_agents):
+            raise ValueError("race_stats: opponent_idx must be another agent than ego_idx")
+        return track
+
     def _opponent_next(self, out, obs=None):
         """Next step's opponent action from this step's outputs: gap_follow from its scan
         (train_ddpg.py:168); "policy": the PolicyOpponent's forward from the opponent's seat (obs: the
@@ -252,6 +296,10 @@ class F110VectorEnv:
             ep = self._episode
             infos["episode"] = {"r": ep.last_return.clone(), "l": ep.last_length.clone(),
                                 "finished": ep.finished.bool()}
+        if self._race is not None:
+            rc = self._race
+            infos["race"] = {"progress": rc.progress.clone(), "lead": rc.lead.clone(), "result": rc.result.clone(),
+                             "finished": rc.finished}
         return infos
 
     def _to_numpy(self, infos):
@@ -295,6 +343,9 @@ class F110VectorEnv:
             self.reward_fn.reset()
         if self._episode is not None:
             self._episode.reset()
+        if self._race is not None:
+            self._race.reset()
+            self._race.begin(out.obs)
         obs = out.obs.clone()
         return (obs.cpu().numpy() if self.as_numpy else obs), self._infos(out)
 
@@ -320,6 +371,8 @@ class F110VectorEnv:
         trunc = out.truncated.bool() if self._limits else torch.zeros_like(term)
         if self._episode is not None:
             self._episode.update(rewards, out.terminated, out.truncated, out.was_reset)
+        if self._race is not None:
+            self._race.update(out.obs, out.terminated, out.truncated, out.was_reset)
         obs = out.obs.clone()
         if self.as_numpy:
             return (obs.cpu().numpy(), rewards.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy(),
@@ -366,6 +419,8 @@ class F110VectorEnv:
                                   torch.full((), self.timestep, dtype=torch.float64, device=self.device))
         if self._episode is not None:
             self._episode.update(rewards, out.terminated, out.truncated, out.was_reset)
+        if self._race is not None:
+            self._race.update(obs, out.terminated, out.truncated, out.was_reset)
         return (obs.clone() if obs_out is None else obs_out), rewards, out.terminated, out.was_reset
 
     @property
@@ -386,6 +441,19 @@ class F110VectorEnv:
         if self._episode is None:
             raise ValueError("reset_episode_totals: build the env with episode_stats=True")
         self._episode.reset_totals()
+
+    def race_totals(self) -> dict:
+        """Totals over the episodes finished since the last reset_race_totals (race_stats=True): the
+        fields of f110_race_totals plus progress_mean, lead_mean, length_mean, win_rate and crash_rate
+        as Python numbers (race.RaceStats.totals).  Waits for the stream."""
+        if self._race is None:
+            raise ValueError("race_totals: build the env with race_stats=True")
+        return self._race.totals()
+
+    def reset_race_totals(self):
+        if self._race is None:
+            raise ValueError("reset_race_totals: build the env with race_stats=True")
+        self._race.reset_totals()
 
     def close(self):
         if getattr(self, "sim", None) is not None:

@@ -503,6 +503,72 @@ F110_API int f110_episode_stats(const double *rewards, const uint8_t *terminated
                                 double *last_return, int32_t *last_length, uint8_t *finished,
                                 f110_episode_totals *totals, void *scratch, void *stream);
 
+/* ---- race statistics (no reference counterpart: train_ddpg.py reports returns only) ------------
+ * Per-env race outcomes of an autoresetting batch -- the ego's progress along the centerline, its
+ * lead over the opponent, passes made and suffered, how the episode ended -- and running totals
+ * over the finished episodes, from each step's observations and flags.  No context; device
+ * pointers; async on `stream`, no host synchronisation, no allocation, no atomics (capturable).
+ * Everything is f64, evaluated left to right, no FMA apart from the projection's own.
+ * Inputs per env e and call: the ego's pose group, four float32 (x, y, yaw, col) at ego + e*stride
+ * (e.g. obs + n_beams + 4*ego_idx, stride f110_outputs.obs_stride), the opponent's at opp +
+ * e*stride (opp == NULL: a single-agent env; there is no opponent part and lead, passes, passed
+ * stay 0), and terminated, truncated (may be NULL), was_reset.  A car with finite x and y is
+ * projected, (s_k, t_k) = CenterlineProgress.project_xy(x_k, y_k), the same function and bits as in
+ * f110_reward and f110_pure_pursuit; a car with a non-finite x or y is "not ok" in this row.
+ * wrap(d): on a closed track, if d > L/2: d -= L; if d < -L/2: d += L; on an open one d.
+ * The rule, in this order:
+ *   1. start row (was_reset != 0, or STARTED not set): the episode's first observation (NEXT_STEP
+ *      autoreset's reset observation).  The state becomes zero, STARTED is set; for each ok car
+ *      s_prev[k] = s_k and S_k is set; lead0 = wrap(direction*(s_0 - s_1)) if both cars are ok,
+ *      else 0; AHEAD is set iff lead0 > 0.  terminated / truncated are ignored.  result = 0.
+ *   2. closed row (CLOSED set: the env ended and was not reset since): ignored, result = 0.
+ *   3. progress: for each ok car, if S_k is set: prog[k] += direction * wrap(s_k - s_prev[k]); then
+ *      s_prev[k] = s_k and S_k is set (a car that is not ok keeps its s_prev).  len += 1.  If the
+ *      ego is ok: t_max = max(t_max, |t_0|).
+ *   4. lead and passes (with an opponent): col_1 != 0 sets OPP_CRASHED.  lead = lead0 + (prog[0] -
+ *      prog[1]).  If AHEAD is clear and lead > pass_margin: AHEAD is set, passes += 1; else if
+ *      AHEAD is set and lead < -pass_margin: AHEAD is cleared, passed += 1.
+ *   5. finish (terminated || truncated): CLOSED is set; result = bit0 finished | bit1 ego crash
+ *      (terminated && col_0 != 0) | bit2 completed (terminated && col_0 == 0: the lap toggles) |
+ *      bit3 truncated (!terminated; terminated wins) | bit4 OPP_CRASHED | bit5 ahead at end
+ *      (opponent present and lead > 0); last_progress = prog[0], last_lead = lead, last_length =
+ *      len, and the env enters the totals with its counts, prog[0], lead, t_max, passes, passed.
+ *   6. otherwise result = 0.
+ * result is written every call; cur [n][2] (may be NULL) receives the state's progress prog[0] and
+ * lead (lead0 + (prog[0] - prog[1]); 0 without an opponent) every call; the last_* arrays (may be
+ * NULL) keep their values where the env does not finish.  Totals accumulate over calls (zero bytes
+ * = fresh; progress_min / progress_max are meaningful only when episodes > 0; t_max is the largest
+ * of the episodes' t_max).  The envs finishing in one call are reduced in f110_episode_stats'
+ * order: blocks of 256 consecutive envs reduce their parts in LDS as a binary tree over the env's
+ * position in the block (entry i += entry i + h for h = 128, 64, .. 1; envs that do not finish
+ * enter as +0.0, or as nothing for min and max), each block stores its partial to scratch, and a
+ * last launch adds the partials in ascending block order, then that sum to the totals.  The same
+ * inputs give the same bits whatever the timing.  scratch: f110_race_scratch_bytes(n_envs) bytes
+ * (the projections of the call and the block partials).
+ * F110_E_INVALID: a null track / params / ego / terminated / was_reset / state / result / totals /
+ * scratch, a host-only track, stride < 4, n_envs < 0, pass_margin negative or NaN, direction other
+ * than +1 / -1. */
+typedef struct f110_race_params {
+    double pass_margin;  /* dead band of the lead, m (0.58, the car's length) */
+    int32_t direction;   /* +1: ascending arclength, -1: descending */
+    int32_t pad_;
+} f110_race_params;
+typedef struct f110_race_state {            /* zero bytes = fresh (not started) */
+    double s_prev[2], prog[2];              /* ego, opp: last arclength; signed progress since the start row, m */
+    double lead0, t_max;                    /* lead at the start row; largest |t| of the ego */
+    int32_t len, passes, passed, flags;     /* flags: 1 STARTED, 2 CLOSED, 4 S0, 8 S1 (s_prev set), 16 AHEAD, 32 OPP_CRASHED */
+} f110_race_state;
+typedef struct f110_race_totals { int64_t episodes, ego_crashes, completed, truncated, opp_crashes, ahead_at_end,
+                                  passes, passed, length_sum;
+                                  double progress_sum, progress_min, progress_max, lead_sum, t_max; } f110_race_totals;
+F110_API void f110_default_race_params(f110_race_params *p);
+F110_API int64_t f110_race_scratch_bytes(int64_t n_envs);
+F110_API int f110_race_stats(const f110_track *track, const f110_race_params *params, const float *ego, const float *opp,
+                             int64_t stride, const uint8_t *terminated, const uint8_t *truncated,
+                             const uint8_t *was_reset, int64_t n_envs, f110_race_state *state, double *cur,
+                             double *last_progress, double *last_lead, int32_t *last_length, uint8_t *result,
+                             f110_race_totals *totals, void *scratch, void *stream);
+
 /* ---- prioritized experience replay ---------------------------------------------
  * Replaces rl_training/DDPG/replay_buffer.py:PrioritizedExperienceReplayBuffer
  * (:6-135), the DDPG agent's memory (agent.py:194): a ring of transitions

@@ -347,6 +347,18 @@ F110_API int f110_host_pure_pursuit(const f110_track *track, const f110_pursuit_
                                     int64_t n_rows, int64_t pose_stride, const double *row_speed,
                                     const uint8_t *row_mask, float *actions, int64_t action_stride, double *aux);
 
+/* f110_race_stats over HOST arrays (same arguments, no scratch, no stream): the projection of
+ * f110_host_pure_pursuit, the same row rule and totals merge (csrc/f110_race.h), envs in ascending
+ * order.  The device differs only in the order progress_sum and lead_sum are added up (f110.h).
+ * Needs only the track's host arrays, so a track built with device < 0 will do.  Same validation
+ * (F110_E_INVALID) otherwise.  Host test hook: the CPU suite and the GPU tests share one statement
+ * of the semantics. */
+F110_API int f110_host_race_stats(const f110_track *track, const f110_race_params *params, const float *ego,
+                                  const float *opp, int64_t stride, const uint8_t *terminated,
+                                  const uint8_t *truncated, const uint8_t *was_reset, int64_t n_envs,
+                                  f110_race_state *state, double *cur, double *last_progress, double *last_lead,
+                                  int32_t *last_length, uint8_t *result, f110_race_totals *totals);
+
 #ifdef __cplusplus
 }
 #endif
