@@ -93,6 +93,12 @@ class F110RaceTotals(ctypes.Structure):  # f110_race_totals (zero bytes = fresh)
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class F110TrackObsParams(ctypes.Structure):  # f110_track_obs_params
+    _fields_ = [(n, ctypes.c_double) for n in ("v_scale", "steer_scale", "yaw_rate_scale", "slip_scale", "lat_scale",
+                                              "gap_scale")] + \
+               [("preview", ctypes.c_double * 8), ("n_preview", ctypes.c_int32), ("direction", ctypes.c_int32)]
+
+
 class F110RayKnobs(ctypes.Structure):  # f110_ray_knobs (include/f110_debug.h)
     _fields_ = [(n, ctypes.c_int32) for n in
                 ("kernel", "lanes", "refill", "fxs_lds", "count_slots", "wtrace", "heavy_list", "heavy_on",
@@ -267,6 +273,11 @@ _API = {
     "f110_race_scratch_bytes": (_i64, [_i64]),
     "f110_race_stats": (_i, [_P, ctypes.POINTER(F110RaceParams), _P, _P, _i64, _P, _P, _P, _i64] + [_P] * 9),
     "f110_host_race_stats": (_i, [_P, ctypes.POINTER(F110RaceParams), _P, _P, _i64, _P, _P, _P, _i64] + [_P] * 7),
+    "f110_default_track_obs_params": (None, [ctypes.POINTER(F110TrackObsParams)]),
+    "f110_track_obs_width": (_i32, [_i32, _i32]),
+    "f110_track_obs": (_i, [_P, ctypes.POINTER(F110TrackObsParams), _P, _i64, _i32, _i32, _i32, _P, _i64, _P]),
+    "f110_ctx_track_obs": (_i, [_P, _P, ctypes.POINTER(F110TrackObsParams), _i32, _i32, _P, _i64, _P]),
+    "f110_host_track_obs": (_i, [_P, ctypes.POINTER(F110TrackObsParams), _P, _i64, _i32, _i32, _i32, _P, _i64]),
 }
 EXPORTS = list(_API)
 

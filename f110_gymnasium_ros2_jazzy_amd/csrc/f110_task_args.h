@@ -1,6 +1,6 @@
 // f110_task_args.h — the argument blocks and launchers of the kernels beside the env step: the
 // C-ABI batch kernels, gap-follow, the track, the reward and the pure-pursuit opponent, the episode
-// and the race statistics.
+// and the race statistics, the track observation.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -115,6 +115,17 @@ struct RaceArgs {
 };
 inline int64_t race_blocks(int64_t E) { return (E + kRaceBlock - 1) / kRaceBlock; }
 hipError_t launch_race_stats(const RaceArgs &a, hipStream_t s);
+
+// ---- track observation (f110_track_obs.hip; the row rule: f110_track_obs.h) -------------------
+struct TrackObsArgs {
+    TrackView track;
+    f110_track_obs_params p;
+    const double *state;  // [7][E*A] f64 (f110_get_state's layout)
+    int64_t E, out_stride;
+    int32_t A, seat, other, width;  // other: -1 = none; width: f110_track_obs_width
+    float *out;           // row e at out + e * out_stride
+};
+hipError_t launch_track_obs(const TrackObsArgs &a, hipStream_t s);
 
 // ---- the C-ABI batch kernels (f110_batch.hip) and the task kernels ----------------------------
 hipError_t launch_scan_batch(const ScanArgs &a, hipStream_t s);

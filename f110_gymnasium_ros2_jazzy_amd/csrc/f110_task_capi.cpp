@@ -1,8 +1,10 @@
 // f110_task_capi.cpp — the context-free training entry points of include/f110.h: the track of the
 // progress reward (f110_track_*), f110_reward, f110_gap_follow, f110_pure_pursuit with its host
-// statement, the race statistics with theirs, the collision batches and the episode statistics.
-// Argument checks and launches; the kernels are in f110_reward.hip, f110_opponent.hip,
-// f110_pursuit.hip, f110_race.hip, f110_batch.hip and f110_episode.hip.
+// statement, the race statistics with theirs, the track observation with its own (and its entry on
+// a context's live state, which needs both the track's and the context's internals), the collision
+// batches and the episode statistics.  Argument checks and launches; the kernels are in
+// f110_reward.hip, f110_opponent.hip, f110_pursuit.hip, f110_race.hip, f110_track_obs.hip,
+// f110_batch.hip and f110_episode.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,12 +15,14 @@
 
 #include "../../include/f110.h"
 #include "../../include/f110_debug.h"
+#include "f110_ctx.h"
 #include "f110_env_rows.h"
 #include "f110_host.h"
 #include "f110_host_util.h"
 #include "f110_pursuit.h"
 #include "f110_step_args.h"
 #include "f110_task_args.h"
+#include "f110_track_obs.h"
 
 using namespace f110;
 
@@ -151,6 +155,7 @@ namespace {
 
 struct HostProj {
     double s, t;
+    int32_t seg;  // the segment (or, from the fallback, the node) s was taken from, as the device's Proj
 };
 
 // CenterlineProgress.project_xy (track_progress.py:58-97) over host arrays: the 5 midpoints of
@@ -178,6 +183,7 @@ HostProj host_project_xy(const TrackView &T, double x, double y) {
     auto bdot = [](double a0, double a1, double b0, double b1) { return std::fma(a1, b1, a0 * b0); };
     bool have = false;
     double bn = 0.0, bs = 0.0, bt = 0.0;
+    int32_t bseg = 0;
     for (int r = 0; r < have5; ++r) {
         const int32_t idx = bi[r];
         const double a0 = T.xy[2 * idx], a1 = T.xy[2 * idx + 1];
@@ -197,6 +203,7 @@ HostProj host_project_xy(const TrackView &T, double x, double y) {
             bn = nrm;
             bs = s_proj;
             bt = t_signed;
+            bseg = idx;
         }
     }
     if (!have) {  // degenerate fallback: nearest node (:93-95)
@@ -210,9 +217,9 @@ HostProj host_project_xy(const TrackView &T, double x, double y) {
                 bj = j;
             }
         }
-        return HostProj{T.s[bj], 0.0};
+        return HostProj{T.s[bj], 0.0, bj};
     }
-    return HostProj{bs, bt};
+    return HostProj{bs, bt, bseg};
 }
 
 }  // namespace
@@ -354,6 +361,125 @@ extern "C" int f110_host_race_stats(const f110_track *track, const f110_race_par
         race_merge(call, race_part(res, st, has_opp));
     }
     race_totals_add(*totals, call);
+    return F110_OK;
+}
+
+// ---- track observation (f110_track_obs.hip; the row rule: f110_track_obs.h) ------------------
+extern "C" void f110_default_track_obs_params(f110_track_obs_params *p) {
+    if (!p) return;
+    *p = f110_track_obs_params{};
+    p->v_scale = 20.0;
+    p->steer_scale = 0.4189;
+    p->yaw_rate_scale = kYawRateCap;
+    p->slip_scale = kSlipCap;
+    p->lat_scale = 1.0;
+    p->gap_scale = 10.0;
+    p->preview[0] = 1.0;
+    p->preview[1] = 2.0;
+    p->preview[2] = 4.0;
+    p->preview[3] = 8.0;
+    p->n_preview = 4;
+    p->direction = 1;
+}
+
+extern "C" int32_t f110_track_obs_width(int32_t n_preview, int32_t has_other) {
+    if (n_preview < 0 || n_preview > kTrackObsMaxPreview) return -1;
+    return track_obs_width(n_preview, has_other != 0);
+}
+
+namespace {
+
+const char kTrackObsBad[] = ": bad arguments (a null pointer, n_envs < 0, n_agents outside 1..8, seat / other outside "
+                            "the agents or equal, out_stride < width, a scale <= 0, n_preview outside 0..8, a preview "
+                            "distance outside (0, L), direction other than +-1)";
+
+int track_obs_launch(const char *fn, const f110_track *track, const f110_track_obs_params *params, const double *state,
+                     int64_t n_envs, int32_t n_agents, int32_t seat, int32_t other, float *out, int64_t out_stride,
+                     void *stream) {
+    if (!track || track_obs_bad_args(params, track->v.L, state, n_envs, n_agents, seat, other, out, out_stride))
+        return fail(F110_E_INVALID, std::string(fn) + kTrackObsBad);
+    if (!track->v.mid) return fail(F110_E_INVALID, std::string(fn) + ": needs a device track");
+    TrackObsArgs a{};
+    a.track = track->v;
+    a.p = *params;
+    a.state = state;
+    a.E = n_envs;
+    a.out_stride = out_stride;
+    a.A = n_agents;
+    a.seat = seat;
+    a.other = other;
+    a.width = track_obs_width(params->n_preview, other >= 0);
+    a.out = out;
+    HIP_TRY(launch_track_obs(a, (hipStream_t)stream));
+    return F110_OK;
+}
+
+}  // namespace
+
+extern "C" int f110_track_obs(const f110_track *track, const f110_track_obs_params *params, const double *state,
+                              int64_t n_envs, int32_t n_agents, int32_t seat, int32_t other, float *out,
+                              int64_t out_stride, void *stream) {
+    return track_obs_launch("f110_track_obs", track, params, state, n_envs, n_agents, seat, other, out, out_stride,
+                            stream);
+}
+
+// on the context's live state: its own buffer goes to the kernel, nothing is copied
+extern "C" int f110_ctx_track_obs(f110_ctx *ctx, const f110_track *track, const f110_track_obs_params *params,
+                                  int32_t seat, int32_t other, float *out, int64_t out_stride, void *stream) {
+    if (!ctx) return fail(F110_E_INVALID, "f110_ctx_track_obs: null context");
+    if (track && track->v.mid && track->arena.device != ctx->arena.device)
+        return fail(F110_E_INVALID, "f110_ctx_track_obs: the track is on another device than the context");
+    if (use_device(ctx) != F110_OK) return F110_E_HIP;
+    return track_obs_launch("f110_ctx_track_obs", track, params, ctx->st, ctx->cfg.n_envs, ctx->cfg.n_agents, seat,
+                            other, out, out_stride, stream);
+}
+
+extern "C" int f110_host_track_obs(const f110_track *track, const f110_track_obs_params *params, const double *state,
+                                   int64_t n_envs, int32_t n_agents, int32_t seat, int32_t other, float *out,
+                                   int64_t out_stride) {
+    if (!track || track_obs_bad_args(params, track->v.L, state, n_envs, n_agents, seat, other, out, out_stride))
+        return fail(F110_E_INVALID, std::string("f110_host_track_obs") + kTrackObsBad);
+    TrackView T = track->v;  // n, closed, L; the arrays on the host
+    T.xy = track->xy.data();
+    T.s = track->s.data();
+    T.tan = track->tan.data();
+    T.nrm = track->nrm.data();
+    T.mid = track->mid.data();
+    const f110_track_obs_params &P = *params;
+    const int np = P.n_preview;
+    const int32_t width = track_obs_width(np, other >= 0);
+    const int64_t EA = n_envs * n_agents;
+    for (int64_t e = 0; e < n_envs; ++e) {
+        float *row = out + e * out_stride;
+        std::fill(row, row + width, 0.0f);  // a row that is not ok, three zeros for such an other car, the pad
+        const TrackObsCar c = track_obs_car(state, EA, e * n_agents + seat);
+        if (!(std::isfinite(c.x) && std::isfinite(c.y) && std::isfinite(c.yaw))) continue;
+        const HostProj pj = host_project_xy(T, c.x, c.y);
+        const int32_t i = pj.seg < T.n - 2 ? pj.seg : T.n - 2;
+        double sn, cs;
+        cr_sincos(c.yaw, sn, cs);
+        double own[kTrackObsOwn];
+        track_obs_own(P, c, pj.t, T.tan[2 * i], T.tan[2 * i + 1], sn, cs, own);
+        for (int j = 0; j < kTrackObsOwn; ++j) row[j] = (float)own[j];
+        for (int j = 0; j < np; ++j) {
+            const double d = P.preview[j];
+            const double sq = track_obs_query(P, d, pj.s, T.closed, T.L);
+            // np.searchsorted(s, sq, side="right") - 1 clipped to [0, n-2]
+            int64_t k = (std::upper_bound(T.s, T.s + T.n, sq) - T.s) - 1;
+            k = std::max<int64_t>(0, std::min<int64_t>(k, T.n - 2));
+            double px, py;
+            track_obs_preview(T.xy, T.s, (int32_t)k, sq, d, c.x, c.y, sn, cs, px, py);
+            row[kTrackObsOwn + 2 * j] = (float)px;
+            row[kTrackObsOwn + 2 * j + 1] = (float)py;
+        }
+        if (other < 0) continue;
+        const TrackObsCar o = track_obs_car(state, EA, e * n_agents + other);
+        if (!(std::isfinite(o.x) && std::isfinite(o.y))) continue;
+        const HostProj po = host_project_xy(T, o.x, o.y);
+        double gap[kTrackObsGap];
+        track_obs_gap(P, T.closed, T.L, pj.s, pj.t, c.v, po.s, po.t, o.v, gap);
+        for (int j = 0; j < kTrackObsGap; ++j) row[kTrackObsOwn + 2 * np + j] = (float)gap[j];
+    }
     return F110_OK;
 }
 

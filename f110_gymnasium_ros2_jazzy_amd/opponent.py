@@ -234,9 +234,15 @@ class PolicyOpponent:
     holds ``act``'s launches sees new weights after a ``load`` without a re-capture.  The action
     bounds are the source actor's at construction.  Device only: a device or actor shape the
     explicit learner path does not take (learner_fused.ExplicitUpdate.actor_supported) is a
-    ValueError -- there is no torch path to keep in step."""
+    ValueError -- there is no torch path to keep in step.
 
-    def __init__(self, actor, n_envs: int, device, lidar_max: float = 30.0):
+    ``track_obs``: a track_obs.TrackObs built for the opponent's seat (``seat=opponent_idx,
+    other=ego_idx``) when the actor takes the track observation after the ``B + 4A`` columns
+    (obs_dim = B + 4A + width); ``act`` then fills the tail of ``obs`` after agent_obs.  It needs
+    the env's simulator, so a trainer that builds the snapshot first hands it over with
+    ``set_track_obs`` once the env exists."""
+
+    def __init__(self, actor, n_envs: int, device, lidar_max: float = 30.0, track_obs=None):
         from .ddpg import Actor, flatten_params
         from .learner_fused import ExplicitUpdate
         self.device = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
@@ -257,7 +263,18 @@ class PolicyOpponent:
         self.flat = flatten_params(self.actor)
         self._scale, self._shift = (t.contiguous() for t in self.actor._affine())
         self.obs = torch.zeros(self.n_envs, self.obs_dim, dtype=torch.float32, device=self.device)
+        self.track_obs = None
+        if track_obs is not None:
+            self.set_track_obs(track_obs)
         self.load(actor)
+
+    def set_track_obs(self, track_obs):
+        """The TrackObs whose block follows the ``B + 4A`` columns of this actor's observation."""
+        sim = track_obs.sim
+        if sim.E != self.n_envs or sim.device != self.device or sim.B + 4 * sim.A + track_obs.width != self.obs_dim:
+            raise ValueError(f"PolicyOpponent: the track observation must be built for {self.n_envs} envs on "
+                             f"{self.device} and fill the actor's {self.obs_dim} columns after B + 4A")
+        self.track_obs = track_obs
 
     @staticmethod
     def _flat_of(actor):
@@ -301,10 +318,16 @@ class PolicyOpponent:
         every env, from the simulator outputs ``sim_out`` (obs: the step's obs tensor when the step
         wrote it elsewhere than sim_out.obs), into ``out_rows`` ([n_envs, act_dim] float32, rows may
         be strided) where row_mask != 0 (None: every row).  Three stages on the current stream:
-        f110_agent_obs into the fixed buffer, fc1 and fc2 on the learner GEMMs over all rows,
-        f110_policy_head_rows."""
+        f110_agent_obs into the fixed buffer (then the track observation's tail, if any), fc1 and
+        fc2 on the learner GEMMs over all rows, f110_policy_head_rows."""
         from .learner_fused import ExplicitUpdate
         agent_obs(sim_out.scans, sim_out.obs if obs is None else obs, agent, self.lidar_max, out=self.obs)
+        head = sim_out.scans.shape[2] + 4 * sim_out.scans.shape[1]
+        if self.track_obs is not None:
+            self.track_obs.fill(self.obs[:, head:])
+        elif self.obs_dim != head:  # (no quiet zeros for columns the actor was trained on)
+            raise ValueError(f"PolicyOpponent: the actor takes {self.obs_dim} columns, the step gives {head}: "
+                             "set_track_obs is missing")
         h2 = ExplicitUpdate.actor_hidden(self.actor, self.obs)
         return policy_head_rows(h2, self.actor.fc3.weight, self.actor.fc3.bias, self._scale, self._shift, out_rows,
                                 row_mask)

@@ -19,6 +19,12 @@ Per vector step, everything on the device:
                 a held row's draw is discarded), as do the opponent, the reward, the episode
                 statistics and the eval bookkeeping
   env.step      (:174) with device autoreset (gymnasium NEXT_STEP)
+  observation   with --track-obs (no reference counterpart) every observation gains the
+                track-relative block of track_obs.TrackObs on the reward's centerline: the ego's speed,
+                steering angle, yaw rate and slip, its lateral offset and heading error, the centerline
+                --track-preview metres ahead in its own frame and the opponent's gap (one more launch
+                inside the step graphs); the learner's obs_dim grows by the block's width, and a
+                self-play snapshot sees the same block from its own seat
   reward        CenterlineSafetyProgressReward (:127-146, :179) on the device
   race          with --race-stats (no reference counterpart) the race outcomes per episode on the
                 reward's centerline: progress, lead over the opponent, passes, crash / completed /
@@ -69,7 +75,7 @@ class VectorTrainer:
                  algo: str = "ddpg", policy_delay: int = 2, policy_noise: float = 0.2, noise_clip: float = 0.5,
                  opponent: str = "gap_follow", selfplay_sync: int = 1000, selfplay_fraction: float = 1.0,
                  opponent_speed=None, opponent_lookahead: float | None = None, opponent_rule: str = "gap_follow",
-                 action_repeat: int = 1, race_stats: bool = False):
+                 action_repeat: int = 1, race_stats: bool = False, track_obs: bool = False, track_preview=None):
         # action_repeat and the opponent arguments: ValueError before anything is built
         if isinstance(action_repeat, bool) or not isinstance(action_repeat, (int, np.integer)) or \
                 not 1 <= action_repeat <= 64:
@@ -91,6 +97,14 @@ class VectorTrainer:
             raise ValueError(f"selfplay_sync must be an integer >= 1; got {selfplay_sync!r}")
         if not 0.0 <= float(selfplay_fraction) <= 1.0:
             raise ValueError(f"selfplay_fraction must be in [0, 1]; got {selfplay_fraction!r}")
+        if track_preview is not None and not track_obs:
+            raise ValueError("track_preview needs track_obs")
+        tobs_kw = None  # F110VectorEnv's track_obs argument
+        if track_obs:
+            from .track_obs import MAX_PREVIEW
+            tobs_kw = {} if track_preview is None else {"preview": tuple(float(d) for d in track_preview)}
+            if len(tobs_kw.get("preview", ())) > MAX_PREVIEW or any(not d > 0.0 for d in tobs_kw.get("preview", ())):
+                raise ValueError(f"track_preview takes at most {MAX_PREVIEW} distances > 0; got {track_preview!r}")
         self.selfplay = opponent == "self"
         self.selfplay_sync, self.selfplay_fraction = int(selfplay_sync), float(selfplay_fraction)
         if self.selfplay:
@@ -126,6 +140,8 @@ class VectorTrainer:
                       episode_stats=self.episode_stats and not self.eval_envs)
         if self.race_stats and not self.eval_envs:
             env_kw["race_stats"] = True
+        if tobs_kw is not None:  # on the reward's centerline (reward_fn.progress)
+            env_kw["track_obs"] = tobs_kw
         learner = lambda obs_dim: DDPGLearner(  # noqa: E731
             obs_dim=obs_dim, act_dim=2, action_low=ACTION_LOW, action_high=ACTION_HIGH, gamma=0.99, tau=0.005,
             actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size, alpha=0.6, beta=0.4,
@@ -146,7 +162,11 @@ class VectorTrainer:
             # the warm-up is raced against
             from . import _lib
             from .opponent import PolicyOpponent, selfplay_mask
-            self.agent = learner(_lib.default_config().n_beams + 4 * 2)
+            tail = 0
+            if tobs_kw is not None:  # the width the env will add (two agents: with the gap columns)
+                from .track_obs import track_obs_params, track_obs_width
+                tail = track_obs_width(track_obs_params(**tobs_kw).n_preview, True)
+            self.agent = learner(_lib.default_config().n_beams + 4 * 2 + tail)
             if self.agent.explicit is None:
                 raise ValueError("opponent='self' needs a learner with the explicit path")
             self.opp = PolicyOpponent(self.agent.actor, self.N, self.device)
@@ -156,6 +176,10 @@ class VectorTrainer:
                                      if mixed else None, opponent_rule=opponent_rule, **pursuit_kw, **env_kw)
             if self.env.single_observation_space.shape[0] != self.agent.obs_dim:
                 raise ValueError("the env's observation size differs from the learner's")
+            if tobs_kw is not None:  # the snapshot's own seat, now that the simulator exists
+                from .track_obs import TrackObs
+                self.opp.set_track_obs(TrackObs(self.env.sim, self.track, seat=self.env.opponent_idx, other=0,
+                                                **tobs_kw))
         else:
             self.env = F110VectorEnv(self.N, opponent=opponent, **pursuit_kw, **env_kw)
         self._synced_at = 0  # the learner update index of the snapshot's last load
@@ -462,7 +486,14 @@ def main():
     ap.add_argument("--best-by", choices=("return", "progress"), default="return",
                     help="what picks best.pt: eval_return_mean, or eval_progress_mean (needs --race-stats and "
                          "--eval-envs)")
+    ap.add_argument("--track-obs", action="store_true",
+                    help="append the track-relative block to every observation: own speed, steering, yaw rate and "
+                         "slip, lateral offset and heading error, a centerline preview and the opponent's gap")
+    ap.add_argument("--track-preview", default=None, metavar="1,2,4,8",
+                    help="--track-obs: the preview distances in metres along the centerline (at most 8)")
     args = ap.parse_args()
+    if args.track_preview is not None and not args.track_obs:
+        ap.error("--track-preview needs --track-obs")
     if args.best_by == "progress" and not (args.race_stats and args.eval_envs > 0):
         ap.error("--best-by progress needs --race-stats and --eval-envs")
     rank, world, local = D.init()
@@ -477,7 +508,9 @@ def main():
                        selfplay_sync=args.selfplay_sync, selfplay_fraction=args.selfplay_fraction,
                        opponent_speed=args.opponent_speed, opponent_lookahead=args.opponent_lookahead,
                        opponent_rule=args.opponent_rule, action_repeat=args.action_repeat,
-                       race_stats=args.race_stats)
+                       race_stats=args.race_stats, track_obs=args.track_obs,
+                       track_preview=None if args.track_preview is None else
+                       [float(d) for d in args.track_preview.split(",") if d.strip()])
     best = -float("inf")
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)
@@ -494,7 +527,7 @@ def main():
                 tr.save_checkpoint("best.pt")
             if rank == 0:
                 st = tr.last or {}
-                print(json.dumps({"step": k + 1, "algo": args.algo,
+                print(json.dumps({"step": k + 1, "algo": args.algo, "obs_dim": tr.agent.obs_dim,
                                   "env_steps_per_s": shard.count * world * (k + 1) / (time.perf_counter() - t0),
                                   "critic_loss": float(st["critic_loss"]) if st else None,
                                   "mean_return": float(ret.mean()), **ep}), flush=True)

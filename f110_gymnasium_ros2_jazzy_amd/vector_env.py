@@ -67,6 +67,17 @@ of the envs that finished in this step (include/f110.h, "race statistics"), "fin
 ``opponent_track``; the opponent is agent ``opponent_idx`` when ``num_agents >= 2``; ``race_params``
 = {"pass_margin", "direction"}.  Off (the default) the infos keys are unchanged.
 
+``track_obs=True`` (or a dict of track_obs.track_obs_params names) appends the track-relative block
+of track_obs.TrackObs to every observation: the ego's speed, steering angle, yaw rate and slip, its
+lateral offset and heading error on the centerline, a preview of the centerline ahead in its own
+frame and, with ``num_agents >= 2``, the gap to agent ``opponent_idx``.  Observations are then
+``[N, B + 4A + width]``: the env owns the wide buffer, the simulator writes its left ``B + 4A``
+columns in place (the rows' stride is the wide width) and one more launch per step fills the tail
+from the simulator's live state.  The centerline is ``obs_track`` (a device
+reward.CenterlineTrack), by default ``reward_fn.progress``, then ``opponent_track``, then
+``race_track``.  The reward, the race statistics and the opponents read the wide rows; the infos are
+unchanged.  Off (the default) nothing differs.
+
 Multi-GPU: give each rank its block of envs (distributed.shard_range) and
 ``env_offset`` = the block's first global id; RNG streams are keyed by global
 env id, so results do not depend on the GPU count.
@@ -93,7 +104,7 @@ class F110VectorEnv:
                  stall_speed: float = 0.0, stall_steps: int | None = None, episode_stats: bool = False,
                  opponent_policy=None, opponent_mask=None, opponent_track=None, opponent_params: dict | None = None,
                  opponent_speed=None, opponent_rule: str = "gap_follow", race_stats: bool = False, race_track=None,
-                 race_params: dict | None = None, **kwargs):
+                 race_params: dict | None = None, track_obs=None, obs_track=None, **kwargs):
         self.num_envs = int(num_envs)
         self.num_agents = int(num_agents)
         self.params = dict(params or DEFAULT_PARAMS)
@@ -102,6 +113,9 @@ class F110VectorEnv:
                              opponent_params, opponent_speed, opponent_rule, device)
         if param_ranges is not None:  # an unknown field: ValueError before anything is built
             param_range_rows(param_ranges, [{**DEFAULT_PARAMS, **self.params}] * self.num_agents)
+        # a track observation without a usable centerline: ValueError before anything is built
+        obs_track, tobs_params = self._check_track_obs(track_obs, obs_track, reward_fn, opponent_track, race_track,
+                                                       device, int(ego_idx), int(opponent_idx))
         # race statistics without a usable centerline: ValueError before anything is built
         race_track = self._check_race(race_stats, race_track, race_params, reward_fn, opponent_track, device,
                                       int(ego_idx), int(opponent_idx))
@@ -143,9 +157,21 @@ class F110VectorEnv:
         self.sim.set_reset_dtype(self.options_dtype)
         B, A = self.sim.B, self.num_agents
         x_min, x_max, y_min, y_max = self.track.bounds
-        self.single_observation_space = _box(
-            np.array([0.0] * B + [x_min, y_min, -np.pi, 0.0] * A, np.float32),
-            np.array([1.0] * B + [x_max, y_max, np.pi, 1.0] * A, np.float32))
+        obs_low = np.array([0.0] * B + [x_min, y_min, -np.pi, 0.0] * A, np.float32)
+        obs_high = np.array([1.0] * B + [x_max, y_max, np.pi, 1.0] * A, np.float32)
+        # the track observation: the env's own wide buffer, whose left B + 4A columns the simulator
+        # writes in place and whose tail TrackObs.fill writes after every step and reset
+        self._tobs = self._wide = None
+        if obs_track is not None:
+            from .track_obs import TrackObs
+            self._tobs = TrackObs(self.sim, obs_track, seat=int(ego_idx),
+                                  other=int(opponent_idx) if A >= 2 else None, **tobs_params)
+            self._head = B + 4 * A
+            self._wide = torch.zeros(self.num_envs, self._head + self._tobs.width, dtype=torch.float32,
+                                     device=self.device)
+            obs_low, obs_high = np.concatenate([obs_low, self._tobs.low]), np.concatenate([obs_high, self._tobs.high])
+        self.obs_dim = int(obs_low.shape[0])
+        self.single_observation_space = _box(obs_low, obs_high)
         low = np.array([self.params["s_min"], self.params["v_min"]], np.float32)
         high = np.array([self.params["s_max"], self.params["v_max"]], np.float32)
         self.single_action_space = _box(np.tile(low, (A, 1)), np.tile(high, (A, 1)))
@@ -164,9 +190,9 @@ class F110VectorEnv:
             raise ValueError("reward_fn must be built for num_envs envs")
         self.opponent_policy = opponent_policy if opponent in ("policy", "mixed") else None
         self.opponent_mask = None
-        if self.opponent_policy is not None and (self.opponent_policy.obs_dim != B + 4 * A
+        if self.opponent_policy is not None and (self.opponent_policy.obs_dim != self.obs_dim
                                                  or self.opponent_policy.device != self.device):
-            raise ValueError(f"opponent_policy must take {B + 4 * A} observations on {self.device}")
+            raise ValueError(f"opponent_policy must take {self.obs_dim} observations on {self.device}")
         # the rule opponent: of every env ("gap_follow", "pure_pursuit"), of the unmasked ones ("mixed")
         self.opponent_rule = {None: None, "policy": None, "mixed": opponent_rule}.get(opponent, opponent)
         self.opponent_track = self._pursuit_params = self._pursuit_speed = None
@@ -238,6 +264,43 @@ class F110VectorEnv:
                 raise ValueError(f"opponent_speed must be one number or an array [{self.num_envs}]")
             if not (np.isfinite(sp).all() and (sp >= 0.0).all()):
                 raise ValueError("opponent_speed must be finite and >= 0")
+
+    def _check_track_obs(self, track_obs, track, reward_fn, opponent_track, race_track, device, ego_idx, opponent_idx):
+        """The track-observation arguments (host values only): (the centerline to use, the parameter
+        dict), or (None, None) when off."""
+        if track_obs is None or track_obs is False:
+            return None, None
+        from .track_obs import MAX_PREVIEW, TRACK_OBS_FIELDS
+        if track_obs is not True and not isinstance(track_obs, dict):
+            raise ValueError("track_obs must be None, True or a dict of track-observation parameters")
+        params = {} if track_obs is True else dict(track_obs)
+        unknown = sorted(set(params) - set(TRACK_OBS_FIELDS))
+        if unknown:
+            raise ValueError(f"unknown track_obs parameters {unknown} (known: {', '.join(TRACK_OBS_FIELDS)})")
+        for cand in (track, getattr(reward_fn, "progress", None), opponent_track, race_track):
+            if cand is not None:
+                track = cand
+                break
+        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        tdev = getattr(track, "device", None)
+        if track is None or tdev is None or not getattr(track, "handle", None):
+            raise ValueError("track_obs needs a centerline: obs_track, reward_fn.progress, opponent_track or "
+                             "race_track (a device reward.CenterlineTrack)")
+        if tdev.type != dev.type or (tdev.index or 0) != (dev.index or 0):
+            raise ValueError(f"the track observation's centerline is on {tdev}, the env on {dev}")
+        if params.get("direction", 1) not in (1, -1):
+            raise ValueError("track_obs: direction must be +1 or -1")
+        prev = [float(d) for d in params.get("preview", ())]
+        if len(prev) > MAX_PREVIEW or any(not 0.0 < d < track.L for d in prev):
+            raise ValueError(f"track_obs: preview takes at most {MAX_PREVIEW} distances in (0, {track.L}) m")
+        for k in set(params) - {"direction", "preview"}:
+            if not float(params[k]) > 0.0:
+                raise ValueError(f"track_obs: {k} must be > 0; got {params[k]!r}")
+        if not 0 <= ego_idx < self.num_agents:
+            raise ValueError("track_obs: ego_idx must be an agent")
+        if self.num_agents >= 2 and (opponent_idx == ego_idx or not 0 <= opponent_idx < self.num_agents):
+            raise ValueError("track_obs: opponent_idx must be another agent than ego_idx")
+        return track, params
 
     def _check_race(self, race_stats, track, params, reward_fn, opponent_track, device, ego_idx, opponent_idx):
         """The race-statistics arguments (host values only): the centerline to use, or None when off."""
@@ -338,16 +401,33 @@ class F110VectorEnv:
         self.sim.set_reset_dtype(dt)
         out = self.sim.reset(options)
         self.sim.set_reset_dtype(self.options_dtype)  # the device autoresets
-        self._opponent_next(out)
+        src = out.obs if self._tobs is None else self._fill_wide(out.obs)
+        self._opponent_next(out, None if self._tobs is None else src)
         if self.reward_fn is not None:
             self.reward_fn.reset()
         if self._episode is not None:
             self._episode.reset()
         if self._race is not None:
             self._race.reset()
-            self._race.begin(out.obs)
-        obs = out.obs.clone()
+            self._race.begin(src)
+        obs = src.clone()
         return (obs.cpu().numpy() if self.as_numpy else obs), self._infos(out)
+
+    def _fill_wide(self, head=None, wide=None):
+        """The wide observation rows (track_obs on): the simulator's ``head`` columns copied into
+        the env's buffer if given (a reset; a step writes them in place), then the tail."""
+        wide = self._wide if wide is None else wide
+        if head is not None:
+            wide[:, :self._head] = head
+        self._tobs.fill(wide[:, self._head:])
+        return wide
+
+    def _check_wide(self, obs_out):
+        if (obs_out.dtype != torch.float32 or obs_out.device != self.device
+                or tuple(obs_out.shape) != (self.num_envs, self.obs_dim) or obs_out.stride(1) != 1
+                or (self.num_envs > 1 and obs_out.stride(0) < self.obs_dim)):
+            raise ValueError(f"obs_out must be a float32 [{self.num_envs}, {self.obs_dim}] tensor on {self.device}, "
+                             "unit column stride")
 
     def step(self, actions):
         a = torch.as_tensor(actions, device=self.device)
@@ -360,10 +440,16 @@ class F110VectorEnv:
             a = self._act
         elif a.dim() == 2 and self.num_agents == 1:
             a = a.unsqueeze(1)
-        out = self.sim.step(a)
-        self._opponent_next(out)
+        if self._tobs is None:
+            out = self.sim.step(a)
+            src = out.obs
+            self._opponent_next(out)
+        else:  # the simulator writes the left columns of the wide rows, one launch fills the tail
+            out = self.sim.step(a, obs_out=self._wide[:, :self._head])
+            src = self._fill_wide()
+            self._opponent_next(out, src)
         if self.reward_fn is not None:  # reset envs: reward_fn.reset(), reward 0 (the u8 flags as they are)
-            rewards = self.reward_fn(out.obs, reset_mask=out.was_reset).clone()
+            rewards = self.reward_fn(src, reset_mask=out.was_reset).clone()
         else:
             rewards = torch.where(out.was_reset.bool(), torch.zeros((), dtype=torch.float64, device=self.device),
                                   torch.full((), self.timestep, dtype=torch.float64, device=self.device))
@@ -372,8 +458,8 @@ class F110VectorEnv:
         if self._episode is not None:
             self._episode.update(rewards, out.terminated, out.truncated, out.was_reset)
         if self._race is not None:
-            self._race.update(out.obs, out.terminated, out.truncated, out.was_reset)
-        obs = out.obs.clone()
+            self._race.update(src, out.terminated, out.truncated, out.was_reset)
+        obs = src.clone()
         if self.as_numpy:
             return (obs.cpu().numpy(), rewards.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy(),
                     self._infos(out))
@@ -398,7 +484,8 @@ class F110VectorEnv:
         With episode limits on, ``self.truncated`` is this step's u8 flag buffer
         (valid until the next step); the 4-tuple is unchanged, and a trainer keeps
         storing ``terminated`` as done: a truncated transition bootstraps from its
-        next_obs, and the reset row after it is skipped like any other."""
+        next_obs, and the reset row after it is skipped like any other.
+        With track_obs on obs_dim is the wide width and obs_out a wide buffer, whose tail is filled too."""
         if self.as_numpy:
             raise ValueError("step_transition: device tensors only (as_numpy=False)")
         a = torch.as_tensor(actions, device=self.device)
@@ -409,8 +496,16 @@ class F110VectorEnv:
             a = self._act
         elif a.dim() == 2 and self.num_agents == 1:
             a = a.unsqueeze(1)
-        out = self.sim.step(a, obs_out=obs_out)  # the simulator writes obs_out itself (no copy)
-        obs = out.obs if obs_out is None else obs_out
+        if self._tobs is None:
+            out = self.sim.step(a, obs_out=obs_out)  # the simulator writes obs_out itself (no copy)
+            obs = out.obs if obs_out is None else obs_out
+        else:  # the left columns of the wide rows (the env's, or obs_out's), then their tail
+            obs = self._wide
+            if obs_out is not None:
+                self._check_wide(obs_out)
+                obs = obs_out
+            out = self.sim.step(a, obs_out=obs[:, :self._head])
+            self._fill_wide(wide=obs)
         self._opponent_next(out, obs)
         if self.reward_fn is not None:
             rewards = self.reward_fn(obs, reset_mask=out.was_reset)

@@ -569,6 +569,68 @@ F110_API int f110_race_stats(const f110_track *track, const f110_race_params *pa
                              double *last_progress, double *last_lead, int32_t *last_length, uint8_t *result,
                              f110_race_totals *totals, void *scratch, void *stream);
 
+/* ---- track observation (no reference counterpart: _pack_flat_obs gives scaled ranges and map poses) --
+ * A track-relative block of observation columns for one seat car `a` of every env, with an optional
+ * other car `o` (-1: none): the seat's own dynamic state, its lateral offset and heading error on
+ * the centerline, a preview of the centerline ahead in the car's frame and the other car's gap.
+ * Meant to be appended after the step's n_beams + 4*n_agents columns (out = obs + n_beams +
+ * 4*n_agents, out_stride = the obs row stride); off unless a caller asks for it.  Everything in
+ * f64, left to right, a*b+c rounded twice; every column is stored as (float)value.
+ *   width = f110_track_obs_width(n_preview, has_other) = 7 + 2*n_preview + (has_other ? 3 : 0),
+ *           rounded up to a multiple of 4; the pad columns are written as +0.
+ * One row, dir = (double)direction, L the track's length, n its node count:
+ *   1. x, y, delta, v, yaw, yaw_rate, slip = the seat's state.  A non-finite x, y or yaw: all width
+ *      columns are +0.
+ *   2. (s_p, t, seg) = CenterlineProgress.project_xy(x, y)       -- f110_reward's projection, same bits
+ *   3. i = min(seg, n-2)  (the projection's nearest-node fallback may return node n-1)
+ *   4. (sn, cs) = cr_sincos(yaw);  5. (tx, ty) = dir * tan[i]
+ *   6. c0 = v/v_scale, c1 = delta/steer_scale, c2 = yaw_rate/yaw_rate_scale, c3 = slip/slip_scale,
+ *      c4 = dir*t/lat_scale
+ *   7. c5 = sn*tx - cs*ty (sine of the heading error), c6 = cs*tx + sn*ty (its cosine)
+ *   8. preview j < n_preview, d = preview[j]: sq = s_p + dir*d, wrapped once on a closed track (if
+ *      sq > L: sq -= L; if sq < 0: sq += L), clamped to [0, L] on an open one; k = searchsorted(s,
+ *      sq, side="right") - 1 clipped to [0, n-2]; u = (sq - s[k]) / (s[k+1] - s[k]) (0 for a
+ *      zero-length segment); target = xy[k] + u*(xy[k+1] - xy[k]); (dx, dy) = target - (x, y);
+ *      c[7+2j] = (cs*dx + sn*dy)/d, c[8+2j] = (-sn*dx + cs*dy)/d
+ *   9. with another car, at columns 7 + 2*n_preview ..: a non-finite x_o or y_o gives three +0;
+ *      otherwise (s_o, t_o) = project_xy(x_o, y_o), g = wrap(dir*(s_o - s_p)) (the race statistics'
+ *      wrap: closed track, if g > L/2: g -= L; if g < -L/2: g += L), and the columns are
+ *      clip(g/gap_scale, -1, 1), dir*(t_o - t)/lat_scale, (v_o - v)/v_scale
+ *  10. the pad columns are +0.
+ * No libm function beyond sqrt enters: the device and the host statement (f110_host_track_obs,
+ * f110_debug.h) agree in every bit. */
+typedef struct f110_track_obs_params {
+    double v_scale;         /* m/s (20.0) */
+    double steer_scale;     /* rad (0.4189) */
+    double yaw_rate_scale;  /* rad/s (10.0) */
+    double slip_scale;      /* rad (pi/3) */
+    double lat_scale;       /* m (1.0) */
+    double gap_scale;       /* m (10.0) */
+    double preview[8];      /* m ahead along the centerline (1, 2, 4, 8); each used one in (0, L) */
+    int32_t n_preview;      /* 0..8 (4) */
+    int32_t direction;      /* +1: ascending arclength, -1: descending */
+} f110_track_obs_params;
+
+/* Host-only helpers.  f110_track_obs_width: the row's width in floats (a multiple of 4), or -1 for
+ * n_preview outside 0..8. */
+F110_API void f110_default_track_obs_params(f110_track_obs_params *p);
+F110_API int32_t f110_track_obs_width(int32_t n_preview, int32_t has_other);
+
+/* state: device [7][n_envs*n_agents] f64 in f110_get_state's layout (car a of env e at column
+ * e*n_agents + a); out: device float32, row e at out + e*out_stride.  One wave per env; no
+ * allocation, no host synchronisation, no atomics (capturable); async on stream.
+ * F110_E_INVALID: a null or host-only track, null params / state / out, n_envs < 0, n_agents outside
+ * 1..8, seat outside [0, n_agents), other neither -1 nor in [0, n_agents) or equal to seat,
+ * out_stride < width, a scale that is not > 0, n_preview outside 0..8, a used preview distance not in
+ * (0, L), direction other than +1 / -1; a NaN among them fails its test. */
+F110_API int f110_track_obs(const f110_track *track, const f110_track_obs_params *params, const double *state,
+                            int64_t n_envs, int32_t n_agents, int32_t seat, int32_t other, float *out,
+                            int64_t out_stride, void *stream);
+/* The same on the context's live state (n_envs, n_agents from the context): no copy is made and no
+ * pointer leaves the library.  The track must be on the context's device. */
+F110_API int f110_ctx_track_obs(f110_ctx *ctx, const f110_track *track, const f110_track_obs_params *params,
+                                int32_t seat, int32_t other, float *out, int64_t out_stride, void *stream);
+
 /* ---- prioritized experience replay ---------------------------------------------
  * Replaces rl_training/DDPG/replay_buffer.py:PrioritizedExperienceReplayBuffer
  * (:6-135), the DDPG agent's memory (agent.py:194): a ring of transitions

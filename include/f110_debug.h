@@ -359,6 +359,15 @@ F110_API int f110_host_race_stats(const f110_track *track, const f110_race_param
                                   f110_race_state *state, double *cur, double *last_progress, double *last_lead,
                                   int32_t *last_length, uint8_t *result, f110_race_totals *totals);
 
+/* f110_track_obs over HOST arrays (same arguments, no stream): the projection of
+ * f110_host_pure_pursuit (with the segment it came from), then the same row rule
+ * (csrc/f110_track_obs.h) -- no libm call but sqrt, so the device's bits.  Needs only the track's
+ * host arrays, so a track built with device < 0 will do.  Same validation (F110_E_INVALID)
+ * otherwise.  Host test hook: the CPU suite and the GPU tests share one statement of the semantics. */
+F110_API int f110_host_track_obs(const f110_track *track, const f110_track_obs_params *params, const double *state,
+                                 int64_t n_envs, int32_t n_agents, int32_t seat, int32_t other, float *out,
+                                 int64_t out_stride);
+
 #ifdef __cplusplus
 }
 #endif
