@@ -13,14 +13,11 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._dev import ptr, stream
 
 
 def _dev(device):
     return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
 
 
 def collision_batch(v1, v2, device=None) -> torch.Tensor:
@@ -32,8 +29,7 @@ def collision_batch(v1, v2, device=None) -> torch.Tensor:
         raise ValueError(f"v1 {tuple(a.shape)} and v2 {tuple(b.shape)} must both be [M, 4, 2]")
     out = torch.empty(a.shape[0], dtype=torch.uint8, device=dev)
     L = _lib.load()
-    _lib.check(L.f110_collision_batch(_ptr(a), _ptr(b), a.shape[0], _ptr(out),
-                                      torch.cuda.current_stream(dev).cuda_stream), "f110_collision_batch")
+    _lib.check(L.f110_collision_batch(ptr(a), ptr(b), a.shape[0], ptr(out), stream(dev)), "f110_collision_batch")
     return out
 
 
@@ -53,6 +49,5 @@ def collision_multiple(verts, device=None):
     col = torch.empty(M, N, dtype=torch.float64, device=dev)
     idx = torch.empty(M, N, dtype=torch.float64, device=dev)
     L = _lib.load()
-    _lib.check(L.f110_collision_multiple(_ptr(v), M, N, _ptr(col), _ptr(idx),
-                                         torch.cuda.current_stream(dev).cuda_stream), "f110_collision_multiple")
+    _lib.check(L.f110_collision_multiple(ptr(v), M, N, ptr(col), ptr(idx), stream(dev)), "f110_collision_multiple")
     return (col[0], idx[0]) if single else (col, idx)

@@ -350,12 +350,9 @@ class DDPGLearner:
         # action_repeat K > 1: the policy's action is held for blocks of up to K simulator steps
         # (hold_env) and remember_env stores one row per block (replay.ActionRepeat); checked here,
         # before any network is built
-        if isinstance(action_repeat, bool) or not isinstance(action_repeat, (int, np.integer)) or \
-                not 1 <= action_repeat <= 64:
-            raise ValueError(f"action_repeat must be an integer in 1..64; got {action_repeat!r}")
-        self.action_repeat = int(action_repeat)
+        from .replay import DeviceReplayBuffer, check_action_repeat
+        self.action_repeat = check_action_repeat(action_repeat)
         if self.action_repeat > 1:
-            from .replay import DeviceReplayBuffer
             if replay != "device" and not isinstance(replay, DeviceReplayBuffer):
                 raise ValueError("action_repeat > 1 needs the device replay buffer")
             if int(n_step) > 1:

@@ -12,19 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-
-
-def _u8(t, n, device, what):
-    if t is None:
-        return None
-    t = torch.as_tensor(t, device=device).reshape(-1)
-    if t.dtype == torch.bool and t.is_contiguous():
-        t = t.view(torch.uint8)
-    elif t.dtype != torch.uint8 or not t.is_contiguous():
-        t = t.to(torch.uint8).contiguous()
-    if t.shape[0] != n:
-        raise ValueError(f"EpisodeStats: {what} must have {n} entries; got {t.shape[0]}")
-    return t
+from ._dev import cuda_device, ptr as P, stream, u8_rows
 
 
 class EpisodeStats:
@@ -38,10 +26,7 @@ class EpisodeStats:
 
     def __init__(self, n_envs: int, device=0):
         self.L = _lib.load()
-        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.F110Error("EpisodeStats runs on a HIP device only (no CPU path)")
-        self.device = dev
+        self.device = dev = cuda_device(device, "EpisodeStats")
         self.n_envs = n = int(n_envs)
         self.state = torch.zeros(n, _lib.EPISODE_STATE_BYTES, dtype=torch.uint8, device=dev)
         self.last_return = torch.zeros(n, dtype=torch.float64, device=dev)
@@ -67,15 +52,13 @@ class EpisodeStats:
             r = r.to(torch.float64).contiguous()
         if r.shape[0] != n:
             raise ValueError(f"EpisodeStats: rewards must have {n} entries; got {r.shape[0]}")
-        te = _u8(terminated, n, self.device, "terminated")
-        tr = _u8(truncated, n, self.device, "truncated")
-        wr = _u8(was_reset, n, self.device, "was_reset")
+        te = u8_rows(terminated, n, self.device, "EpisodeStats: terminated")
+        tr = u8_rows(truncated, n, self.device, "EpisodeStats: truncated")
+        wr = u8_rows(was_reset, n, self.device, "EpisodeStats: was_reset")
         self._keep = (r, te, tr, wr)
-        P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        s = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self.L.f110_episode_stats(P(r), P(te), P(tr), P(wr), n, P(self.state), P(self.last_return),
                                              P(self.last_length), P(self.finished), P(self._totals),
-                                             P(self._scratch), ctypes.c_void_p(s)), "f110_episode_stats")
+                                             P(self._scratch), stream(self.device)), "f110_episode_stats")
 
     def totals(self) -> dict:
         """The running totals as Python numbers (episodes, terminated, truncated, length_sum,
@@ -100,7 +83,6 @@ def host_episode_stats(rewards, terminated, truncated, was_reset, state, last_re
     order.  state: uint8 [n, 16] (f110_episode_state rows); totals: an _lib.F110EpisodeTotals."""
     L = _lib.load()
     n = int(np.asarray(rewards).shape[0])
-    P = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)  # noqa: E731
     for a, dt in ((rewards, np.float64), (terminated, np.uint8), (truncated, np.uint8), (was_reset, np.uint8),
                   (state, np.uint8), (last_return, np.float64), (last_length, np.int32), (finished, np.uint8)):
         if a is not None and (a.dtype != dt or not a.flags.c_contiguous):

@@ -26,6 +26,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._dev import as_device, device_track, ptr, row_stride
+from ._dev import stream as current_stream
 
 ANGLE_MIN = -math.pi / 2          # gap_follow.py:44 defaults
 ANGLE_INCREMENT = math.pi / 1080
@@ -45,22 +47,26 @@ def gap_follow(scans: torch.Tensor, out: torch.Tensor | None = None, angle_min: 
     if out.shape != (M, 2) or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != scans.device:
         raise ValueError("out must be a float32 [M, 2] tensor on the scans' device with unit column stride")
     gaps = torch.empty(M, 2, dtype=torch.int32, device=scans.device) if return_gaps else None
-    L = _lib.load()
-    s = stream if stream is not None else torch.cuda.current_stream(scans.device).cuda_stream
-    _lib.check(L.f110_gap_follow(ctypes.c_void_p(scans.data_ptr()), M, scans.stride(0) if M > 1 else B, B,
-                                 float(angle_min), float(angle_increment), ctypes.c_void_p(out.data_ptr()),
-                                 out.stride(0) if M > 1 else 2,
-                                 ctypes.c_void_p(gaps.data_ptr()) if gaps is not None else None,
-                                 ctypes.c_void_p(s)), "f110_gap_follow")
+    _lib.check(_lib.load().f110_gap_follow(ptr(scans), M, row_stride(scans), B, float(angle_min),
+                                           float(angle_increment), ptr(out), row_stride(out), ptr(gaps),
+                                           current_stream(scans.device, stream)), "f110_gap_follow")
     return (out, gaps) if return_gaps else out
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 # ------------------------------------------------------------- pure pursuit --
 PURSUIT_FIELDS = ("lookahead", "wheelbase", "speed", "a_lat", "v_floor", "steer_limit", "direction")
+
+
+def check_pursuit_speed(speed, n_envs):
+    """opponent_speed (an env's or a trainer's argument): None, one number or one per env, finite
+    and >= 0; host values only."""
+    if speed is None:
+        return
+    sp = np.asarray(speed, dtype=np.float64)
+    if sp.shape not in ((), (int(n_envs),)):
+        raise ValueError(f"opponent_speed must be one number or an array [{int(n_envs)}]")
+    if not (np.isfinite(sp).all() and (sp >= 0.0).all()):
+        raise ValueError("opponent_speed must be finite and >= 0")
 
 
 def pursuit_params(**params) -> "_lib.F110PursuitParams":
@@ -94,8 +100,7 @@ def pure_pursuit(poses: torch.Tensor, track, out: torch.Tensor | None = None, ro
             or poses.stride(1) != 1):
         raise ValueError("poses must be a float32 cuda tensor [M, >= 3] with unit stride along the pose")
     M = poses.shape[0]
-    if getattr(track, "device", None) != poses.device or not getattr(track, "handle", None):
-        raise ValueError("track must be an open reward.CenterlineTrack on the poses' device")
+    device_track(track, poses.device, "track", user="the poses")
     if out is None:
         out = torch.empty(M, 2, dtype=torch.float32, device=poses.device)
     if out.shape != (M, 2) or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != poses.device:
@@ -105,11 +110,9 @@ def pure_pursuit(poses: torch.Tensor, track, out: torch.Tensor | None = None, ro
             raise ValueError(f"{name} must be a contiguous {dt} [M] tensor on the poses' device")
     aux = torch.empty(M, 4, dtype=torch.float64, device=poses.device) if return_aux else None
     p = pursuit_params(**params)
-    s = stream if stream is not None else torch.cuda.current_stream(poses.device).cuda_stream
-    _lib.check(_lib.load().f110_pure_pursuit(track.handle, ctypes.byref(p), _vp(poses), M,
-                                             poses.stride(0) if M > 1 else poses.shape[1], _vp(row_speed),
-                                             _vp(row_mask), _vp(out), out.stride(0) if M > 1 else 2, _vp(aux),
-                                             ctypes.c_void_p(s)), "f110_pure_pursuit")
+    _lib.check(_lib.load().f110_pure_pursuit(track.handle, ctypes.byref(p), ptr(poses), M, row_stride(poses),
+                                             ptr(row_speed), ptr(row_mask), ptr(out), row_stride(out), ptr(aux),
+                                             current_stream(poses.device, stream)), "f110_pure_pursuit")
     return (out, aux) if return_aux else out
 
 
@@ -139,10 +142,10 @@ def host_pure_pursuit(poses: np.ndarray, track, out: np.ndarray | None = None, r
             raise ValueError(f"{name} must have shape [M]")
     aux = np.empty((M, 4), dtype=np.float64) if return_aux else None
     p = pursuit_params(**params)
-    P = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-    _lib.check(_lib.load().f110_host_pure_pursuit(track.handle, ctypes.byref(p), P(poses), M,
-                                                  poses.strides[0] // 4 if M > 1 else poses.shape[1], P(row_speed),
-                                                  P(row_mask), P(out), out.strides[0] // 4 if M > 1 else 2, P(aux)),
+    _lib.check(_lib.load().f110_host_pure_pursuit(track.handle, ctypes.byref(p), ptr(poses), M,
+                                                  poses.strides[0] // 4 if M > 1 else poses.shape[1], ptr(row_speed),
+                                                  ptr(row_mask), ptr(out), out.strides[0] // 4 if M > 1 else 2,
+                                                  ptr(aux)),
                "f110_host_pure_pursuit")
     return (out, aux) if return_aux else out
 
@@ -170,10 +173,8 @@ def agent_obs(scans: torch.Tensor, obs: torch.Tensor, agent: int, lidar_max: flo
             raise ValueError(f"{name} must be a float32 [E, >= B + 4A] tensor on the scans' device, unit column stride")
     if not 0 <= int(agent) < A:
         raise ValueError(f"agent must be in [0, {A}); got {agent}")
-    s = torch.cuda.current_stream(scans.device).cuda_stream
-    _lib.check(_lib.load().f110_agent_obs(_vp(scans), A * B, _vp(obs), obs.stride(0) if E > 1 else obs.shape[1], E, A,
-                                          B, int(agent), float(lidar_max), _vp(out),
-                                          out.stride(0) if E > 1 else out.shape[1], ctypes.c_void_p(s)),
+    _lib.check(_lib.load().f110_agent_obs(ptr(scans), A * B, ptr(obs), row_stride(obs), E, A, B, int(agent),
+                                          float(lidar_max), ptr(out), row_stride(out), current_stream(scans.device)),
                "f110_agent_obs")
     return out
 
@@ -208,10 +209,9 @@ def policy_head_rows(h: torch.Tensor, W: torch.Tensor, b: torch.Tensor, scale: t
     if row_mask is not None and (row_mask.dtype != torch.uint8 or row_mask.shape != (M,) or not row_mask.is_contiguous()
                                  or row_mask.device != h.device):
         raise ValueError("policy_head_rows: row_mask must be a contiguous uint8 [M] tensor on h's device")
-    s = torch.cuda.current_stream(h.device).cuda_stream
-    _lib.check(_lib.load().f110_policy_head_rows(_vp(h), _vp(W), _vp(b), _vp(scale), _vp(shift), M, K, n,
-                                                 _vp(row_mask), _vp(out), out.stride(0) if M > 1 else n,
-                                                 ctypes.c_void_p(s)), "f110_policy_head_rows")
+    _lib.check(_lib.load().f110_policy_head_rows(ptr(h), ptr(W), ptr(b), ptr(scale), ptr(shift), M, K, n,
+                                                 ptr(row_mask), ptr(out), row_stride(out), current_stream(h.device)),
+               "f110_policy_head_rows")
     return out
 
 
@@ -245,7 +245,7 @@ class PolicyOpponent:
     def __init__(self, actor, n_envs: int, device, lidar_max: float = 30.0, track_obs=None):
         from .ddpg import Actor, flatten_params
         from .learner_fused import ExplicitUpdate
-        self.device = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        self.device = as_device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         if not ExplicitUpdate.actor_supported(actor, self.device):

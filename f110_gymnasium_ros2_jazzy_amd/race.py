@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .episode import _u8
+from ._dev import cuda_device, device_track, f32_rows, ptr as P, stream, u8_rows
 
 
 def race_params(pass_margin=None, direction: int = 1) -> "_lib.F110RaceParams":
@@ -44,11 +44,8 @@ class RaceStats:
     def __init__(self, n_envs: int, track, n_beams: int, ego_idx: int = 0, opponent_idx: int | None = 1,
                  pass_margin: float | None = None, direction: int = 1, device=0):
         self.L = _lib.load()
-        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.F110Error("RaceStats runs on a HIP device only (no CPU path)")
-        if track is None or getattr(track, "device", None) is None or not getattr(track, "handle", None):
-            raise ValueError("RaceStats needs a device reward.CenterlineTrack")
+        dev = cuda_device(device, "RaceStats")
+        device_track(track, dev, "the track", "RaceStats needs a device reward.CenterlineTrack", user="RaceStats")
         if opponent_idx is not None and int(opponent_idx) == int(ego_idx):
             raise ValueError("RaceStats: opponent_idx must differ from ego_idx")
         if int(n_beams) < 0 or int(ego_idx) < 0 or (opponent_idx is not None and int(opponent_idx) < 0):
@@ -100,27 +97,22 @@ class RaceStats:
         buffer -- the row stride is the tensor's; flags u8 / bool [n]; truncated may be None).
         Asynchronous on the current stream."""
         n = self.n_envs
-        o = torch.as_tensor(obs, device=self.device)
-        if o.dtype != torch.float32 or o.dim() != 2 or (o.shape[1] > 1 and o.stride(1) != 1):
-            o = o.to(torch.float32).reshape(o.shape[0], -1).contiguous()
+        o, stride = f32_rows(obs, n, None, self.device, "RaceStats: obs")
         need = self.n_beams + 4 * (max(self.ego_idx, self.opponent_idx or 0) + 1)
-        if o.shape[0] != n or o.shape[1] < need:
+        if o.shape[1] < need:
             raise ValueError(f"RaceStats: obs must be [{n}, >= {need}]; got {tuple(o.shape)}")
-        stride = int(o.stride(0)) if n > 1 else max(int(o.stride(0)), int(o.shape[1]))
-        te = _u8(terminated, n, self.device, "terminated")
-        tr = _u8(truncated, n, self.device, "truncated")
-        wr = _u8(was_reset, n, self.device, "was_reset")
+        te = u8_rows(terminated, n, self.device, "RaceStats: terminated")
+        tr = u8_rows(truncated, n, self.device, "RaceStats: truncated")
+        wr = u8_rows(was_reset, n, self.device, "RaceStats: was_reset")
         self._keep = (o, te, tr, wr)
         V = ctypes.c_void_p
-        P = lambda t: None if t is None else V(t.data_ptr())  # noqa: E731
         base = o.data_ptr()
         ego = V(base + 4 * (self.n_beams + 4 * self.ego_idx))
         opp = None if self.opponent_idx is None else V(base + 4 * (self.n_beams + 4 * self.opponent_idx))
-        s = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self.L.f110_race_stats(self.track.handle, ctypes.byref(self.params), ego, opp, stride, P(te), P(tr),
                                           P(wr), n, P(self.state), P(self._cur), P(self.last_progress),
                                           P(self.last_lead), P(self.last_length), P(self.result), P(self._totals),
-                                          P(self._scratch), V(s)), "f110_race_stats")
+                                          P(self._scratch), stream(self.device)), "f110_race_stats")
 
     def totals(self) -> dict:
         """The running totals as Python numbers (the fields of f110_race_totals; progress_min /
@@ -155,7 +147,6 @@ def host_race_stats(track, params, ego, opp, terminated, truncated, was_reset, s
     _lib.F110RaceTotals."""
     L = _lib.load()
     n = int(ego.shape[0])
-    P = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)  # noqa: E731
     for a in (ego, opp):
         if a is not None and (a.dtype != np.float32 or a.ndim != 2 or a.shape[1] < 4 or a.strides[1] != 4 or
                               a.strides[0] % 4 or a.shape[0] != n):

@@ -22,19 +22,8 @@ import ctypes
 import torch
 
 from . import _lib
+from ._dev import cuda_device, f32_rows, ptr, same_device, stream, u8_rows
 
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-
-def _as_u8(t: torch.Tensor) -> torch.Tensor:
-    """Flat uint8 flags; a contiguous bool tensor is reinterpreted (no copy)."""
-    t = t.reshape(-1)
-    if t.dtype == torch.bool and t.is_contiguous():
-        return t.view(torch.uint8)
-    return t.to(torch.uint8).contiguous()
 
 class DeviceReplayBuffer:
     def __init__(self, buffer_size: int, batch_size: int, alpha: float = 0.6, seed: int = 42,
@@ -42,10 +31,7 @@ class DeviceReplayBuffer:
                  max_add: int | None = None):
         if batch_size <= 0 or buffer_size <= 0:
             raise ValueError("buffer_size and batch_size must be positive")  # replay_buffer.py:26
-        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.F110Error("DeviceReplayBuffer runs on a HIP device only (no CPU path)")
-        self.device = dev
+        self.device = dev = cuda_device(device, "DeviceReplayBuffer")
         self.L = _lib.load()
         self._buffer_size = int(buffer_size)
         self._batch_size = int(batch_size)
@@ -73,7 +59,7 @@ class DeviceReplayBuffer:
         self._keep = None
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream(self.device)
 
     # ------------------------------------------------------------------
     def __len__(self) -> int:
@@ -92,8 +78,8 @@ class DeviceReplayBuffer:
         a = self._rows(actions, self.act_dim)
         n = s.shape[0]
         r = torch.as_tensor(rewards, device=self.device).reshape(-1).to(torch.float32).contiguous()
-        d = None if dones is None else _as_u8(torch.as_tensor(dones, device=self.device))
-        m = None if mask is None else _as_u8(torch.as_tensor(mask, device=self.device))
+        d = u8_rows(dones, None, self.device, "dones")
+        m = u8_rows(mask, None, self.device, "mask")
         pr = None if priority is None else \
             torch.as_tensor(priority, device=self.device).reshape(-1).to(torch.float32).contiguous()
         if (pr is not None and pr.shape[0] != n) or ns.shape[0] != n or a.shape[0] != n or r.shape[0] != n or (d is not None and d.shape[0] != n) or \
@@ -103,9 +89,9 @@ class DeviceReplayBuffer:
         for lo in range(0, n, self.max_add):
             hi = min(n, lo + self.max_add)
             _lib.check(self.L.f110_replay_add(
-                self.handle, _p(s[lo:hi]), s.stride(0), _p(a[lo:hi]), a.stride(0), _p(r[lo:hi]), _p(ns[lo:hi]),
-                ns.stride(0), _p(None if d is None else d[lo:hi]), _p(None if pr is None else pr[lo:hi]),
-                _p(None if m is None else m[lo:hi]), hi - lo,
+                self.handle, ptr(s[lo:hi]), s.stride(0), ptr(a[lo:hi]), a.stride(0), ptr(r[lo:hi]), ptr(ns[lo:hi]),
+                ns.stride(0), ptr(None if d is None else d[lo:hi]), ptr(None if pr is None else pr[lo:hi]),
+                ptr(None if m is None else m[lo:hi]), hi - lo,
                 self._stream()), "f110_replay_add")
         self._added += n
 
@@ -134,8 +120,8 @@ class DeviceReplayBuffer:
         for lo in range(0, n, self.max_add):
             hi = min(n, lo + self.max_add)
             _lib.check(self.L.f110_replay_add_env(
-                self.handle, _p(s[lo:hi]), s.stride(0), _p(a[lo:hi]), a.stride(0), _p(r[lo:hi]), _p(ns[lo:hi]),
-                ns.stride(0), _p(d[lo:hi]), _p(m[lo:hi]), hi - lo, self._stream()), "f110_replay_add_env")
+                self.handle, ptr(s[lo:hi]), s.stride(0), ptr(a[lo:hi]), a.stride(0), ptr(r[lo:hi]), ptr(ns[lo:hi]),
+                ns.stride(0), ptr(d[lo:hi]), ptr(m[lo:hi]), hi - lo, self._stream()), "f110_replay_add_env")
         self._added += n
 
     def _rows(self, x, width):
@@ -157,8 +143,8 @@ class DeviceReplayBuffer:
             raise ValueError("batch_size above the buffer's batch_size")
         b = self.batch
         _lib.check(self.L.f110_replay_sample(
-            self.handle, B, float(beta), _p(self.idx), _p(self.weights),
-            *((_p(b["states"]), _p(b["actions"]), _p(b["rewards"]), _p(b["next_states"]), _p(b["dones"]))
+            self.handle, B, float(beta), ptr(self.idx), ptr(self.weights),
+            *((ptr(b["states"]), ptr(b["actions"]), ptr(b["rewards"]), ptr(b["next_states"]), ptr(b["dones"]))
               if gather else (None,) * 5), self._stream()), "f110_replay_sample")
         if B == self._batch_size:
             return self.idx, (b if gather else None), self.weights
@@ -173,7 +159,7 @@ class DeviceReplayBuffer:
         if i.shape != t.shape:
             raise ValueError("update_priorities: idxs and priorities differ in length")
         self._keep_u = (i, t)
-        _lib.check(self.L.f110_replay_update_priorities(self.handle, _p(i), _p(t), i.shape[0], int(bool(td_errors)),
+        _lib.check(self.L.f110_replay_update_priorities(self.handle, ptr(i), ptr(t), i.shape[0], int(bool(td_errors)),
                                                         float(add_eps), self._stream()),
                    "f110_replay_update_priorities")
 
@@ -207,8 +193,8 @@ class DeviceReplayBuffer:
         k = k.contiguous()
         B = int(batch_size or self._batch_size)
         self._keep_k = k
-        _lib.check(self.L.f110_replay_select_keys(self.handle, _p(k), k.shape[0], B, float(beta), _p(self.idx),
-                                                  _p(self.weights), self._stream()), "f110_replay_select_keys")
+        _lib.check(self.L.f110_replay_select_keys(self.handle, ptr(k), k.shape[0], B, float(beta), ptr(self.idx),
+                                                  ptr(self.weights), self._stream()), "f110_replay_select_keys")
         return self.idx[:B], self.weights[:B]
 
     def _select_state(self, **out):
@@ -260,31 +246,91 @@ class DeviceReplayBuffer:
             pass
 
 
-class NStepAccumulator:
+class _EnvWindows:
+    """What NStepAccumulator and ActionRepeat share: a library object of per-env state in front of a
+    DeviceReplayBuffer (entry points f110_<KIND>_create / _destroy / _reset / _arrays), the checks
+    of a step's reward and flag buffers, and the device copies of its arrays."""
+    KIND = None  # "nstep" | "repeat"
+
+    def __init__(self, n_envs, length, gamma, obs_dim, act_dim, device):
+        self.L = _lib.load()
+        self.n_envs, self.gamma = int(n_envs), float(gamma)
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        self.handle = None
+        self.device = dev = cuda_device(device, type(self).__name__)
+        h = ctypes.c_void_p()
+        _lib.check(self._entry("create")(ctypes.byref(h), dev.index or 0, self.n_envs, int(length), self.gamma,
+                                         self.obs_dim, self.act_dim), f"f110_{self.KIND}_create")
+        self.handle = h
+        self._keep = self._keep_h = self._keep_m = None  # a call's inputs, alive until the stream has consumed them
+
+    def _entry(self, name):
+        return getattr(self.L, f"f110_{self.KIND}_{name}")
+
+    def _stream(self):
+        return stream(self.device)
+
+    def _step_flags(self, rewards, terminated, truncated, was_reset, *rows):
+        """push's reward and flag buffers as the simulator writes them, flat (truncated may be None);
+        they and ``rows`` must have n_envs rows."""
+        r, d, m = rewards.reshape(-1), terminated.reshape(-1), was_reset.reshape(-1)
+        t = None if truncated is None else truncated.reshape(-1)
+        if r.dtype != torch.float64 or d.dtype != torch.uint8 or m.dtype != torch.uint8 or \
+                (t is not None and t.dtype != torch.uint8):
+            raise TypeError("push: rewards float64, terminated, truncated and was_reset uint8")
+        if not (r.is_contiguous() and d.is_contiguous() and m.is_contiguous() and (t is None or t.is_contiguous())):
+            raise ValueError("push: contiguous rewards / flags")
+        n = self.n_envs
+        if any(x.shape[0] != n for x in (*rows, r, d, m)) or (t is not None and t.shape[0] != n):
+            raise ValueError(f"push: every input needs n_envs = {n} rows")
+        return r, d, t, m
+
+    def reset(self, env_mask=None):
+        """Drop the pending state of the envs with env_mask != 0 (None: all); nothing is emitted."""
+        m = u8_rows(env_mask, None, self.device, "env_mask")
+        if m is not None and m.shape[0] != self.n_envs:
+            raise ValueError("reset: env_mask needs n_envs entries")
+        self._keep_m = m
+        _lib.check(self._entry("reset")(self.handle, ptr(m), self._stream()), f"f110_{self.KIND}_reset")
+
+    def _copy_arrays(self, spec, first_only=False):
+        """Device copies of the library's arrays: spec = (name, shape, dtype) in f110_<KIND>_arrays'
+        order; first_only: the first array alone (the other pointers are not asked for)."""
+        ptrs = [ctypes.c_void_p() for _ in spec[:1 if first_only else None]]
+        _lib.check(self._entry("arrays")(self.handle, *[ctypes.byref(p) for p in ptrs],
+                                         *[None] * (len(spec) - len(ptrs))), f"f110_{self.KIND}_arrays")
+        out = {}
+        for (name, shape, dt), p in zip(spec, ptrs):
+            out[name] = torch.empty(shape, dtype=dt, device=self.device)
+            _d2d(out[name], p.value, self._stream())
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize(self.device)
+            self._entry("destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NStepAccumulator(_EnvWindows):
     """N-step returns in front of a DeviceReplayBuffer (include/f110.h, "n-step returns"): per env a
     device window of at most ``n_step`` pending (s, a, running return) entries.  ``push`` takes a
     vector env's raw step outputs as ``add_env`` does and appends what leaves the windows to the
     ring: an entry with its n rewards, or every entry of an env whose episode ends.  A stored row's
     done column is the effective done 1 - gamma^(k-1) (1 - done), so the one-step learner
-    bootstraps it with gamma^k.  All on the current torch stream; nothing goes through the host."""
+    bootstraps it with gamma^k.  ``reset`` drops the windows of the masked envs.  All on the current
+    torch stream; nothing goes through the host."""
+    KIND = "nstep"
 
     def __init__(self, n_envs: int, n_step: int, gamma: float, obs_dim: int = 1088, act_dim: int = 2, device=0):
-        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
-        self.L = _lib.load()
-        self.n_envs, self.n_step, self.gamma = int(n_envs), int(n_step), float(gamma)
-        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
-        self.handle = None
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.F110Error("NStepAccumulator runs on a HIP device only (no CPU path)")
-        self.device = dev
-        h = ctypes.c_void_p()
-        _lib.check(self.L.f110_nstep_create(ctypes.byref(h), dev.index or 0, self.n_envs, self.n_step, self.gamma,
-                                            self.obs_dim, self.act_dim), "f110_nstep_create")
-        self.handle = h
-        self._keep = None
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self.n_step = int(n_step)
+        super().__init__(n_envs, n_step, gamma, obs_dim, act_dim, device)
 
     def push(self, memory: DeviceReplayBuffer, states, actions, rewards, next_states, terminated, truncated,
              was_reset):
@@ -294,115 +340,60 @@ class NStepAccumulator:
         s = memory._rows(states, self.obs_dim)
         ns = memory._rows(next_states, self.obs_dim)
         a = memory._rows(actions, self.act_dim)
-        r, d, m = rewards.reshape(-1), terminated.reshape(-1), was_reset.reshape(-1)
-        t = None if truncated is None else truncated.reshape(-1)
-        if r.dtype != torch.float64 or d.dtype != torch.uint8 or m.dtype != torch.uint8 or \
-                (t is not None and t.dtype != torch.uint8):
-            raise TypeError("push: rewards float64, terminated, truncated and was_reset uint8")
-        if not (r.is_contiguous() and d.is_contiguous() and m.is_contiguous() and (t is None or t.is_contiguous())):
-            raise ValueError("push: contiguous rewards / flags")
-        n = self.n_envs
-        if any(x.shape[0] != n for x in (s, ns, a, r, d, m)) or (t is not None and t.shape[0] != n):
-            raise ValueError(f"push: every input needs n_envs = {n} rows")
+        r, d, t, m = self._step_flags(rewards, terminated, truncated, was_reset, s, ns, a)
         self._keep = (s, ns, a, r, d, t, m)  # alive until the stream has consumed them
-        _lib.check(self.L.f110_nstep_push(self.handle, memory.handle, _p(s), s.stride(0), _p(a), a.stride(0), _p(r),
-                                          _p(ns), ns.stride(0), _p(d), _p(t), _p(m), self._stream()),
+        _lib.check(self.L.f110_nstep_push(self.handle, memory.handle, ptr(s), s.stride(0), ptr(a), a.stride(0), ptr(r),
+                                          ptr(ns), ns.stride(0), ptr(d), ptr(t), ptr(m), self._stream()),
                    "f110_nstep_push")
-        memory.note_added(n)  # an upper bound: emitted rows never outnumber pushed rows in total
+        memory.note_added(self.n_envs)  # an upper bound: emitted rows never outnumber pushed rows in total
 
-    def reset(self, env_mask=None):
-        """Drop the windows of the envs with env_mask != 0 (None: all); nothing is emitted."""
-        m = None if env_mask is None else _as_u8(torch.as_tensor(env_mask, device=self.device))
-        if m is not None and m.shape[0] != self.n_envs:
-            raise ValueError("reset: env_mask needs n_envs entries")
-        self._keep_m = m
-        _lib.check(self.L.f110_nstep_reset(self.handle, _p(m), self._stream()), "f110_nstep_reset")
+    def _spec(self):
+        N, n = self.n_envs, self.n_step
+        return [("len", (N,), torch.int32), ("head", (N,), torch.int32), ("ret", (N, n), torch.float64),
+                ("k", (N, n), torch.int32), ("obs", (N, n, self.obs_dim), torch.float32),
+                ("act", (N, n, self.act_dim), torch.float32)]
 
     def arrays(self):
         """Device copies of the windows (tests): len, head [N] int32, ret [N, n] float64, k [N, n]
         int32, obs [N, n, D], act [N, n, A]; entry i of env e sits in slot (head + i) % n."""
-        ptrs = [ctypes.c_void_p() for _ in range(6)]
-        _lib.check(self.L.f110_nstep_arrays(self.handle, *[ctypes.byref(p) for p in ptrs]), "f110_nstep_arrays")
-        N, n = self.n_envs, self.n_step
-        spec = [("len", (N,), torch.int32), ("head", (N,), torch.int32), ("ret", (N, n), torch.float64),
-                ("k", (N, n), torch.int32), ("obs", (N, n, self.obs_dim), torch.float32),
-                ("act", (N, n, self.act_dim), torch.float32)]
-        out = {}
-        for (name, shape, dt), p in zip(spec, ptrs):
-            t = torch.empty(shape, dtype=dt, device=self.device)
-            _d2d(t, p.value, self._stream())
-            out[name] = t
-        return out
+        return self._copy_arrays(self._spec())
 
     def pending(self) -> torch.Tensor:
         """[n_envs] int32 copy of the window lengths."""
-        p = ctypes.c_void_p()
-        _lib.check(self.L.f110_nstep_arrays(self.handle, ctypes.byref(p), None, None, None, None, None),
-                   "f110_nstep_arrays")
-        t = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
-        _d2d(t, p.value, self._stream())
-        return t
-
-    def close(self):
-        if getattr(self, "handle", None):
-            torch.cuda.synchronize(self.device)
-            self.L.f110_nstep_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._copy_arrays(self._spec(), first_only=True)["len"]
 
 
-class ActionRepeat:
+class ActionRepeat(_EnvWindows):
     """Action repeat around a vector env's step (include/f110.h, "action repeat"): per env a device
     phase, the block's first observation and action, and a running return.  ``hold`` runs before the
     env step: envs whose decision is due keep the policy's action and latch it with the observation;
     the others get their held action written over the policy's.  ``push`` runs after it and appends
     one row per finished block to the ring -- a block is finished after ``repeat`` steps or when its
     episode ends -- with the effective done 1 - gamma^(k-1) (1 - done), so the one-step learner
-    bootstraps it with gamma^k.  All on the current torch stream; nothing goes through the host."""
+    bootstraps it with gamma^k.  ``reset`` drops the running blocks of the masked envs: a decision is
+    due at their next hold.  All on the current torch stream; nothing goes through the host."""
+    KIND = "repeat"
 
     def __init__(self, n_envs: int, repeat: int, gamma: float, obs_dim: int = 1088, act_dim: int = 2, device=0):
-        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
-        self.L = _lib.load()
-        self.n_envs, self.repeat, self.gamma = int(n_envs), int(repeat), float(gamma)
-        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
-        self.handle = None
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.F110Error("ActionRepeat runs on a HIP device only (no CPU path)")
-        self.device = dev
-        h = ctypes.c_void_p()
-        _lib.check(self.L.f110_repeat_create(ctypes.byref(h), dev.index or 0, self.n_envs, self.repeat, self.gamma,
-                                             self.obs_dim, self.act_dim), "f110_repeat_create")
-        self.handle = h
-        self.decision = torch.zeros(self.n_envs, dtype=torch.uint8, device=dev)  # written by the last hold
-        self._keep = self._keep_h = None
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self.repeat = int(repeat)
+        super().__init__(n_envs, repeat, gamma, obs_dim, act_dim, device)
+        self.decision = torch.zeros(self.n_envs, dtype=torch.uint8, device=self.device)  # written by the last hold
 
     def _rows(self, x, width, what):
-        """x as [n_envs, width] float32 rows of unit inner stride, WITHOUT a copy (hold writes in place)."""
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device.type != "cuda" or \
-                (x.device.index or 0) != (self.device.index or 0):
+        """x as [n_envs, width] float32 rows of unit inner stride, WITHOUT a copy (hold writes in
+        place), and their row stride."""
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not same_device(x.device, self.device):
             raise TypeError(f"{what}: a float32 tensor on {self.device}")
-        if x.dim() != 2 or x.shape[1] != width or x.stride(1) != 1 or x.stride(0) < width:
-            raise ValueError(f"{what}: [n_envs, {width}] rows of unit inner stride (views are fine, copies are not)")
-        if x.shape[0] != self.n_envs:
-            raise ValueError(f"{what}: every input needs n_envs = {self.n_envs} rows")
-        return x
+        return f32_rows(x, self.n_envs, width, self.device, what, copy_ok=False)
 
     def hold(self, obs, act):
         """Before the env step.  obs [n_envs, obs_dim], act [n_envs, act_dim]: float32 device
         tensors or strided row views of them; act is rewritten in place and returned.
         ``decision`` [n_envs] uint8 is 1 where the policy's action was kept."""
-        s = self._rows(obs, self.obs_dim, "hold: obs")
-        a = self._rows(act, self.act_dim, "hold: act")
+        s, s_stride = self._rows(obs, self.obs_dim, "hold: obs")
+        a, a_stride = self._rows(act, self.act_dim, "hold: act")
         self._keep_h = (s, a)  # alive until the stream has consumed them
-        _lib.check(self.L.f110_repeat_hold(self.handle, _p(s), s.stride(0), _p(a), a.stride(0), _p(self.decision),
+        _lib.check(self.L.f110_repeat_hold(self.handle, ptr(s), s_stride, ptr(a), a_stride, ptr(self.decision),
                                            self._stream()), "f110_repeat_hold")
         return act
 
@@ -411,63 +402,34 @@ class ActionRepeat:
         rewards float64, terminated / truncated / was_reset uint8 device tensors as the simulator
         writes them (truncated may be None: no episode limits); ``n_envs`` rows each."""
         ns = memory._rows(next_obs, self.obs_dim)
-        r, d, m = rewards.reshape(-1), terminated.reshape(-1), was_reset.reshape(-1)
-        t = None if truncated is None else truncated.reshape(-1)
-        if r.dtype != torch.float64 or d.dtype != torch.uint8 or m.dtype != torch.uint8 or \
-                (t is not None and t.dtype != torch.uint8):
-            raise TypeError("push: rewards float64, terminated, truncated and was_reset uint8")
-        if not (r.is_contiguous() and d.is_contiguous() and m.is_contiguous() and (t is None or t.is_contiguous())):
-            raise ValueError("push: contiguous rewards / flags")
-        n = self.n_envs
-        if any(x.shape[0] != n for x in (ns, r, d, m)) or (t is not None and t.shape[0] != n):
-            raise ValueError(f"push: every input needs n_envs = {n} rows")
+        r, d, t, m = self._step_flags(rewards, terminated, truncated, was_reset, ns)
         self._keep = (ns, r, d, t, m)  # alive until the stream has consumed them
-        _lib.check(self.L.f110_repeat_push(self.handle, memory.handle, _p(r), _p(ns), ns.stride(0), _p(d), _p(t), _p(m),
-                                           self._stream()), "f110_repeat_push")
-        memory.note_added(n)  # an upper bound: at most one row per env and push
+        _lib.check(self.L.f110_repeat_push(self.handle, memory.handle, ptr(r), ptr(ns), ns.stride(0), ptr(d), ptr(t),
+                                           ptr(m), self._stream()), "f110_repeat_push")
+        memory.note_added(self.n_envs)  # an upper bound: at most one row per env and push
 
-    def reset(self, env_mask=None):
-        """A decision is due at the next hold for the envs with env_mask != 0 (None: all); their
-        running blocks are dropped and nothing is emitted."""
-        m = None if env_mask is None else _as_u8(torch.as_tensor(env_mask, device=self.device))
-        if m is not None and m.shape[0] != self.n_envs:
-            raise ValueError("reset: env_mask needs n_envs entries")
-        self._keep_m = m
-        _lib.check(self.L.f110_repeat_reset(self.handle, _p(m), self._stream()), "f110_repeat_reset")
+    def _spec(self):
+        N = self.n_envs
+        return [("k", (N,), torch.int32), ("ret", (N,), torch.float64), ("obs", (N, self.obs_dim), torch.float32),
+                ("act", (N, self.act_dim), torch.float32)]
 
     def arrays(self):
         """Device copies of the state (tests): k [N] int32, ret [N] float64, obs [N, D], act [N, A]."""
-        ptrs = [ctypes.c_void_p() for _ in range(4)]
-        _lib.check(self.L.f110_repeat_arrays(self.handle, *[ctypes.byref(p) for p in ptrs]), "f110_repeat_arrays")
-        N = self.n_envs
-        spec = [("k", (N,), torch.int32), ("ret", (N,), torch.float64), ("obs", (N, self.obs_dim), torch.float32),
-                ("act", (N, self.act_dim), torch.float32)]
-        out = {}
-        for (name, shape, dt), p in zip(spec, ptrs):
-            t = torch.empty(shape, dtype=dt, device=self.device)
-            _d2d(t, p.value, self._stream())
-            out[name] = t
-        return out
+        return self._copy_arrays(self._spec())
 
     def phase(self) -> torch.Tensor:
         """[n_envs] int32 copy of the phases (0: a decision is due)."""
-        p = ctypes.c_void_p()
-        _lib.check(self.L.f110_repeat_arrays(self.handle, ctypes.byref(p), None, None, None), "f110_repeat_arrays")
-        t = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
-        _d2d(t, p.value, self._stream())
-        return t
+        return self._copy_arrays(self._spec(), first_only=True)["k"]
 
-    def close(self):
-        if getattr(self, "handle", None):
-            torch.cuda.synchronize(self.device)
-            self.L.f110_repeat_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def check_action_repeat(action_repeat) -> int:
+    """action_repeat (a trainer's or a learner's argument) as an int: a ValueError unless it is an
+    integer in 1..64."""
+    import numpy as np
+    if isinstance(action_repeat, bool) or not isinstance(action_repeat, (int, np.integer)) or \
+            not 1 <= action_repeat <= 64:
+        raise ValueError(f"action_repeat must be an integer in 1..64; got {action_repeat!r}")
+    return int(action_repeat)
 
 
 def host_repeat_state(n_envs: int, obs_dim: int, act_dim: int) -> dict:
@@ -489,34 +451,35 @@ def host_repeat_hold(state: dict, obs, act):
     obs = np.ascontiguousarray(obs, np.float32).reshape(N, D)
     act = np.array(act, np.float32, order="C").reshape(N, A)  # (a copy: the caller's rows stay)
     decision = np.empty(N, np.uint8)
-    _lib.check(L.f110_host_repeat_hold(N, D, A, *[ctypes.c_void_p(x.ctypes.data) for x in
-                                                  (state["k"], state["obs"], state["act"], obs, act, decision)]),
-               "f110_host_repeat_hold")
+    _lib.check(L.f110_host_repeat_hold(N, D, A, *[ptr(x) for x in (state["k"], state["obs"], state["act"], obs, act,
+                                                                   decision)]), "f110_host_repeat_hold")
     return act, decision
+
+
+def _host_push_io(N, D, A, max_rows, reward, next_obs, terminated, truncated, was_reset):
+    """A host push's step inputs as the C arrays the library reads, and the arrays it emits into:
+    (reward, next_obs, flags, out rows (obs, act, reward, next_obs, done), the emitted-row count)."""
+    import numpy as np
+    next_obs = np.ascontiguousarray(next_obs, np.float32).reshape(N, D)
+    reward = np.ascontiguousarray(reward, np.float64).reshape(N)
+    flags = [None if f is None else np.ascontiguousarray(f, np.uint8).reshape(N)
+             for f in (terminated, truncated, was_reset)]
+    out = [np.empty((max_rows, D), np.float32), np.empty((max_rows, A), np.float32), np.empty(max_rows, np.float32),
+           np.empty((max_rows, D), np.float32), np.empty(max_rows, np.float32)]
+    return reward, next_obs, flags, out, ctypes.c_int64()
 
 
 def host_repeat_push(state: dict, repeat, gamma, reward, next_obs, terminated, truncated, was_reset,
                      capacity: int = 0):
     """One push on the host (f110_host_repeat_push) over NumPy arrays.  Returns the emitted rows
     (obs, act, reward, next_obs, done) in the order the device appends them."""
-    import numpy as np
-    L = _lib.load()
     N, D = state["obs"].shape
     A = state["act"].shape[1]
-    next_obs = np.ascontiguousarray(next_obs, np.float32).reshape(N, D)
-    reward = np.ascontiguousarray(reward, np.float64).reshape(N)
-    flags = [None if f is None else np.ascontiguousarray(f, np.uint8).reshape(N)
-             for f in (terminated, truncated, was_reset)]
-    out = [np.empty((N, D), np.float32), np.empty((N, A), np.float32), np.empty(N, np.float32),
-           np.empty((N, D), np.float32), np.empty(N, np.float32)]
-    cnt = ctypes.c_int64()
-
-    def ptr(x):
-        return None if x is None else ctypes.c_void_p(x.ctypes.data)
-    _lib.check(L.f110_host_repeat_push(N, int(repeat), float(gamma), D, A, int(capacity),
-                                       *[ptr(state[q]) for q in ("k", "ret", "obs", "act")], ptr(reward),
-                                       ptr(next_obs), *[ptr(f) for f in flags], *[ptr(x) for x in out],
-                                       ctypes.byref(cnt)), "f110_host_repeat_push")
+    reward, next_obs, flags, out, cnt = _host_push_io(N, D, A, N, reward, next_obs, terminated, truncated, was_reset)
+    _lib.check(_lib.load().f110_host_repeat_push(N, int(repeat), float(gamma), D, A, int(capacity),
+                                                 *[ptr(state[q]) for q in ("k", "ret", "obs", "act")], ptr(reward),
+                                                 ptr(next_obs), *[ptr(f) for f in flags], *[ptr(x) for x in out],
+                                                 ctypes.byref(cnt)), "f110_host_repeat_push")
     return tuple(x[:cnt.value] for x in out)
 
 
@@ -525,24 +488,16 @@ def host_nstep(state: dict, gamma, obs, act, reward, next_obs, terminated, trunc
     ``host_nstep_state`` makes them, updated in place.  Returns the emitted rows
     (obs, act, reward, next_obs, done) in the order the device appends them."""
     import numpy as np
-    L = _lib.load()
     N, n = state["ret"].shape
     D, A = state["obs"].shape[2], state["act"].shape[2]
-    obs, next_obs = (np.ascontiguousarray(x, np.float32).reshape(N, D) for x in (obs, next_obs))
+    obs = np.ascontiguousarray(obs, np.float32).reshape(N, D)
     act = np.ascontiguousarray(act, np.float32).reshape(N, A)
-    reward = np.ascontiguousarray(reward, np.float64).reshape(N)
-    flags = [None if f is None else np.ascontiguousarray(f, np.uint8).reshape(N)
-             for f in (terminated, truncated, was_reset)]
-    out = [np.empty((N * n, D), np.float32), np.empty((N * n, A), np.float32), np.empty(N * n, np.float32),
-           np.empty((N * n, D), np.float32), np.empty(N * n, np.float32)]
-    cnt = ctypes.c_int64()
-
-    def ptr(x):
-        return None if x is None else ctypes.c_void_p(x.ctypes.data)
-    _lib.check(L.f110_host_nstep(N, n, float(gamma), D, A, int(capacity),
-                                 *[ptr(state[q]) for q in ("len", "head", "ret", "k", "obs", "act")],
-                                 ptr(obs), ptr(act), ptr(reward), ptr(next_obs), *[ptr(f) for f in flags],
-                                 *[ptr(x) for x in out], ctypes.byref(cnt)), "f110_host_nstep")
+    reward, next_obs, flags, out, cnt = _host_push_io(N, D, A, N * n, reward, next_obs, terminated, truncated,
+                                                      was_reset)
+    _lib.check(_lib.load().f110_host_nstep(N, n, float(gamma), D, A, int(capacity),
+                                           *[ptr(state[q]) for q in ("len", "head", "ret", "k", "obs", "act")],
+                                           ptr(obs), ptr(act), ptr(reward), ptr(next_obs), *[ptr(f) for f in flags],
+                                           *[ptr(x) for x in out], ctypes.byref(cnt)), "f110_host_nstep")
     return tuple(x[:cnt.value] for x in out)
 
 

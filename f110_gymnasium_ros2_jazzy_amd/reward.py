@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._dev import cuda_device, ptr, stream, u8_rows
 
 
 def load_centerline_csv(path: str):
@@ -118,10 +119,7 @@ class BatchedCenterlineReward:
         self.progress = progress
         self.n_envs = int(n_envs)
         self.num_beams = int(num_beams)
-        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise _lib.F110Error("BatchedCenterlineReward runs on a HIP device only (no CPU path)")
-        self.device = dev
+        self.device = dev = cuda_device(device, "BatchedCenterlineReward")
         self.state = torch.zeros(self.n_envs, _lib.REWARD_STATE_BYTES, dtype=torch.uint8, device=dev)
         self.rewards = torch.zeros(self.n_envs, dtype=torch.float64, device=dev)
 
@@ -141,15 +139,10 @@ class BatchedCenterlineReward:
         if o.dtype != torch.float32:
             o = o.to(torch.float32)
         o = o.reshape(self.n_envs, -1).contiguous()
-        m = None
-        if reset_mask is not None:
-            m = torch.as_tensor(reset_mask, device=self.device).reshape(-1)
-            m = m.view(torch.uint8) if m.dtype == torch.bool and m.is_contiguous() else m.to(torch.uint8).contiguous()
+        m = u8_rows(reset_mask, None, self.device, "reset_mask")
         self._keep = (o, m)
-        s = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self.L_lib.f110_reward(
-            self.progress.handle if self.progress is not None else None, ctypes.byref(self.params),
-            ctypes.c_void_p(o.data_ptr()), self.n_envs, o.shape[1], self.num_beams,
-            ctypes.c_void_p(self.state.data_ptr()), ctypes.c_void_p(m.data_ptr()) if m is not None else None,
-            ctypes.c_void_p(self.rewards.data_ptr()), ctypes.c_void_p(s)), "f110_reward")
+            self.progress.handle if self.progress is not None else None, ctypes.byref(self.params), ptr(o),
+            self.n_envs, o.shape[1], self.num_beams, ptr(self.state), ptr(m), ptr(self.rewards),
+            stream(self.device)), "f110_reward")
         return self.rewards

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._dev import as_device, f32_rows, ptr, stream
 from .maps import TrackMap, load_map
 
 
@@ -30,10 +31,6 @@ class StepOut:
     sim_time: torch.Tensor     # [E] f64
     scans_f64: torch.Tensor = None  # [E, A, B] f64 (optional)
     truncated: torch.Tensor = None  # [E] u8: 0, 1 time limit, 2 stall (set_episode_limits; else None)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _known_fields(d, what):
@@ -101,7 +98,7 @@ class BatchSim:
         if isinstance(track, str):
             track = load_map(track, map_ext)
         self.track = track
-        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        dev = as_device(device)
         if dev.type != "cuda":
             raise _lib.F110Error("BatchSim runs on a HIP device only (no CPU path)")
         if not torch.cuda.is_available():
@@ -171,7 +168,7 @@ class BatchSim:
 
     # ------------------------------------------------------------------
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream(self.device)
 
     def reset(self, poses, env_mask=None) -> StepOut:
         """F110Env.reset for the envs in ``env_mask`` (all if None).
@@ -187,7 +184,7 @@ class BatchSim:
         if env_mask is not None:
             m = torch.as_tensor(env_mask, device=self.device).to(torch.uint8).contiguous()
         self._keep = (p, m)
-        _lib.check(self.L.f110_reset(self.ctx, _ptr(p), _ptr(m), ctypes.byref(self._outs), self._stream()),
+        _lib.check(self.L.f110_reset(self.ctx, ptr(p), ptr(m), ctypes.byref(self._outs), self._stream()),
                    "f110_reset")
         return self.out
 
@@ -208,16 +205,13 @@ class BatchSim:
         self._keep_a = a
         outs = self._outs_min if minimal_outputs else self._outs
         if obs_out is not None:
-            B = self.out.obs.shape[1]
-            if (obs_out.dtype != torch.float32 or obs_out.device != self.device or tuple(obs_out.shape) != (self.E, B)
-                    or obs_out.stride(1) != 1 or obs_out.stride(0) < B):
-                raise ValueError(f"obs_out must be a float32 [{self.E}, {B}] tensor on {self.device}, unit column stride")
+            obs_out, stride = f32_rows(obs_out, self.E, self.out.obs.shape[1], self.device, "obs_out", copy_ok=False)
             o = _lib.F110Outputs()
             ctypes.pointer(o)[0] = outs
-            o.obs, o.obs_stride = obs_out.data_ptr(), obs_out.stride(0)
+            o.obs, o.obs_stride = obs_out.data_ptr(), stride
             outs = o
         dt = _lib.F64 if a.dtype == torch.float64 else _lib.F32
-        _lib.check(self.L.f110_step(self.ctx, _ptr(a), dt, ctypes.byref(outs), self._stream()), "f110_step")
+        _lib.check(self.L.f110_step(self.ctx, ptr(a), dt, ctypes.byref(outs), self._stream()), "f110_step")
         return self.out
 
     def step_n(self, actions, minimal_outputs: bool = False) -> StepOut:
@@ -233,7 +227,7 @@ class BatchSim:
         self._keep_a = a
         outs = self._outs_min if minimal_outputs else self._outs
         dt = _lib.F64 if a.dtype == torch.float64 else _lib.F32
-        _lib.check(self.L.f110_step_n(self.ctx, _ptr(a), dt, int(a.shape[0]), 0, ctypes.byref(outs), self._stream()),
+        _lib.check(self.L.f110_step_n(self.ctx, ptr(a), dt, int(a.shape[0]), 0, ctypes.byref(outs), self._stream()),
                    "f110_step_n")
         return self.out
 
@@ -328,7 +322,7 @@ class BatchSim:
             buf = self.out.truncated
             if buf is None:
                 buf = torch.zeros(self.E, dtype=torch.uint8, device=self.device)
-        _lib.check(self.L.f110_set_episode_limits(self.ctx, ms, sp, ss, _ptr(buf), self._stream()),
+        _lib.check(self.L.f110_set_episode_limits(self.ctx, ms, sp, ss, ptr(buf), self._stream()),
                    "f110_set_episode_limits")
         self.out.truncated = buf
 
@@ -344,7 +338,7 @@ class BatchSim:
                 and tuple(noise.shape) == (self.E, self.B) and noise.is_contiguous()):
             raise ValueError(f"noise must be a contiguous float64 [{self.E}, {self.B}] tensor on {self.device}")
         self._noise = noise
-        _lib.check(self.L.f110_set_scan_noise(self.ctx, _ptr(noise)), "f110_set_scan_noise")
+        _lib.check(self.L.f110_set_scan_noise(self.ctx, ptr(noise)), "f110_set_scan_noise")
 
     def get_state(self):
         """(state [7, E*A] f64, steer_buf [2, E*A] f64, steer_cnt [E*A] i32) — SoA."""
@@ -352,7 +346,7 @@ class BatchSim:
         st = torch.empty(7, EA, dtype=torch.float64, device=self.device)
         sb = torch.empty(2, EA, dtype=torch.float64, device=self.device)
         sc = torch.empty(EA, dtype=torch.int32, device=self.device)
-        _lib.check(self.L.f110_get_state(self.ctx, _ptr(st), _ptr(sb), _ptr(sc), self._stream()), "f110_get_state")
+        _lib.check(self.L.f110_get_state(self.ctx, ptr(st), ptr(sb), ptr(sc), self._stream()), "f110_get_state")
         return st, sb, sc
 
     def lap_state(self):
@@ -360,7 +354,7 @@ class BatchSim:
         toggle_list as the device holds them (f110_get_lap_state)."""
         rot = torch.empty(2, self.E, dtype=torch.float64, device=self.device)
         tog = torch.empty(self.E * self.A, dtype=torch.int32, device=self.device)
-        _lib.check(self.L.f110_get_lap_state(self.ctx, _ptr(rot), _ptr(tog), self._stream()), "f110_get_lap_state")
+        _lib.check(self.L.f110_get_lap_state(self.ctx, ptr(rot), ptr(tog), self._stream()), "f110_get_lap_state")
         return rot, tog.reshape(self.E, self.A)
 
     def set_state(self, state=None, steer_buf=None, steer_cnt=None):
@@ -369,7 +363,7 @@ class BatchSim:
         sb = None if steer_buf is None else torch.as_tensor(steer_buf, dtype=torch.float64, device=self.device).reshape(2, EA).contiguous()
         sc = None if steer_cnt is None else torch.as_tensor(steer_cnt, dtype=torch.int32, device=self.device).reshape(EA).contiguous()
         self._keep_s = (st, sb, sc)
-        _lib.check(self.L.f110_set_state(self.ctx, _ptr(st), _ptr(sb), _ptr(sc), self._stream()), "f110_set_state")
+        _lib.check(self.L.f110_set_state(self.ctx, ptr(st), ptr(sb), ptr(sc), self._stream()), "f110_set_state")
 
     def agent_states(self) -> torch.Tensor:
         """[E, A, 7] f64 copy of the state (AoS view for consumers)."""
@@ -383,7 +377,7 @@ class BatchSim:
         scans = torch.empty(M, self.B, dtype=torch.float64, device=self.device)
         look = torch.empty(M, self.B, dtype=torch.int32, device=self.device) if probe else None
         rc = torch.empty(M, self.B, 2, dtype=torch.int32, device=self.device) if probe else None
-        _lib.check(self.L.f110_scan_batch(self.ctx, _ptr(p), M, _ptr(scans), _ptr(look), _ptr(rc), self._stream()),
+        _lib.check(self.L.f110_scan_batch(self.ctx, ptr(p), M, ptr(scans), ptr(look), ptr(rc), self._stream()),
                    "f110_scan_batch")
         return (scans, look, rc) if probe else scans
 
@@ -391,7 +385,7 @@ class BatchSim:
         x = torch.as_tensor(x, dtype=torch.float64, device=self.device).reshape(-1, 7).contiguous()
         u = torch.as_tensor(u, dtype=torch.float64, device=self.device).reshape(-1, 2).contiguous()
         f = torch.empty_like(x)
-        _lib.check(self.L.f110_dynamics_batch(self.ctx, _ptr(x), _ptr(u), _ptr(f), x.shape[0], self._stream()),
+        _lib.check(self.L.f110_dynamics_batch(self.ctx, ptr(x), ptr(u), ptr(f), x.shape[0], self._stream()),
                    "f110_dynamics_batch")
         return f
 
@@ -400,7 +394,7 @@ class BatchSim:
         x = torch.as_tensor(x, dtype=torch.float64, device=self.device).reshape(-1, 5).contiguous()
         u = torch.as_tensor(u, dtype=torch.float64, device=self.device).reshape(-1, 2).contiguous()
         f = torch.empty_like(x)
-        _lib.check(self.L.f110_dynamics_ks_batch(self.ctx, _ptr(x), _ptr(u), _ptr(f), x.shape[0], self._stream()),
+        _lib.check(self.L.f110_dynamics_ks_batch(self.ctx, ptr(x), ptr(u), ptr(f), x.shape[0], self._stream()),
                    "f110_dynamics_ks_batch")
         return f
 

@@ -19,6 +19,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._dev import device_track, f32_rows, ptr
+from ._dev import stream as current_stream
 
 TRACK_OBS_FIELDS = ("v_scale", "steer_scale", "yaw_rate_scale", "slip_scale", "lat_scale", "gap_scale", "preview",
                     "direction")
@@ -81,17 +83,6 @@ def _seats(n_agents, seat, other, what):
     return seat, other
 
 
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _check_rows(out, E, width, device, what):
-    if (out.dim() != 2 or out.dtype != torch.float32 or out.device != device or tuple(out.shape) != (E, width)
-            or out.stride(1) != 1 or (E > 1 and out.stride(0) < width)):
-        raise ValueError(f"{what}: out must be a float32 [{E}, {width}] tensor on {device} with unit column stride")
-    return out.stride(0) if E > 1 else width
-
-
 def track_obs(state: torch.Tensor, track, n_envs: int, n_agents: int, seat: int = 0, other=None,
               out: torch.Tensor | None = None, stream=None, **params):
     """The block for ``n_envs`` envs (f110_track_obs).  state: float64 device tensor [7, n_envs *
@@ -104,16 +95,14 @@ def track_obs(state: torch.Tensor, track, n_envs: int, n_agents: int, seat: int 
     if (state.dtype != torch.float64 or state.device.type != "cuda" or tuple(state.shape) != (7, E * A)
             or not state.is_contiguous()):
         raise ValueError(f"state must be a contiguous float64 cuda tensor [7, {E * A}]")
-    if getattr(track, "device", None) != state.device or not getattr(track, "handle", None):
-        raise ValueError("track must be an open reward.CenterlineTrack on the state's device")
+    device_track(track, state.device, "track", user="the state")
     p = track_obs_params(**params)
     width = track_obs_width(p.n_preview, other >= 0)
     if out is None:
         out = torch.empty(E, width, dtype=torch.float32, device=state.device)
-    stride = _check_rows(out, E, width, state.device, "track_obs")
-    s = stream if stream is not None else torch.cuda.current_stream(state.device).cuda_stream
-    _lib.check(_lib.load().f110_track_obs(track.handle, ctypes.byref(p), _vp(state), E, A, seat, other, _vp(out),
-                                          stride, ctypes.c_void_p(s)), "f110_track_obs")
+    stride = f32_rows(out, E, width, state.device, "track_obs: out", copy_ok=False)[1]
+    _lib.check(_lib.load().f110_track_obs(track.handle, ctypes.byref(p), ptr(state), E, A, seat, other, ptr(out),
+                                          stride, current_stream(state.device, stream)), "f110_track_obs")
     return out
 
 
@@ -151,11 +140,8 @@ class TrackObs:
     def __init__(self, sim, track, seat: int = 0, other=None, **params):
         self.sim, self.track = sim, track
         self.seat, self.other = _seats(sim.A, seat, other, "TrackObs")
-        tdev = getattr(track, "device", None)
-        if tdev is None or not getattr(track, "handle", None):
-            raise ValueError("TrackObs needs an open device reward.CenterlineTrack")
-        if tdev != sim.device:
-            raise ValueError(f"the track is on {tdev}, the simulator on {sim.device}")
+        device_track(track, sim.device, "the track", "TrackObs needs an open device reward.CenterlineTrack",
+                     user="the simulator")
         self.params = track_obs_params(**params)
         if any(not 0.0 < self.params.preview[j] < track.L for j in range(self.params.n_preview)):
             raise ValueError(f"preview distances must be in (0, {track.L}) m")
@@ -167,9 +153,8 @@ class TrackObs:
         """out_rows: float32 [E, width] (unit column stride, rows may be strided), e.g. the tail of
         a wide obs buffer.  Returns it."""
         sim = self.sim
-        stride = _check_rows(out_rows, sim.E, self.width, sim.device, "TrackObs.fill")
-        s = torch.cuda.current_stream(sim.device).cuda_stream
+        stride = f32_rows(out_rows, sim.E, self.width, sim.device, "TrackObs.fill: out", copy_ok=False)[1]
         _lib.check(_lib.load().f110_ctx_track_obs(sim.ctx, self.track.handle, ctypes.byref(self.params), self.seat,
-                                                  self.other, _vp(out_rows), stride, ctypes.c_void_p(s)),
+                                                  self.other, ptr(out_rows), stride, current_stream(sim.device)),
                    "f110_ctx_track_obs")
         return out_rows

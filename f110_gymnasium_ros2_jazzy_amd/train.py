@@ -64,6 +64,29 @@ REWARD_KW = dict(w_prog=5.0, alive_bonus=0.5, grace_steps_wall=25, grace_steps_o
                  w_rel_lead=0.0)
 
 
+class _RowStats:
+    """The statistics of the rows [lo, hi) of a step's buffers: an episode.EpisodeStats and a
+    race.RaceStats built for hi - lo envs (either may be None)."""
+
+    def __init__(self, lo, hi, episode, race=None):
+        self.lo, self.hi, self.episode, self.race = lo, hi, episode, race
+
+    def update(self, rew, obs, term, trunc, was_reset):
+        rows = slice(self.lo, self.hi)
+        term, trunc, was_reset = term[rows], None if trunc is None else trunc[rows], was_reset[rows]
+        self.episode.update(rew[rows], term, trunc, was_reset)
+        if self.race is not None:
+            self.race.update(obs[rows], term, trunc, was_reset)
+
+    def totals_and_reset(self):
+        """[episode totals or None, race totals or None] since the last call (waits for the stream)."""
+        out = [None if s is None else s.totals() for s in (self.episode, self.race)]
+        for s in (self.episode, self.race):
+            if s is not None:
+                s.reset_totals()
+        return out
+
+
 class VectorTrainer:
     """One rank's share of the batched train_ddpg loop."""
 
@@ -77,10 +100,9 @@ class VectorTrainer:
                  opponent_speed=None, opponent_lookahead: float | None = None, opponent_rule: str = "gap_follow",
                  action_repeat: int = 1, race_stats: bool = False, track_obs: bool = False, track_preview=None):
         # action_repeat and the opponent arguments: ValueError before anything is built
-        if isinstance(action_repeat, bool) or not isinstance(action_repeat, (int, np.integer)) or \
-                not 1 <= action_repeat <= 64:
-            raise ValueError(f"action_repeat must be an integer in 1..64; got {action_repeat!r}")
-        if action_repeat > 1 and int(n_step) > 1:
+        from .opponent import check_pursuit_speed
+        from .replay import check_action_repeat
+        if check_action_repeat(action_repeat) > 1 and int(n_step) > 1:
             raise ValueError("action_repeat > 1 with n_step > 1 is not supported; use one of the two")
         if opponent not in ("gap_follow", "self", "pure_pursuit"):
             raise ValueError(f"opponent must be 'gap_follow', 'self' or 'pure_pursuit'; got {opponent!r}")
@@ -88,11 +110,7 @@ class VectorTrainer:
             raise ValueError(f"opponent_rule must be 'gap_follow' or 'pure_pursuit'; got {opponent_rule!r}")
         if opponent_lookahead is not None and not float(opponent_lookahead) > 0.0:
             raise ValueError(f"opponent_lookahead must be > 0; got {opponent_lookahead!r}")
-        if opponent_speed is not None:
-            sp = np.asarray(opponent_speed, dtype=np.float64)
-            if sp.shape not in ((), (int(envs_per_rank),)) or not (np.isfinite(sp).all() and (sp >= 0.0).all()):
-                raise ValueError(f"opponent_speed must be one finite number >= 0 or an array [{int(envs_per_rank)}] "
-                                 "of them")
+        check_pursuit_speed(opponent_speed, envs_per_rank)
         if int(selfplay_sync) != selfplay_sync or selfplay_sync < 1:
             raise ValueError(f"selfplay_sync must be an integer >= 1; got {selfplay_sync!r}")
         if not 0.0 <= float(selfplay_fraction) <= 1.0:
@@ -183,19 +201,23 @@ class VectorTrainer:
         else:
             self.env = F110VectorEnv(self.N, opponent=opponent, **pursuit_kw, **env_kw)
         self._synced_at = 0  # the learner update index of the snapshot's last load
-        self.train_stats = self.eval_stats = self._eval_mask = None
+        # the statistics the report reads, as (report prefix, group): the env's own, or with evaluation
+        # envs one group over the training rows and one over the eval rows, which _transition updates
+        self._eval_mask = self.train_stats = self.eval_stats = self.train_race = self.eval_race = None
+        self._stats = [("", _RowStats(0, self.N, self.env._episode, self.env._race))]
         if self.eval_envs:
             from .episode import EpisodeStats
-            self.train_stats = EpisodeStats(self.N - self.eval_envs, device=self.device)
-            self.eval_stats = EpisodeStats(self.eval_envs, device=self.device)
-            self._eval_mask = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
-            self._eval_mask[self.N - self.eval_envs:] = 1
-        self.train_race = self.eval_race = None
-        if self.eval_envs and self.race_stats:
             from .race import RaceStats
-            race_kw = dict(ego_idx=0, opponent_idx=self.env.opponent_idx, device=self.device)
-            self.train_race = RaceStats(self.N - self.eval_envs, self.track, self.env.sim.B, **race_kw)
-            self.eval_race = RaceStats(self.eval_envs, self.track, self.env.sim.B, **race_kw)
+            k = self.N - self.eval_envs
+            self._eval_mask = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
+            self._eval_mask[k:] = 1
+            self._stats = [(prefix, _RowStats(
+                lo, hi, EpisodeStats(hi - lo, device=self.device),
+                RaceStats(hi - lo, self.track, self.env.sim.B, ego_idx=0, opponent_idx=self.env.opponent_idx,
+                          device=self.device) if self.race_stats else None))
+                for prefix, lo, hi in (("", 0, k), ("eval_", k, self.N))]
+            (_, tg), (_, eg) = self._stats
+            self.train_stats, self.train_race, self.eval_stats, self.eval_race = tg.episode, tg.race, eg.episode, eg.race
         if not self.selfplay:
             self.agent = learner(self.env.single_observation_space.shape[0])
         self.warmup = int(warmup_steps)
@@ -216,9 +238,8 @@ class VectorTrainer:
         self._high = torch.tensor(ACTION_HIGH, device=self.device)
         self.obs, self.info = self.env.reset(seed=seed + rank_seed)
         if self.train_race is not None:  # the reset observation starts every env's race
-            k = self.N - self.eval_envs
-            self.train_race.begin(self.obs[:k])
-            self.eval_race.begin(self.obs[k:])
+            for _, g in self._stats:
+                g.race.begin(self.obs[g.lo:g.hi])
         self.global_step = 0
         self.last = None
 
@@ -292,14 +313,9 @@ class VectorTrainer:
         env.step, the episode statistics of the two row ranges (eval_envs > 0) and remember."""
         act = self.agent.hold_env(obs_in, act)
         nxt, rew, term, was_reset = self.env.step_transition(act, obs_out=obs_out)
-        if self.eval_envs:
-            k = self.N - self.eval_envs
-            trunc = self.env.truncated
-            self.train_stats.update(rew[:k], term[:k], None if trunc is None else trunc[:k], was_reset[:k])
-            self.eval_stats.update(rew[k:], term[k:], None if trunc is None else trunc[k:], was_reset[k:])
-            if self.train_race is not None:  # on the obs buffer the reward saw
-                self.train_race.update(nxt[:k], term[:k], None if trunc is None else trunc[:k], was_reset[:k])
-                self.eval_race.update(nxt[k:], term[k:], None if trunc is None else trunc[k:], was_reset[k:])
+        if self.eval_envs:  # (the race statistics on the obs buffer the reward saw)
+            for _, g in self._stats:
+                g.update(rew, nxt, term, self.env.truncated, was_reset)
         # NEXT_STEP autoreset: a reset row's obs is the previous episode's last
         # observation and its next_obs the new episode's first -- not a transition
         # (remember_env skips the rows with was_reset != 0); eval transitions are stored like any
@@ -381,7 +397,12 @@ class VectorTrainer:
         self.track.close()
 
 
-RACE_REPORT_SUMS = ("episodes", "progress_sum", "lead_sum", "ahead_at_end", "ego_crashes", "passes")
+# the report of one group's totals: (the count's report key, the totals that ride in the all-reduce, the count
+# first, and the report key of each other total's mean per episode); "{p}" is the group's prefix
+EPISODE_REPORT = ("{p}episodes", ("episodes", "return_sum", "length_sum"), ("{e}return_mean", "{e}length_mean"))
+RACE_REPORT = ("{p}race_episodes", ("episodes", "progress_sum", "lead_sum", "ahead_at_end", "ego_crashes", "passes"),
+               ("{p}progress_mean", "{p}lead_mean", "{p}win_rate", "{p}crash_rate", "{p}passes_per_episode"))
+RACE_REPORT_SUMS = RACE_REPORT[1]
 
 
 def episode_report(tr: VectorTrainer, world: int = 1) -> dict:
@@ -391,29 +412,11 @@ def episode_report(tr: VectorTrainer, world: int = 1) -> dict:
     With race_stats also race_episodes, progress_mean, lead_mean, win_rate, crash_rate and
     passes_per_episode (and their eval_ twins), from the race totals in the same all-reduce; a
     trainer that keeps race statistics only (no limits, no evaluation envs) reports those alone."""
-    t = te = None
-    if tr.eval_envs:
-        t, te = tr.train_stats.totals(), tr.eval_stats.totals()
-        tr.train_stats.reset_totals()
-        tr.eval_stats.reset_totals()
-    elif tr.episode_stats:
-        t = tr.env.episode_totals()
-        tr.env.reset_episode_totals()
-    v = []
-    for tot in (t, te):
-        if tot is not None:
-            v += [float(tot["episodes"]), float(tot["return_sum"]), float(tot["length_sum"])]
-    n_ep = len(v)
-    if tr.race_stats:  # the race totals ride in the same vector, after the episode entries
-        if tr.eval_envs:
-            races = [tr.train_race.totals(), tr.eval_race.totals()]
-            tr.train_race.reset_totals()
-            tr.eval_race.reset_totals()
-        else:
-            races = [tr.env.race_totals()]
-            tr.env.reset_race_totals()
-        for r in races:
-            v += [float(r[k]) for k in RACE_REPORT_SUMS]
+    totals = [(prefix, *g.totals_and_reset()) for prefix, g in tr._stats]
+    # one vector, the same layout on every rank: every group's episode sums, then every group's race sums
+    parts = [(prefix, EPISODE_REPORT, ep) for prefix, ep, _ in totals if ep is not None] + \
+            [(prefix, RACE_REPORT, race) for prefix, _, race in totals if race is not None]
+    v = [float(tot[k]) for _, (_, sums, _), tot in parts for k in sums]
     if world > 1:
         import torch.distributed as dist
         w = torch.tensor(v, dtype=torch.float64)
@@ -422,25 +425,11 @@ def episode_report(tr: VectorTrainer, world: int = 1) -> dict:
         dist.all_reduce(w)
         v = w.tolist()
     rep = {}
-    if t is not None:
-        n = int(v[0])
-        rep = {"episodes": n, "episode_return_mean": v[1] / n if n else None,
-               "episode_length_mean": v[2] / n if n else None}
-    if te is not None:
-        m = int(v[3])
-        rep.update(eval_episodes=m, eval_return_mean=v[4] / m if m else None,
-                   eval_length_mean=v[5] / m if m else None)
-    if tr.race_stats:
-        w = len(RACE_REPORT_SUMS)
-        for j, prefix in enumerate(("", "eval_") if te is not None else ("",)):
-            ne, prog, lead, ahead, crashes, passes = v[n_ep + j * w:n_ep + (j + 1) * w]
-            ne = int(ne)
-            rep.update({prefix + "race_episodes": ne,
-                        prefix + "progress_mean": prog / ne if ne else None,
-                        prefix + "lead_mean": lead / ne if ne else None,
-                        prefix + "win_rate": ahead / ne if ne else None,
-                        prefix + "crash_rate": crashes / ne if ne else None,
-                        prefix + "passes_per_episode": passes / ne if ne else None})
+    for prefix, (count, sums, means), _ in parts:
+        n, names = int(v[0]), dict(p=prefix, e=prefix or "episode_")
+        rep[count.format(**names)] = n
+        rep.update({key.format(**names): x / n if n else None for key, x in zip(means, v[1:len(sums)])})
+        v = v[len(sums):]
     return rep
 
 

@@ -87,6 +87,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from ._dev import device_track, f32_rows, first_track
 from .f110_env import DEFAULT_PARAMS, _box
 from .maps import centerline_spawns, load_map
 from .sim import BatchSim, param_range_rows
@@ -248,22 +249,13 @@ class F110VectorEnv:
     def _check_pursuit(self, track, params, speed, device):
         """The pure-pursuit arguments: a device track on the env's device, known parameter names,
         one speed or one per env (host values only)."""
-        from .opponent import PURSUIT_FIELDS
-        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
-        tdev = getattr(track, "device", None)
-        if track is None or tdev is None or not getattr(track, "handle", None):
-            raise ValueError("opponent 'pure_pursuit' needs opponent_track (a device reward.CenterlineTrack)")
-        if tdev.type != dev.type or (tdev.index or 0) != (dev.index or 0):
-            raise ValueError(f"opponent_track is on {tdev}, the env on {dev}")
+        from .opponent import PURSUIT_FIELDS, check_pursuit_speed
+        device_track(track, device, "opponent_track",
+                     "opponent 'pure_pursuit' needs opponent_track (a device reward.CenterlineTrack)")
         unknown = sorted(set(params or {}) - set(PURSUIT_FIELDS))
         if unknown:
             raise ValueError(f"unknown opponent_params {unknown} (known: {', '.join(PURSUIT_FIELDS)})")
-        if speed is not None:
-            sp = np.asarray(speed, dtype=np.float64)
-            if sp.shape not in ((), (self.num_envs,)):
-                raise ValueError(f"opponent_speed must be one number or an array [{self.num_envs}]")
-            if not (np.isfinite(sp).all() and (sp >= 0.0).all()):
-                raise ValueError("opponent_speed must be finite and >= 0")
+        check_pursuit_speed(speed, self.num_envs)
 
     def _check_track_obs(self, track_obs, track, reward_fn, opponent_track, race_track, device, ego_idx, opponent_idx):
         """The track-observation arguments (host values only): (the centerline to use, the parameter
@@ -277,17 +269,10 @@ class F110VectorEnv:
         unknown = sorted(set(params) - set(TRACK_OBS_FIELDS))
         if unknown:
             raise ValueError(f"unknown track_obs parameters {unknown} (known: {', '.join(TRACK_OBS_FIELDS)})")
-        for cand in (track, getattr(reward_fn, "progress", None), opponent_track, race_track):
-            if cand is not None:
-                track = cand
-                break
-        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
-        tdev = getattr(track, "device", None)
-        if track is None or tdev is None or not getattr(track, "handle", None):
-            raise ValueError("track_obs needs a centerline: obs_track, reward_fn.progress, opponent_track or "
+        track = device_track(first_track(track, getattr(reward_fn, "progress", None), opponent_track, race_track),
+                             device, "the track observation's centerline",
+                             "track_obs needs a centerline: obs_track, reward_fn.progress, opponent_track or "
                              "race_track (a device reward.CenterlineTrack)")
-        if tdev.type != dev.type or (tdev.index or 0) != (dev.index or 0):
-            raise ValueError(f"the track observation's centerline is on {tdev}, the env on {dev}")
         if params.get("direction", 1) not in (1, -1):
             raise ValueError("track_obs: direction must be +1 or -1")
         prev = [float(d) for d in params.get("preview", ())]
@@ -306,17 +291,9 @@ class F110VectorEnv:
         """The race-statistics arguments (host values only): the centerline to use, or None when off."""
         if not race_stats:
             return None
-        for cand in (track, getattr(reward_fn, "progress", None), opponent_track):
-            if cand is not None:
-                track = cand
-                break
-        dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
-        tdev = getattr(track, "device", None)
-        if track is None or tdev is None or not getattr(track, "handle", None):
-            raise ValueError("race_stats=True needs a centerline: race_track, reward_fn.progress or opponent_track "
-                             "(a device reward.CenterlineTrack)")
-        if tdev.type != dev.type or (tdev.index or 0) != (dev.index or 0):
-            raise ValueError(f"the race track is on {tdev}, the env on {dev}")
+        track = device_track(first_track(track, getattr(reward_fn, "progress", None), opponent_track), device,
+                             "the race track", "race_stats=True needs a centerline: race_track, reward_fn.progress "
+                             "or opponent_track (a device reward.CenterlineTrack)")
         unknown = sorted(set(params or {}) - {"pass_margin", "direction"})
         if unknown:
             raise ValueError(f"unknown race_params {unknown} (known: pass_margin, direction)")
@@ -422,43 +399,54 @@ class F110VectorEnv:
         self._tobs.fill(wide[:, self._head:])
         return wide
 
-    def _check_wide(self, obs_out):
-        if (obs_out.dtype != torch.float32 or obs_out.device != self.device
-                or tuple(obs_out.shape) != (self.num_envs, self.obs_dim) or obs_out.stride(1) != 1
-                or (self.num_envs > 1 and obs_out.stride(0) < self.obs_dim)):
-            raise ValueError(f"obs_out must be a float32 [{self.num_envs}, {self.obs_dim}] tensor on {self.device}, "
-                             "unit column stride")
-
-    def step(self, actions):
+    def _route(self, actions, own_rows=False):
+        """The step's [N, A, 2] action rows: with an opponent the caller's rows copied into the env's
+        action buffer beside the opponent's (own_rows: unless they are agent_actions() itself), else
+        the caller's tensor."""
         a = torch.as_tensor(actions, device=self.device)
-        if self.opponent is not None:
-            if a.dim() == 2:
+        if self.opponent is None:
+            return a.unsqueeze(1) if a.dim() == 2 and self.num_agents == 1 else a
+        dst = self.agent_actions() if own_rows else None
+        if dst is None or a.data_ptr() != dst.data_ptr() or a.stride() != dst.stride():
+            if own_rows or a.dim() == 2:
                 a = a.reshape(self.num_envs, len(self._others), 2)
-            if a.shape[1] == self.num_agents:
+            if not own_rows and a.shape[1] == self.num_agents:  # every agent's rows: the opponent's are dropped
                 a = a[:, self._others_sl]
             self._act[:, self._others_sl] = a
-            a = self._act
-        elif a.dim() == 2 and self.num_agents == 1:
-            a = a.unsqueeze(1)
+        return self._act
+
+    def _advance(self, a, obs_out=None):
+        """One step of every stage, in order: the simulator (into obs_out, if given), the track
+        observation's tail, the next opponent action, the reward, the episode and race statistics.
+        Returns (out, obs, rewards): the simulator's outputs, the rows every stage read (the
+        simulator's own, the env's wide buffer, or obs_out) and the reward's own buffer."""
         if self._tobs is None:
-            out = self.sim.step(a)
-            src = out.obs
-            self._opponent_next(out)
+            out = self.sim.step(a, obs_out=obs_out)  # the simulator writes obs_out itself (no copy)
+            obs = out.obs if obs_out is None else obs_out
         else:  # the simulator writes the left columns of the wide rows, one launch fills the tail
-            out = self.sim.step(a, obs_out=self._wide[:, :self._head])
-            src = self._fill_wide()
-            self._opponent_next(out, src)
+            obs = self._wide
+            if obs_out is not None:
+                obs = f32_rows(obs_out, self.num_envs, self.obs_dim, self.device, "obs_out", copy_ok=False)[0]
+            out = self.sim.step(a, obs_out=obs[:, :self._head])
+            self._fill_wide(wide=obs)
+        self._opponent_next(out, None if obs is out.obs else obs)
         if self.reward_fn is not None:  # reset envs: reward_fn.reset(), reward 0 (the u8 flags as they are)
-            rewards = self.reward_fn(src, reset_mask=out.was_reset).clone()
+            rewards = self.reward_fn(obs, reset_mask=out.was_reset)
         else:
             rewards = torch.where(out.was_reset.bool(), torch.zeros((), dtype=torch.float64, device=self.device),
                                   torch.full((), self.timestep, dtype=torch.float64, device=self.device))
-        term = out.terminated.bool()
-        trunc = out.truncated.bool() if self._limits else torch.zeros_like(term)
         if self._episode is not None:
             self._episode.update(rewards, out.terminated, out.truncated, out.was_reset)
         if self._race is not None:
-            self._race.update(src, out.terminated, out.truncated, out.was_reset)
+            self._race.update(obs, out.terminated, out.truncated, out.was_reset)
+        return out, obs, rewards
+
+    def step(self, actions):
+        out, src, rewards = self._advance(self._route(actions))
+        if self.reward_fn is not None:
+            rewards = rewards.clone()
+        term = out.terminated.bool()
+        trunc = out.truncated.bool() if self._limits else torch.zeros_like(term)
         obs = src.clone()
         if self.as_numpy:
             return (obs.cpu().numpy(), rewards.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy(),
@@ -488,34 +476,7 @@ class F110VectorEnv:
         With track_obs on obs_dim is the wide width and obs_out a wide buffer, whose tail is filled too."""
         if self.as_numpy:
             raise ValueError("step_transition: device tensors only (as_numpy=False)")
-        a = torch.as_tensor(actions, device=self.device)
-        if self.opponent is not None:
-            dst = self.agent_actions()
-            if dst is None or a.data_ptr() != dst.data_ptr() or a.stride() != dst.stride():
-                self._act[:, self._others_sl] = a.reshape(self.num_envs, len(self._others), 2)
-            a = self._act
-        elif a.dim() == 2 and self.num_agents == 1:
-            a = a.unsqueeze(1)
-        if self._tobs is None:
-            out = self.sim.step(a, obs_out=obs_out)  # the simulator writes obs_out itself (no copy)
-            obs = out.obs if obs_out is None else obs_out
-        else:  # the left columns of the wide rows (the env's, or obs_out's), then their tail
-            obs = self._wide
-            if obs_out is not None:
-                self._check_wide(obs_out)
-                obs = obs_out
-            out = self.sim.step(a, obs_out=obs[:, :self._head])
-            self._fill_wide(wide=obs)
-        self._opponent_next(out, obs)
-        if self.reward_fn is not None:
-            rewards = self.reward_fn(obs, reset_mask=out.was_reset)
-        else:
-            rewards = torch.where(out.was_reset.bool(), torch.zeros((), dtype=torch.float64, device=self.device),
-                                  torch.full((), self.timestep, dtype=torch.float64, device=self.device))
-        if self._episode is not None:
-            self._episode.update(rewards, out.terminated, out.truncated, out.was_reset)
-        if self._race is not None:
-            self._race.update(obs, out.terminated, out.truncated, out.was_reset)
+        out, obs, rewards = self._advance(self._route(actions, own_rows=True), obs_out)
         return (obs.clone() if obs_out is None else obs_out), rewards, out.terminated, out.was_reset
 
     @property
