@@ -99,6 +99,10 @@ class F110TrackObsParams(ctypes.Structure):  # f110_track_obs_params
                [("preview", ctypes.c_double * 8), ("n_preview", ctypes.c_int32), ("direction", ctypes.c_int32)]
 
 
+class F110ScanObsParams(ctypes.Structure):  # f110_scan_obs_params
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_bins", "n_frames", "stride", "reduce", "keep_mid")]
+
+
 class F110RayKnobs(ctypes.Structure):  # f110_ray_knobs (include/f110_debug.h)
     _fields_ = [(n, ctypes.c_int32) for n in
                 ("kernel", "lanes", "refill", "fxs_lds", "count_slots", "wtrace", "heavy_list", "heavy_on",
@@ -278,6 +282,15 @@ _API = {
     "f110_track_obs": (_i, [_P, ctypes.POINTER(F110TrackObsParams), _P, _i64, _i32, _i32, _i32, _P, _i64, _P]),
     "f110_ctx_track_obs": (_i, [_P, _P, ctypes.POINTER(F110TrackObsParams), _i32, _i32, _P, _i64, _P]),
     "f110_host_track_obs": (_i, [_P, ctypes.POINTER(F110TrackObsParams), _P, _i64, _i32, _i32, _i32, _P, _i64]),
+    "f110_default_scan_obs_params": (None, [ctypes.POINTER(F110ScanObsParams)]),
+    "f110_scan_obs_width": (_i32, [ctypes.POINTER(F110ScanObsParams), _i32, _i32, _i32]),
+    "f110_scan_obs_create": (_i, [ctypes.POINTER(_P), _i32, _i64, _i32, _i32, _i32, ctypes.POINTER(F110ScanObsParams)]),
+    "f110_scan_obs_destroy": (_i, [_P]),
+    "f110_scan_obs_push": (_i, [_P, _P, _i64, _P, _P, _i64, _P]),
+    "f110_scan_obs_reset": (_i, [_P, _P, _P]),
+    "f110_scan_obs_arrays": (_i, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P)]),
+    "f110_host_scan_obs_push": (_i, [ctypes.POINTER(F110ScanObsParams), _i64, _i32, _i32, _i32, _P, _i64, _P, _P, _P, _P,
+                                     _i64]),
 }
 EXPORTS = list(_API)
 

@@ -2,8 +2,8 @@
 // touches no handle.  The error string, the defaults, the reference's lookup tables, the exact EDT
 // (Felzenszwalb-Huttenlocher lower envelopes, integer arithmetic) and the tables built from it,
 // the beam-index and sin/cos test hooks, the ray-launch decision (ray_rules, plan_ray_launch), the
-// argument checks of the params / episode / n-step entry points and their host models, and the
-// derivation of a track's arrays.  It links on its own (tests/host_check runs it under ASan / UBSan).
+// argument checks of the params / episode / n-step entry points and their host models, the
+// derivation of a track's arrays, and the scan observation's host statement.  It links on its own (tests/host_check runs it under ASan / UBSan).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -21,6 +21,7 @@
 #include "f110_learner_args.h"
 #include "f110_map.h"
 #include "f110_math.h"
+#include "f110_scan_obs.h"
 #include "f110_sincos.h"
 #include "f110_step_args.h"
 #include "f110_task_args.h"
@@ -823,6 +824,64 @@ extern "C" int f110_host_agent_obs(const float *scans, int64_t scan_env_stride, 
             const int src = g == 0 ? agent : (g <= agent ? g - 1 : g);
             std::copy(p + 4 * src, p + 4 * src + 4, o + B + 4 * g);
         }
+    }
+    return F110_OK;
+}
+
+// ---- scan observation (f110_scan_obs.hip; the row rule: f110_scan_obs.h) ----------------------
+extern "C" void f110_default_scan_obs_params(f110_scan_obs_params *p) {
+    if (!p) return;
+    *p = f110_scan_obs_params{};
+    p->n_bins = 108;
+    p->n_frames = 1;
+    p->stride = 1;
+    p->reduce = 0;
+    p->keep_mid = 1;
+}
+
+extern "C" int32_t f110_scan_obs_width(const f110_scan_obs_params *params, int32_t n_beams, int32_t n_mid,
+                                       int32_t n_tail) {
+    if (scan_obs_bad_shape(params, n_beams, n_mid, n_tail)) return -1;
+    return scan_obs_width(*params, n_mid, n_tail);
+}
+
+extern "C" int f110_host_scan_obs_push(const f110_scan_obs_params *params, int64_t n_envs, int32_t n_beams,
+                                       int32_t n_mid, int32_t n_tail, const float *rows, int64_t row_stride,
+                                       const uint8_t *reset, float *ring, int32_t *head, float *out,
+                                       int64_t out_stride) {
+    const char *bad = scan_obs_bad_shape(params, n_beams, n_mid, n_tail);
+    if (!bad && n_envs < 1) bad = "n_envs must be at least 1";
+    if (!bad && (!ring || !head)) bad = "null ring or head";
+    const f110_scan_obs_params &P = *params;
+    if (!bad) bad = scan_obs_bad_push(n_envs, n_beams + n_mid + n_tail, scan_obs_width(P, n_mid, n_tail), rows,
+                                      row_stride, out, out_stride);
+    if (bad) return fail(F110_E_INVALID, std::string("f110_host_scan_obs_push: ") + bad);
+    const int32_t B = n_beams, K = P.n_bins, F = P.n_frames, S = P.stride, D = scan_obs_depth(P);
+    for (int64_t e = 0; e < n_envs; ++e)
+        if (head[e] < -1 || head[e] >= D)
+            return fail(F110_E_INVALID, "f110_host_scan_obs_push: a head outside [-1, D)");
+    const int32_t n_copy = (P.keep_mid ? n_mid : 0) + n_tail;
+    for (int64_t e = 0; e < n_envs; ++e) {
+        const float *row = rows + e * row_stride;
+        float *o = out + e * out_stride;
+        float *rg = ring + (size_t)e * D * K;
+        bool refill;
+        const int32_t h = scan_obs_advance(head[e], reset ? reset[e] : 0, D, refill);
+        for (int32_t k = 0; k < K; ++k) {
+            const float v = scan_obs_pool(row, scan_obs_edge(k, B, K), scan_obs_edge(k + 1, B, K), P.reduce);
+            if (refill) {
+                for (int32_t d = 0; d < D; ++d) rg[(size_t)d * K + k] = v;
+            } else {
+                rg[(size_t)h * K + k] = v;
+            }
+        }
+        head[e] = h;
+        for (int32_t j = 0; j < F; ++j) {
+            const float *slot = rg + (size_t)scan_obs_slot(h, j, S, D) * K;
+            std::copy(slot, slot + K, o + (size_t)j * K);
+        }
+        const float *src = row + B + (P.keep_mid ? 0 : n_mid);
+        std::copy(src, src + n_copy, o + (size_t)F * K);
     }
     return F110_OK;
 }

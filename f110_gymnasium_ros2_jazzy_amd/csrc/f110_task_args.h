@@ -1,6 +1,6 @@
 // f110_task_args.h — the argument blocks and launchers of the kernels beside the env step: the
 // C-ABI batch kernels, gap-follow, the track, the reward and the pure-pursuit opponent, the episode
-// and the race statistics, the track observation.
+// and the race statistics, the track observation, the scan observation.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -126,6 +126,20 @@ struct TrackObsArgs {
     float *out;           // row e at out + e * out_stride
 };
 hipError_t launch_track_obs(const TrackObsArgs &a, hipStream_t s);
+
+// ---- scan observation (f110_scan_obs.hip; the row rule: f110_scan_obs.h) ----------------------
+struct ScanObsArgs {
+    const float *rows;     // row e at rows + e * row_stride: [B | M | T]
+    const uint8_t *reset;  // [E] or null
+    float *ring;           // [E][D][K]
+    int32_t *head;         // [E], -1 = empty
+    float *out;            // row e at out + e * out_stride: [F*K | M if keep_mid | T]
+    int64_t E, row_stride, out_stride;
+    int32_t B, M, T, K, F, S, D, reduce, keep_mid;
+    int32_t vec4;          // rows 16-byte aligned and row_stride % 4 == 0: the row is loaded as float4
+};
+hipError_t launch_scan_obs(const ScanObsArgs &a, hipStream_t s);
+hipError_t launch_scan_obs_reset(int32_t *head, const uint8_t *env_mask, int64_t E, hipStream_t s);
 
 // ---- the C-ABI batch kernels (f110_batch.hip) and the task kernels ----------------------------
 hipError_t launch_scan_batch(const ScanArgs &a, hipStream_t s);

@@ -1,10 +1,10 @@
 // f110_task_capi.cpp — the context-free training entry points of include/f110.h: the track of the
 // progress reward (f110_track_*), f110_reward, f110_gap_follow, f110_pure_pursuit with its host
 // statement, the race statistics with theirs, the track observation with its own (and its entry on
-// a context's live state, which needs both the track's and the context's internals), the collision
-// batches and the episode statistics.  Argument checks and launches; the kernels are in
-// f110_reward.hip, f110_opponent.hip, f110_pursuit.hip, f110_race.hip, f110_track_obs.hip,
-// f110_batch.hip and f110_episode.hip.
+// a context's live state, which needs both the track's and the context's internals), the scan
+// observation's handle, the collision batches and the episode statistics.  Argument checks and
+// launches; the kernels are in f110_reward.hip, f110_opponent.hip, f110_pursuit.hip, f110_race.hip,
+// f110_track_obs.hip, f110_scan_obs.hip, f110_batch.hip and f110_episode.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +20,7 @@
 #include "f110_host.h"
 #include "f110_host_util.h"
 #include "f110_pursuit.h"
+#include "f110_scan_obs.h"
 #include "f110_step_args.h"
 #include "f110_task_args.h"
 #include "f110_track_obs.h"
@@ -480,6 +481,89 @@ extern "C" int f110_host_track_obs(const f110_track *track, const f110_track_obs
         track_obs_gap(P, T.closed, T.L, pj.s, pj.t, c.v, po.s, po.t, o.v, gap);
         for (int j = 0; j < kTrackObsGap; ++j) row[kTrackObsOwn + 2 * np + j] = (float)gap[j];
     }
+    return F110_OK;
+}
+
+// ---- scan observation (f110_scan_obs.hip; the row rule: f110_scan_obs.h) ----------------------
+// (f110_default_scan_obs_params, f110_scan_obs_width and the host statement: f110_host.cpp)
+struct f110_scan_obs {
+    DeviceArena arena;
+    ScanObsArgs a{};  // the shape, the ring and the heads; a push fills in its rows
+    f110_scan_obs_params p{};
+};
+
+extern "C" int f110_scan_obs_create(f110_scan_obs **out, int32_t device, int64_t n_envs, int32_t n_beams,
+                                    int32_t n_mid, int32_t n_tail, const f110_scan_obs_params *params) {
+    const char *bad = !out ? "null out" : scan_obs_bad_shape(params, n_beams, n_mid, n_tail);
+    if (!bad && (n_envs < 1 || n_envs >= (int64_t)1 << 31)) bad = "n_envs must be positive (and below 2^31)";
+    if (bad) return fail(F110_E_INVALID, std::string("f110_scan_obs_create: ") + bad);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
+        return fail(F110_E_NODEVICE, "f110_scan_obs_create: no such HIP device");
+    if (hipSetDevice(device) != hipSuccess) return fail(F110_E_NODEVICE, "f110_scan_obs_create: hipSetDevice");
+    auto *so = new f110_scan_obs();
+    so->arena.device = device;
+    so->p = *params;
+    ScanObsArgs &a = so->a;
+    a.E = n_envs;
+    a.B = n_beams;
+    a.M = n_mid;
+    a.T = n_tail;
+    a.K = params->n_bins;
+    a.F = params->n_frames;
+    a.S = params->stride;
+    a.D = scan_obs_depth(*params);
+    a.reduce = params->reduce;
+    a.keep_mid = params->keep_mid;
+    const size_t N = (size_t)n_envs;
+    hipError_t e = so->arena.alloc(&a.ring, N * a.D * a.K, /*zero=*/true);
+    if (e == hipSuccess) e = so->arena.alloc(&a.head, N, /*zero=*/false);
+    if (e == hipSuccess) e = hipMemset(a.head, 0xff, N * sizeof(int32_t));  // every head -1: empty
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        delete so;  // (the arena frees what was allocated)
+        return hip_fail("f110_scan_obs_create", e, F110_E_ALLOC);
+    }
+    *out = so;
+    return F110_OK;
+}
+
+extern "C" int f110_scan_obs_destroy(f110_scan_obs *so) {
+    delete so;
+    return F110_OK;
+}
+
+extern "C" int f110_scan_obs_push(f110_scan_obs *so, const float *rows, int64_t row_stride, const uint8_t *reset,
+                                  float *out, int64_t out_stride, void *stream) {
+    if (!so) return fail(F110_E_INVALID, "f110_scan_obs_push: null handle");
+    ScanObsArgs a = so->a;
+    const char *bad = scan_obs_bad_push(a.E, a.B + a.M + a.T, scan_obs_width(so->p, a.M, a.T), rows, row_stride, out,
+                                        out_stride);
+    if (bad) return fail(F110_E_INVALID, std::string("f110_scan_obs_push: ") + bad);
+    if (hipSetDevice(so->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_scan_obs_push: hipSetDevice");
+    a.rows = rows;
+    a.row_stride = row_stride;
+    a.reset = reset;
+    a.out = out;
+    a.out_stride = out_stride;
+    a.vec4 = (row_stride % 4 == 0 && ((uintptr_t)rows & 15u) == 0) ? 1 : 0;
+    hipError_t e = launch_scan_obs(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail("f110_scan_obs_push", e);
+    return F110_OK;
+}
+
+extern "C" int f110_scan_obs_reset(f110_scan_obs *so, const uint8_t *env_mask, void *stream) {
+    if (!so) return fail(F110_E_INVALID, "f110_scan_obs_reset: null handle");
+    if (hipSetDevice(so->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_scan_obs_reset: hipSetDevice");
+    hipError_t e = launch_scan_obs_reset(so->a.head, env_mask, so->a.E, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail("f110_scan_obs_reset", e);
+    return F110_OK;
+}
+
+extern "C" int f110_scan_obs_arrays(f110_scan_obs *so, float **ring, int32_t **head) {
+    if (!so) return fail(F110_E_INVALID, "f110_scan_obs_arrays: null handle");
+    if (ring) *ring = so->a.ring;
+    if (head) *head = so->a.head;
     return F110_OK;
 }
 

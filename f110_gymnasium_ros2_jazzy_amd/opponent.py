@@ -240,9 +240,16 @@ class PolicyOpponent:
     other=ego_idx``) when the actor takes the track observation after the ``B + 4A`` columns
     (obs_dim = B + 4A + width); ``act`` then fills the tail of ``obs`` after agent_obs.  It needs
     the env's simulator, so a trainer that builds the snapshot first hands it over with
-    ``set_track_obs`` once the env exists."""
+    ``set_track_obs`` once the env exists.
 
-    def __init__(self, actor, n_envs: int, device, lidar_max: float = 30.0, track_obs=None):
+    ``scan_obs``: a scan_obs.ScanObs of this snapshot's own (its own ring) when the actor takes the
+    compact observation (obs_dim = its width): ``act`` then builds the seat's full row (agent_obs,
+    then the track tail, if any) in a buffer of its own and pushes it into ``obs``, refilling the
+    rows the simulator's ``was_reset`` flags mark.  F110VectorEnv.reset empties the ring.  With both,
+    hand over the scan observation first: the track block's width is then checked against its full
+    row."""
+
+    def __init__(self, actor, n_envs: int, device, lidar_max: float = 30.0, track_obs=None, scan_obs=None):
         from .ddpg import Actor, flatten_params
         from .learner_fused import ExplicitUpdate
         self.device = as_device(device)
@@ -263,18 +270,29 @@ class PolicyOpponent:
         self.flat = flatten_params(self.actor)
         self._scale, self._shift = (t.contiguous() for t in self.actor._affine())
         self.obs = torch.zeros(self.n_envs, self.obs_dim, dtype=torch.float32, device=self.device)
-        self.track_obs = None
+        self.track_obs = self.scan_obs = self._full = None
+        if scan_obs is not None:
+            self.set_scan_obs(scan_obs)
         if track_obs is not None:
             self.set_track_obs(track_obs)
         self.load(actor)
 
     def set_track_obs(self, track_obs):
-        """The TrackObs whose block follows the ``B + 4A`` columns of this actor's observation."""
+        """The TrackObs whose block follows the ``B + 4A`` columns of this actor's (full) observation."""
         sim = track_obs.sim
-        if sim.E != self.n_envs or sim.device != self.device or sim.B + 4 * sim.A + track_obs.width != self.obs_dim:
+        full = self.obs_dim if self.scan_obs is None else self.scan_obs.in_width
+        if sim.E != self.n_envs or sim.device != self.device or sim.B + 4 * sim.A + track_obs.width != full:
             raise ValueError(f"PolicyOpponent: the track observation must be built for {self.n_envs} envs on "
-                             f"{self.device} and fill the actor's {self.obs_dim} columns after B + 4A")
+                             f"{self.device} and fill the actor's {full} columns after B + 4A")
         self.track_obs = track_obs
+
+    def set_scan_obs(self, scan_obs):
+        """The ScanObs that makes this actor's compact observation from the seat's full row."""
+        if scan_obs.n_envs != self.n_envs or scan_obs.device != self.device or scan_obs.width != self.obs_dim:
+            raise ValueError(f"PolicyOpponent: the scan observation must be built for {self.n_envs} envs on "
+                             f"{self.device} and give the actor's {self.obs_dim} columns; it gives {scan_obs.width}")
+        self.scan_obs = scan_obs
+        self._full = torch.zeros(self.n_envs, scan_obs.in_width, dtype=torch.float32, device=self.device)
 
     @staticmethod
     def _flat_of(actor):
@@ -318,16 +336,20 @@ class PolicyOpponent:
         every env, from the simulator outputs ``sim_out`` (obs: the step's obs tensor when the step
         wrote it elsewhere than sim_out.obs), into ``out_rows`` ([n_envs, act_dim] float32, rows may
         be strided) where row_mask != 0 (None: every row).  Three stages on the current stream:
-        f110_agent_obs into the fixed buffer (then the track observation's tail, if any), fc1 and
-        fc2 on the learner GEMMs over all rows, f110_policy_head_rows."""
+        f110_agent_obs into the fixed buffer (then the track observation's tail, if any, and with a
+        scan observation its push from the full row into the fixed compact buffer), fc1 and fc2 on
+        the learner GEMMs over all rows, f110_policy_head_rows."""
         from .learner_fused import ExplicitUpdate
-        agent_obs(sim_out.scans, sim_out.obs if obs is None else obs, agent, self.lidar_max, out=self.obs)
+        full = self.obs if self.scan_obs is None else self._full  # the seat's full row
+        agent_obs(sim_out.scans, sim_out.obs if obs is None else obs, agent, self.lidar_max, out=full)
         head = sim_out.scans.shape[2] + 4 * sim_out.scans.shape[1]
         if self.track_obs is not None:
-            self.track_obs.fill(self.obs[:, head:])
-        elif self.obs_dim != head:  # (no quiet zeros for columns the actor was trained on)
-            raise ValueError(f"PolicyOpponent: the actor takes {self.obs_dim} columns, the step gives {head}: "
+            self.track_obs.fill(full[:, head:])
+        elif full.shape[1] != head:  # (no quiet zeros for columns the actor was trained on)
+            raise ValueError(f"PolicyOpponent: the actor takes {full.shape[1]} columns, the step gives {head}: "
                              "set_track_obs is missing")
+        if self.scan_obs is not None:
+            self.scan_obs.push(full, reset=sim_out.was_reset, out=self.obs)
         h2 = ExplicitUpdate.actor_hidden(self.actor, self.obs)
         return policy_head_rows(h2, self.actor.fc3.weight, self.actor.fc3.bias, self._scale, self._shift, out_rows,
                                 row_mask)

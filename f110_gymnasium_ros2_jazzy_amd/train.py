@@ -25,6 +25,12 @@ Per vector step, everything on the device:
                 --track-preview metres ahead in its own frame and the opponent's gap (one more launch
                 inside the step graphs); the learner's obs_dim grows by the block's width, and a
                 self-play snapshot sees the same block from its own seat
+                with --scan-bins K (no reference counterpart) the observation the policy, the critic,
+                the replay and a self-play snapshot see is compact (scan_obs.ScanObs, one more launch
+                inside the step graphs): the 1080 ranges pooled into K sectors (--scan-reduce min |
+                mean), the last --scan-frames pooled frames stacked --scan-stride steps apart, the pose
+                columns kept (or dropped: --scan-drop-poses), the track block after them; the reward,
+                the opponents and the statistics keep reading the full rows
   reward        CenterlineSafetyProgressReward (:127-146, :179) on the device
   race          with --race-stats (no reference counterpart) the race outcomes per episode on the
                 reward's centerline: progress, lead over the opponent, passes, crash / completed /
@@ -98,7 +104,9 @@ class VectorTrainer:
                  algo: str = "ddpg", policy_delay: int = 2, policy_noise: float = 0.2, noise_clip: float = 0.5,
                  opponent: str = "gap_follow", selfplay_sync: int = 1000, selfplay_fraction: float = 1.0,
                  opponent_speed=None, opponent_lookahead: float | None = None, opponent_rule: str = "gap_follow",
-                 action_repeat: int = 1, race_stats: bool = False, track_obs: bool = False, track_preview=None):
+                 action_repeat: int = 1, race_stats: bool = False, track_obs: bool = False, track_preview=None,
+                 scan_bins: int | None = None, scan_frames: int = 1, scan_stride: int = 1, scan_reduce: str = "min",
+                 scan_keep_poses: bool = True):
         # action_repeat and the opponent arguments: ValueError before anything is built
         from .opponent import check_pursuit_speed
         from .replay import check_action_repeat
@@ -123,6 +131,16 @@ class VectorTrainer:
             tobs_kw = {} if track_preview is None else {"preview": tuple(float(d) for d in track_preview)}
             if len(tobs_kw.get("preview", ())) > MAX_PREVIEW or any(not d > 0.0 for d in tobs_kw.get("preview", ())):
                 raise ValueError(f"track_preview takes at most {MAX_PREVIEW} distances > 0; got {track_preview!r}")
+        sobs_kw = None  # F110VectorEnv's scan_obs argument
+        if scan_bins is None:
+            if (scan_frames, scan_stride, scan_reduce, bool(scan_keep_poses)) != (1, 1, "min", True):
+                raise ValueError("scan_frames, scan_stride, scan_reduce and scan_keep_poses need scan_bins")
+        else:
+            from . import _lib
+            from .scan_obs import scan_obs_params
+            sobs_kw = dict(n_bins=scan_bins, n_frames=scan_frames, stride=scan_stride, reduce=scan_reduce,
+                           keep_mid=bool(scan_keep_poses))
+            scan_obs_params(_lib.default_config().n_beams, **sobs_kw)  # a value out of range: ValueError
         self.selfplay = opponent == "self"
         self.selfplay_sync, self.selfplay_fraction = int(selfplay_sync), float(selfplay_fraction)
         if self.selfplay:
@@ -160,6 +178,8 @@ class VectorTrainer:
             env_kw["race_stats"] = True
         if tobs_kw is not None:  # on the reward's centerline (reward_fn.progress)
             env_kw["track_obs"] = tobs_kw
+        if sobs_kw is not None:  # the learner, the replay and the snapshot see the compact rows
+            env_kw["scan_obs"] = sobs_kw
         learner = lambda obs_dim: DDPGLearner(  # noqa: E731
             obs_dim=obs_dim, act_dim=2, action_low=ACTION_LOW, action_high=ACTION_HIGH, gamma=0.99, tau=0.005,
             actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size, alpha=0.6, beta=0.4,
@@ -184,10 +204,17 @@ class VectorTrainer:
             if tobs_kw is not None:  # the width the env will add (two agents: with the gap columns)
                 from .track_obs import track_obs_params, track_obs_width
                 tail = track_obs_width(track_obs_params(**tobs_kw).n_preview, True)
-            self.agent = learner(_lib.default_config().n_beams + 4 * 2 + tail)
+            beams = _lib.default_config().n_beams
+            width = beams + 4 * 2 + tail
+            if sobs_kw is not None:
+                from .scan_obs import ScanObs, scan_obs_width
+                width = scan_obs_width(beams, 4 * 2, tail, **sobs_kw)
+            self.agent = learner(width)
             if self.agent.explicit is None:
                 raise ValueError("opponent='self' needs a learner with the explicit path")
             self.opp = PolicyOpponent(self.agent.actor, self.N, self.device)
+            if sobs_kw is not None:  # the snapshot's own ring, over its own seat's full rows
+                self.opp.set_scan_obs(ScanObs(self.N, beams, 4 * 2, tail, device=self.device, **sobs_kw))
             mixed = self.selfplay_fraction < 1.0
             self.env = F110VectorEnv(self.N, opponent="mixed" if mixed else "policy", opponent_policy=self.opp,
                                      opponent_mask=selfplay_mask(self.N, env_offset, self.selfplay_fraction)
@@ -237,9 +264,9 @@ class VectorTrainer:
         self._low = torch.tensor(ACTION_LOW, device=self.device)
         self._high = torch.tensor(ACTION_HIGH, device=self.device)
         self.obs, self.info = self.env.reset(seed=seed + rank_seed)
-        if self.train_race is not None:  # the reset observation starts every env's race
+        if self.train_race is not None:  # the reset observation (its full rows) starts every env's race
             for _, g in self._stats:
-                g.race.begin(self.obs[g.lo:g.hi])
+                g.race.begin(self.env.full_obs[g.lo:g.hi])
         self.global_step = 0
         self.last = None
 
@@ -313,9 +340,9 @@ class VectorTrainer:
         env.step, the episode statistics of the two row ranges (eval_envs > 0) and remember."""
         act = self.agent.hold_env(obs_in, act)
         nxt, rew, term, was_reset = self.env.step_transition(act, obs_out=obs_out)
-        if self.eval_envs:  # (the race statistics on the obs buffer the reward saw)
+        if self.eval_envs:  # (the race statistics on the obs buffer the reward saw: the full rows)
             for _, g in self._stats:
-                g.update(rew, nxt, term, self.env.truncated, was_reset)
+                g.update(rew, self.env.full_obs, term, self.env.truncated, was_reset)
         # NEXT_STEP autoreset: a reset row's obs is the previous episode's last
         # observation and its next_obs the new episode's first -- not a transition
         # (remember_env skips the rows with was_reset != 0); eval transitions are stored like any
@@ -480,9 +507,22 @@ def main():
                          "slip, lateral offset and heading error, a centerline preview and the opponent's gap")
     ap.add_argument("--track-preview", default=None, metavar="1,2,4,8",
                     help="--track-obs: the preview distances in metres along the centerline (at most 8)")
+    ap.add_argument("--scan-bins", type=int, default=None, metavar="K",
+                    help="compact observation: pool the 1080 ranges into K sectors on the device (off by default)")
+    ap.add_argument("--scan-frames", type=int, default=None, metavar="F",
+                    help="--scan-bins: stack the last F pooled frames, newest first (1..8, default 1)")
+    ap.add_argument("--scan-stride", type=int, default=None, metavar="S",
+                    help="--scan-bins: simulator steps between stacked frames (1..16, default 1)")
+    ap.add_argument("--scan-reduce", choices=("min", "mean"), default=None,
+                    help="--scan-bins: a sector's value, the minimum (default) or the mean of its ranges")
+    ap.add_argument("--scan-drop-poses", action="store_true",
+                    help="--scan-bins: drop the map-frame pose columns from the compact observation")
     args = ap.parse_args()
     if args.track_preview is not None and not args.track_obs:
         ap.error("--track-preview needs --track-obs")
+    if args.scan_bins is None and (args.scan_frames is not None or args.scan_stride is not None
+                                   or args.scan_reduce is not None or args.scan_drop_poses):
+        ap.error("--scan-frames, --scan-stride, --scan-reduce and --scan-drop-poses need --scan-bins")
     if args.best_by == "progress" and not (args.race_stats and args.eval_envs > 0):
         ap.error("--best-by progress needs --race-stats and --eval-envs")
     rank, world, local = D.init()
@@ -499,7 +539,9 @@ def main():
                        opponent_rule=args.opponent_rule, action_repeat=args.action_repeat,
                        race_stats=args.race_stats, track_obs=args.track_obs,
                        track_preview=None if args.track_preview is None else
-                       [float(d) for d in args.track_preview.split(",") if d.strip()])
+                       [float(d) for d in args.track_preview.split(",") if d.strip()],
+                       scan_bins=args.scan_bins, scan_frames=args.scan_frames or 1, scan_stride=args.scan_stride or 1,
+                       scan_reduce=args.scan_reduce or "min", scan_keep_poses=not args.scan_drop_poses)
     best = -float("inf")
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)

@@ -78,6 +78,19 @@ reward.CenterlineTrack), by default ``reward_fn.progress``, then ``opponent_trac
 ``race_track``.  The reward, the race statistics and the opponents read the wide rows; the infos are
 unchanged.  Off (the default) nothing differs.
 
+``scan_obs=True`` (or a dict of scan_obs.scan_obs_params names: n_bins, n_frames, stride, reduce,
+keep_mid) makes the observation compact on the device (scan_obs.ScanObs): the ``B`` range columns
+pooled into ``n_bins`` sectors, the last ``n_frames`` pooled frames stacked ``stride`` steps apart,
+newest first, the pose groups carried through (or dropped: ``keep_mid=False``) and the track block,
+if any, after them.  The env owns the full-width buffer, the simulator writes its left columns and
+every existing stage (the track observation's fill, the opponents, the reward, the statistics) reads
+it unchanged; one more launch then makes the compact rows ``step``, ``reset`` and
+``step_transition`` return (``obs_out`` is then a compact buffer), which ``obs_dim`` and
+``single_observation_space`` describe.  ``full_obs`` is the last full rows, valid until the next
+step.  ``reset()`` empties the ring; a ``was_reset`` row (a NEXT_STEP autoreset: the new episode's
+first frame) refills its ring, so all of its stacked frames are that frame.  Off (the default)
+nothing differs.
+
 Multi-GPU: give each rank its block of envs (distributed.shard_range) and
 ``env_offset`` = the block's first global id; RNG streams are keyed by global
 env id, so results do not depend on the GPU count.
@@ -105,10 +118,12 @@ class F110VectorEnv:
                  stall_speed: float = 0.0, stall_steps: int | None = None, episode_stats: bool = False,
                  opponent_policy=None, opponent_mask=None, opponent_track=None, opponent_params: dict | None = None,
                  opponent_speed=None, opponent_rule: str = "gap_follow", race_stats: bool = False, race_track=None,
-                 race_params: dict | None = None, track_obs=None, obs_track=None, **kwargs):
+                 race_params: dict | None = None, track_obs=None, obs_track=None, scan_obs=None, **kwargs):
         self.num_envs = int(num_envs)
         self.num_agents = int(num_agents)
         self.params = dict(params or DEFAULT_PARAMS)
+        # a bad scan-observation parameter: ValueError before anything is built
+        sobs_params = self._check_scan_obs(scan_obs, int(kwargs.get("num_beams", 1080)))
         # a bad opponent argument: ValueError before anything is built
         self._check_opponent(opponent, int(opponent_idx), opponent_policy, opponent_mask, opponent_track,
                              opponent_params, opponent_speed, opponent_rule, device)
@@ -171,6 +186,20 @@ class F110VectorEnv:
             self._wide = torch.zeros(self.num_envs, self._head + self._tobs.width, dtype=torch.float32,
                                      device=self.device)
             obs_low, obs_high = np.concatenate([obs_low, self._tobs.low]), np.concatenate([obs_high, self._tobs.high])
+        # the scan observation: every stage keeps reading the full rows in the env's own buffer (the
+        # one above, or one of B + 4A columns); one more launch per step and reset makes the compact
+        # rows the caller gets back
+        self._sobs = self._compact = self._last_full = None
+        if sobs_params is not None:
+            from .scan_obs import ScanObs, scan_obs_columns
+            self._head = B + 4 * A
+            if self._wide is None:
+                self._wide = torch.zeros(self.num_envs, self._head, dtype=torch.float32, device=self.device)
+            tail = self._wide.shape[1] - self._head
+            self._sobs = ScanObs(self.num_envs, B, 4 * A, tail, device=self.device, **sobs_params)
+            self._compact = torch.zeros(self.num_envs, self._sobs.width, dtype=torch.float32, device=self.device)
+            obs_low, obs_high = scan_obs_columns(self._sobs.params, obs_low[B:self._head], obs_high[B:self._head],
+                                                 obs_low[self._head:], obs_high[self._head:])
         self.obs_dim = int(obs_low.shape[0])
         self.single_observation_space = _box(obs_low, obs_high)
         low = np.array([self.params["s_min"], self.params["v_min"]], np.float32)
@@ -287,6 +316,18 @@ class F110VectorEnv:
             raise ValueError("track_obs: opponent_idx must be another agent than ego_idx")
         return track, params
 
+    @staticmethod
+    def _check_scan_obs(scan_obs, n_beams):
+        """The scan-observation argument (host values only): the parameter dict, or None when off."""
+        if scan_obs is None or scan_obs is False:
+            return None
+        if scan_obs is not True and not isinstance(scan_obs, dict):
+            raise ValueError("scan_obs must be None, True or a dict of scan-observation parameters")
+        from .scan_obs import scan_obs_params
+        params = {} if scan_obs is True else dict(scan_obs)
+        scan_obs_params(n_beams, **params)  # unknown names, values out of range: ValueError
+        return params
+
     def _check_race(self, race_stats, track, params, reward_fn, opponent_track, device, ego_idx, opponent_idx):
         """The race-statistics arguments (host values only): the centerline to use, or None when off."""
         if not race_stats:
@@ -378,8 +419,12 @@ class F110VectorEnv:
         self.sim.set_reset_dtype(dt)
         out = self.sim.reset(options)
         self.sim.set_reset_dtype(self.options_dtype)  # the device autoresets
-        src = out.obs if self._tobs is None else self._fill_wide(out.obs)
-        self._opponent_next(out, None if self._tobs is None else src)
+        src = out.obs if self._wide is None else self._fill_wide(out.obs)
+        self._last_full = src
+        scan_opp = getattr(self.opponent_policy, "scan_obs", None)
+        if scan_opp is not None:  # the snapshot's own ring starts over with the env
+            scan_opp.reset()
+        self._opponent_next(out, None if self._wide is None else src)
         if self.reward_fn is not None:
             self.reward_fn.reset()
         if self._episode is not None:
@@ -387,17 +432,29 @@ class F110VectorEnv:
         if self._race is not None:
             self._race.reset()
             self._race.begin(src)
+        if self._sobs is not None:  # an empty ring: every stacked frame is the reset's
+            self._sobs.reset()
+            src = self._sobs.push(src, out=self._compact)
         obs = src.clone()
         return (obs.cpu().numpy() if self.as_numpy else obs), self._infos(out)
 
     def _fill_wide(self, head=None, wide=None):
-        """The wide observation rows (track_obs on): the simulator's ``head`` columns copied into
-        the env's buffer if given (a reset; a step writes them in place), then the tail."""
+        """The full observation rows in the env's own buffer (track_obs or scan_obs on): the
+        simulator's ``head`` columns copied in if given (a reset; a step writes them in place), then
+        the track observation's tail, if any."""
         wide = self._wide if wide is None else wide
         if head is not None:
             wide[:, :self._head] = head
-        self._tobs.fill(wide[:, self._head:])
+        if self._tobs is not None:
+            self._tobs.fill(wide[:, self._head:])
         return wide
+
+    @property
+    def full_obs(self):
+        """The last full observation rows [N, B + 4A (+ the track block)] every stage read (the reward,
+        the statistics, the opponents): with scan_obs on what the compact rows were made from.
+        Read-only, valid until the next step or reset; None before the first reset."""
+        return self._last_full
 
     def _route(self, actions, own_rows=False):
         """The step's [N, A, 2] action rows: with an opponent the caller's rows copied into the env's
@@ -417,18 +474,23 @@ class F110VectorEnv:
 
     def _advance(self, a, obs_out=None):
         """One step of every stage, in order: the simulator (into obs_out, if given), the track
-        observation's tail, the next opponent action, the reward, the episode and race statistics.
-        Returns (out, obs, rewards): the simulator's outputs, the rows every stage read (the
-        simulator's own, the env's wide buffer, or obs_out) and the reward's own buffer."""
-        if self._tobs is None:
+        observation's tail, the next opponent action, the reward, the episode and race statistics,
+        the scan observation's compact rows.  Returns (out, obs, rewards): the simulator's outputs,
+        the rows the caller gets (what every stage read: the simulator's own, the env's wide buffer,
+        or obs_out; with scan_obs on the compact rows made from them, in the env's compact buffer
+        or obs_out) and the reward's own buffer."""
+        if self._wide is None:
             out = self.sim.step(a, obs_out=obs_out)  # the simulator writes obs_out itself (no copy)
             obs = out.obs if obs_out is None else obs_out
         else:  # the simulator writes the left columns of the wide rows, one launch fills the tail
             obs = self._wide
-            if obs_out is not None:
-                obs = f32_rows(obs_out, self.num_envs, self.obs_dim, self.device, "obs_out", copy_ok=False)[0]
+            if obs_out is not None:  # (checked before the simulator moves)
+                obs_out = f32_rows(obs_out, self.num_envs, self.obs_dim, self.device, "obs_out", copy_ok=False)[0]
+                if self._sobs is None:
+                    obs = obs_out
             out = self.sim.step(a, obs_out=obs[:, :self._head])
             self._fill_wide(wide=obs)
+        self._last_full = obs
         self._opponent_next(out, None if obs is out.obs else obs)
         if self.reward_fn is not None:  # reset envs: reward_fn.reset(), reward 0 (the u8 flags as they are)
             rewards = self.reward_fn(obs, reset_mask=out.was_reset)
@@ -439,6 +501,8 @@ class F110VectorEnv:
             self._episode.update(rewards, out.terminated, out.truncated, out.was_reset)
         if self._race is not None:
             self._race.update(obs, out.terminated, out.truncated, out.was_reset)
+        if self._sobs is not None:  # the compact rows of the full ones; a reset row refills its ring
+            obs = self._sobs.push(obs, reset=out.was_reset, out=self._compact if obs_out is None else obs_out)
         return out, obs, rewards
 
     def step(self, actions):
@@ -473,7 +537,8 @@ class F110VectorEnv:
         (valid until the next step); the 4-tuple is unchanged, and a trainer keeps
         storing ``terminated`` as done: a truncated transition bootstraps from its
         next_obs, and the reset row after it is skipped like any other.
-        With track_obs on obs_dim is the wide width and obs_out a wide buffer, whose tail is filled too."""
+        With track_obs on obs_dim is the wide width and obs_out a wide buffer, whose tail is filled too.
+        With scan_obs on obs_dim is the compact width and obs_out a compact buffer."""
         if self.as_numpy:
             raise ValueError("step_transition: device tensors only (as_numpy=False)")
         out, obs, rewards = self._advance(self._route(actions, own_rows=True), obs_out)
@@ -512,6 +577,9 @@ class F110VectorEnv:
         self._race.reset_totals()
 
     def close(self):
+        if getattr(self, "_sobs", None) is not None:
+            self._sobs.close()
+            self._sobs = None
         if getattr(self, "sim", None) is not None:
             self.sim.close()
             self.sim = None

@@ -631,6 +631,58 @@ F110_API int f110_track_obs(const f110_track *track, const f110_track_obs_params
 F110_API int f110_ctx_track_obs(f110_ctx *ctx, const f110_track *track, const f110_track_obs_params *params,
                                 int32_t seat, int32_t other, float *out, int64_t out_stride, void *stream);
 
+/* ---- scan observation (no reference counterpart: _pack_flat_obs hands the policy all 1080 ranges) --
+ * A compact policy row made from the full observation row on the device: the range columns pooled
+ * into sectors, the last few pooled frames stacked, the other columns carried through.  The full
+ * rows stay what they are for everything else that reads them (the reward, the race statistics,
+ * the opponents, the track observation's fill); off unless a caller asks for it.
+ *   input row   [B range columns | M middle columns (the 4A pose groups) | T tail columns (the
+ *               track block; may be 0)], float32, unit column stride, rows row_stride floats apart
+ *   output row  [F*K | M if keep_mid | T], width = f110_scan_obs_width = F*K + keep_mid*M + T
+ * One push of one env, K = n_bins, F = n_frames, S = stride, D = (F-1)*S + 1 (the ring depth):
+ *   1. pooling: bin j < K covers beams [floor(j*B/K), floor((j+1)*B/K)) (64-bit integers; the bins
+ *      may be ragged, K == B is the identity).  min: fminf over the bin, ascending.  mean: a float32
+ *      sum over the bin in ascending beam order starting from the first beam's value, divided by
+ *      (float)count -- IEEE division, no contraction.
+ *   2. ring: per env D slots of K float32 and an int32 head, -1 = empty.  With head == -1 or the
+ *      env's reset flag nonzero every slot takes the pooled frame and head becomes 0 (a refill);
+ *      otherwise head becomes (head + 1) % D and that slot takes the pooled frame.
+ *   3. output: frame j < F (0 = newest) is slot (head - j*S) mod D, at columns [j*K, (j+1)*K); the
+ *      middle (if kept) and tail columns are the current input row's, not stacked.
+ * All float32 and in a fixed order, so the device and the host statement (f110_host_scan_obs_push,
+ * f110_debug.h) agree in every bit.  Limits (by design): 1 <= K <= B <= 4096, 1 <= F <= 8,
+ * 1 <= S <= 16, D <= 32. */
+typedef struct f110_scan_obs f110_scan_obs;
+typedef struct f110_scan_obs_params {
+    int32_t n_bins;    /* K: pooled sectors, 1..n_beams (108) */
+    int32_t n_frames;  /* F: stacked frames, 1..8 (1) */
+    int32_t stride;    /* S: simulator steps between stacked frames, 1..16 (1) */
+    int32_t reduce;    /* 0 = min (default), 1 = mean */
+    int32_t keep_mid;  /* 1: carry the middle columns (default), 0: drop them */
+} f110_scan_obs_params;
+
+/* Host-only helpers.  f110_scan_obs_width: the output row's width in floats, or -1 for parameters
+ * or a shape f110_scan_obs_create would refuse. */
+F110_API void f110_default_scan_obs_params(f110_scan_obs_params *p);
+F110_API int32_t f110_scan_obs_width(const f110_scan_obs_params *params, int32_t n_beams, int32_t n_mid,
+                                     int32_t n_tail);
+
+/* The ring [n_envs][D][K] float32 and the heads [n_envs] int32 (all -1) on `device`.
+ * F110_E_INVALID: a null pointer, n_envs < 1, a shape or parameter outside the limits above. */
+F110_API int f110_scan_obs_create(f110_scan_obs **out, int32_t device, int64_t n_envs, int32_t n_beams,
+                                  int32_t n_mid, int32_t n_tail, const f110_scan_obs_params *params);
+F110_API int f110_scan_obs_destroy(f110_scan_obs *so);
+/* One push of every env: rows / out device float32 (row e at rows + e*row_stride, out + e*out_stride),
+ * reset device u8 [n_envs] or NULL (no env resets).  One launch, one wave per env; the head is on
+ * the device: no allocation, no host synchronisation, no atomics (capturable); async on stream.
+ * F110_E_INVALID: a null pointer, row_stride < B + M + T, out_stride < width, out overlapping rows. */
+F110_API int f110_scan_obs_push(f110_scan_obs *so, const float *rows, int64_t row_stride, const uint8_t *reset,
+                                float *out, int64_t out_stride, void *stream);
+/* Empties the rings (head = -1) of the envs with env_mask != 0; the next push refills them. */
+F110_API int f110_scan_obs_reset(f110_scan_obs *so, const uint8_t *env_mask /* NULL = all */, void *stream);
+/* The device ring and heads (tests); either may be NULL. */
+F110_API int f110_scan_obs_arrays(f110_scan_obs *so, float **ring, int32_t **head);
+
 /* ---- prioritized experience replay ---------------------------------------------
  * Replaces rl_training/DDPG/replay_buffer.py:PrioritizedExperienceReplayBuffer
  * (:6-135), the DDPG agent's memory (agent.py:194): a ring of transitions

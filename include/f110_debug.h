@@ -368,6 +368,17 @@ F110_API int f110_host_track_obs(const f110_track *track, const f110_track_obs_p
                                  int64_t n_envs, int32_t n_agents, int32_t seat, int32_t other, float *out,
                                  int64_t out_stride);
 
+/* f110_scan_obs_push over HOST arrays: the same row rule (csrc/f110_scan_obs.h), envs in ascending
+ * order, with the shape and the state passed in: ring [n_envs][D][K] float32 and head [n_envs] int32
+ * (f110_scan_obs_arrays' layout; head -1 = empty), updated in place.  Same validation
+ * (F110_E_INVALID), and a head outside [-1, D) is refused too.  Pure host code: the sanitizer
+ * program links it.  Host test hook: the CPU suite and the GPU tests share one statement of the
+ * semantics. */
+F110_API int f110_host_scan_obs_push(const f110_scan_obs_params *params, int64_t n_envs, int32_t n_beams,
+                                     int32_t n_mid, int32_t n_tail, const float *rows, int64_t row_stride,
+                                     const uint8_t *reset, float *ring, int32_t *head, float *out,
+                                     int64_t out_stride);
+
 #ifdef __cplusplus
 }
 #endif
