@@ -103,6 +103,11 @@ class F110ScanObsParams(ctypes.Structure):  # f110_scan_obs_params
     _fields_ = [(n, ctypes.c_int32) for n in ("n_bins", "n_frames", "stride", "reduce", "keep_mid")]
 
 
+class F110SpawnRange(ctypes.Structure):  # f110_spawn_range (zero bytes = the agent's base pose at rest)
+    _fields_ = [("lateral", ctypes.c_double * 2), ("heading", ctypes.c_double * 2), ("speed", ctypes.c_double * 2),
+                ("gap", ctypes.c_int32 * 2), ("behind", ctypes.c_double), ("clearance", ctypes.c_double)]
+
+
 class F110RayKnobs(ctypes.Structure):  # f110_ray_knobs (include/f110_debug.h)
     _fields_ = [(n, ctypes.c_int32) for n in
                 ("kernel", "lanes", "refill", "fxs_lds", "count_slots", "wtrace", "heavy_list", "heavy_on",
@@ -127,6 +132,9 @@ RACE_TOTALS_BYTES = 112               # f110_race_totals
 RACE_FLAGS = dict(STARTED=1, CLOSED=2, S0=4, S1=8, AHEAD=16, OPP_CRASHED=32)  # f110_race_state.flags
 RACE_RESULT = dict(finished=1, ego_crash=2, completed=4, truncated=8, opp_crashed=16, ahead_at_end=32)  # result bits
 
+SPAWN_RANGE_BYTES = 72                # f110_spawn_range
+SPAWN_FIELDS = tuple(n for n, _ in F110SpawnRange._fields_)  # lateral, heading, speed, gap: (lo, hi); behind, clearance
+
 PARAM_FIELDS = tuple(n for n, _ in F110Params._fields_)
 DYN_FIELDS = PARAM_FIELDS[:16]  # the fields a context may hold per env (f110_set_env_params)
 
@@ -139,6 +147,7 @@ INTEGRATOR_EULER = 2
 _i, _i32, _i64, _u64 = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _f32, _f64 = ctypes.c_float, ctypes.c_double
 _PP = ctypes.POINTER(F110Params)
+_SR = ctypes.POINTER(F110SpawnRange)
 _OUT = ctypes.POINTER(F110Outputs)
 _PTRS6 = [ctypes.POINTER(_P)] * 6
 _EXPLORE = [_P] * 5 + [_i32] * 3 + [_P, _P, _f64, _f64, _P, _P, _u64, _P, _i64]  # f110_ddpg_actor_explore less its stream
@@ -219,6 +228,11 @@ _API = {
     "f110_set_param_randomization": (_i, [_P, _PP, _PP, _u64, _P]),
     "f110_host_check_param_ranges": (_i, [_PP, _PP, _PP, _i32]),
     "f110_host_param_draw": (_i, [_u64, _i64, _i32, _u64, _PP, _PP, _PP]),
+    "f110_set_spawn_randomization": (_i, [_P, _SR, _u64, _P]),
+    "f110_get_spawn_state": (_i, [_P, _P, _P]),
+    "f110_host_check_spawn_ranges": (_i, [_SR, _i32, _i32]),
+    "f110_host_spawn_rows": (_i, [_SR, _i32, _u64, _u64, _P, _i32, _i32, _f64, _D, _P, _i32, _P, _P, _P, _P, _i64, _i32,
+                                  _P, _P]),
     "f110_set_episode_limits": (_i, [_P, _i64, _f64, _i32, _P, _P]),
     "f110_host_check_episode_limits": (_i, [_i64, _f64, _i32]),
     "f110_episode_scratch_bytes": (_i64, [_i64]),

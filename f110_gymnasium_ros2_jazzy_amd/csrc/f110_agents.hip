@@ -13,6 +13,7 @@
 #include "f110_rng.h"
 #include "f110_sincos.h"
 #include "f110_sincos_table.h"
+#include "f110_spawn.h"
 #include "f110_step_args.h"
 
 namespace f110 {
@@ -139,7 +140,11 @@ __device__ void handoff_chunks(const StepArgs &a, int g, const float *sx, const 
 // car's row is loaded with the prologue and update_pose reads a local f110_params built from it
 // (width, length, lidar_max from a.pa[ag]); with a range table too (a.prange) a resetting car first
 // redraws its row (param_draw) and stores it.  Without PENV nothing of this is compiled in.
-template <bool HMASK, bool PENV>
+// SPAWN: the context draws start states (a.srange, f110_set_spawn_randomization): the agent's range
+// block is loaded with the prologue, and a resetting car perturbs its base pose (f110_spawn.h: the
+// gap's table row, the cleared lateral offset, the heading offset), starts at the drawn speed and
+// stores (x, y, yaw, speed) in a.spawn_state.  Without SPAWN nothing of this is compiled in.
+template <bool HMASK, bool PENV, bool SPAWN>
 __global__ void __launch_bounds__(64) k_agents(StepArgs a) {
     const int g = blockIdx.x * 64 + threadIdx.x;
     const int EA = a.E * a.A;
@@ -155,7 +160,9 @@ __global__ void __launch_bounds__(64) k_agents(StepArgs a) {
     uint32_t episode = 0;
     uint64_t nstep = 0;
     double pv[PENV ? kDynFields : 1] = {};  // the car's table row (padding threads read none)
+    f110_spawn_range sr = {};                // the agent's spawn ranges
     if (valid) {
+        if (SPAWN) sr = a.srange[ag];
         if (ag == 0) nstep = a.nstep[e];
         if (PENV) {
 #pragma unroll
@@ -259,16 +266,29 @@ __global__ void __launch_bounds__(64) k_agents(StepArgs a) {
     if (do_reset) {
         // RaceCar.reset (base_classes.py:183-204), then F110Env.reset's zero-action step (f110_env.py:457)
         const double *pz;
+        SpawnDraws sw = {};
+        if (SPAWN) sw = spawn_draws(a.sseed, genv, ag, a.mode == 1 ? 0ull : (uint64_t)episode + 1ull, sr);
         if (a.mode == 1) {
             pz = a.reset_poses + (size_t)g * 3;
         } else {
             uint32_t k = spawn_draw(a.seed, genv, episode) % (uint32_t)a.n_spawn;
-            pz = a.spawn + ((size_t)k * A + ag) * 3;
+            int col = ag;
+            if (SPAWN && !spawn_own_column(sr)) {  // the gap: column 0 of the shifted row
+                k = spawn_shift_row(k, sw.mag, sw.behind, (uint32_t)a.n_spawn);
+                col = 0;
+            }
+            pz = a.spawn + ((size_t)k * A + col) * 3;
         }
         // float32 options (train_ddpg's dtype): the poses are float32 values
         // and start_rot is NumPy's float32 cos / sin of the float32 yaw
         double px = pz[0], py = pz[1], pth = pz[2];
-        if (a.reset_f32) {
+        double ss[4] = {0.0, 0.0, 0.0, 0.0};
+        if (SPAWN) {  // the perturbed pose, rounded under float32 options where the base pose is
+            spawn_pose(a.map, px, py, pth, sw, sr.clearance, a.reset_f32 != 0, ss, tab);
+            px = ss[0];
+            py = ss[1];
+            pth = ss[2];
+        } else if (a.reset_f32) {
             px = (double)(float)px;
             py = (double)(float)py;
             pth = (double)(float)pth;
@@ -278,6 +298,11 @@ __global__ void __launch_bounds__(64) k_agents(StepArgs a) {
         s[0] = px;
         s[1] = py;
         s[4] = pth;
+        if (SPAWN) {
+            s[3] = ss[3];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a.spawn_state[(size_t)k * EA + g] = ss[k];
+        }
         b0 = b1 = 0.0;
         cnt = 0;
         raw_steer = 0.0;
@@ -337,14 +362,17 @@ __global__ void __launch_bounds__(64) k_agents(StepArgs a) {
     }
 }
 
-// 64-thread blocks: a few thousand cars must still spread over all CUs.  <HMASK, PENV>: a context
-// without hand-off masks / without a per-env table launches the instantiations compiled without them.
+// 64-thread blocks: a few thousand cars must still spread over all CUs.  <HMASK, PENV, SPAWN>: a context
+// without hand-off masks / a per-env table / spawn ranges launches the instantiations compiled without them.
 hipError_t launch_agents(const StepArgs &a, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
-    static void (*const fn[2][2])(StepArgs) = {{k_agents<false, false>, k_agents<false, true>},
-                                               {k_agents<true, false>, k_agents<true, true>}};
+    static void (*const fn[2][2][2])(StepArgs) = {
+        {{k_agents<false, false, false>, k_agents<false, false, true>},
+         {k_agents<false, true, false>, k_agents<false, true, true>}},
+        {{k_agents<true, false, false>, k_agents<true, false, true>},
+         {k_agents<true, true, false>, k_agents<true, true, true>}}};
     const int EA = a.E * a.A;
-    hipExtLaunchKernelGGL(fn[a.hmask != nullptr][a.ptab != nullptr], dim3((EA + 63) / 64), dim3(64), 0, s, start, stop,
-                          0, a);
+    hipExtLaunchKernelGGL(fn[a.hmask != nullptr][a.ptab != nullptr][a.srange != nullptr], dim3((EA + 63) / 64), dim3(64),
+                          0, s, start, stop, 0, a);
     return hipGetLastError();
 }
 

@@ -487,6 +487,11 @@ static StepArgs make_step_args(f110_ctx *c, const f110_outputs *out) {
         a.stall = c->stall_steps ? c->stall : nullptr;
         a.truncated = c->truncated;
     }
+    if (c->spawn_on) {
+        a.srange = c->srange;
+        a.spawn_state = c->spawn_state;
+        a.sseed = c->sseed;
+    }
     return a;
 }
 
@@ -762,6 +767,40 @@ extern "C" int f110_set_param_randomization(f110_ctx *ctx, const f110_params *lo
     HIP_TRY(hipStreamSynchronize(s));
     ctx->pseed = seed;
     ctx->ptab_on = ctx->prange_on = true;
+    return F110_OK;
+}
+
+// ---------------------------------------------------- spawn randomization --
+extern "C" int f110_set_spawn_randomization(f110_ctx *ctx, const f110_spawn_range *ranges, uint64_t seed, void *stream) {
+    if (!ctx) return fail(F110_E_INVALID, "f110_set_spawn_randomization: null context");
+    if (!ranges) {  // off; the buffers stay
+        ctx->spawn_on = false;
+        return F110_OK;
+    }
+    const int A = ctx->cfg.n_agents;
+    const int rc = check_spawn_ranges("f110_set_spawn_randomization", ranges, A, ctx->n_spawn);
+    if (rc != F110_OK) return rc;  // (before any device call)
+    if (use_device(ctx) != F110_OK) return F110_E_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    if (!ctx->srange) {
+        hipError_t e = ctx->alloc(&ctx->srange, (size_t)A);
+        if (e == hipSuccess) e = ctx->alloc(&ctx->spawn_state, (size_t)4 * ctx->cfg.n_envs * A);  // (zero-filled)
+        if (e != hipSuccess) return hip_fail("hipMalloc spawn ranges", e, F110_E_ALLOC);
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->srange, ranges, (size_t)A * sizeof(f110_spawn_range), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // the caller's array may go away
+    ctx->sseed = seed;
+    ctx->spawn_on = true;
+    return F110_OK;
+}
+
+extern "C" int f110_get_spawn_state(f110_ctx *ctx, double *out, void *stream) {
+    if (!ctx || !out) return fail(F110_E_INVALID, "f110_get_spawn_state: null argument");
+    if (!ctx->spawn_state)
+        return fail(F110_E_INVALID, "f110_get_spawn_state: f110_set_spawn_randomization was never turned on");
+    if (use_device(ctx) != F110_OK) return F110_E_HIP;
+    const size_t EA = (size_t)ctx->cfg.n_envs * ctx->cfg.n_agents;
+    HIP_TRY(hipMemcpyAsync(out, ctx->spawn_state, 4 * EA * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return F110_OK;
 }
 

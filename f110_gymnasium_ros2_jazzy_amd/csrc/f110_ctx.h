@@ -101,6 +101,12 @@ struct f110_ctx {
     int32_t stall_steps = 0;
     int32_t *stall = nullptr;
     uint8_t *truncated = nullptr;  // caller-owned
+    // spawn randomization (f110_set_spawn_randomization); both buffers are allocated by the first
+    // call that turns it on and kept until f110_destroy
+    f110_spawn_range *srange = nullptr;  // [A]
+    double *spawn_state = nullptr;       // [4][E*A]
+    bool spawn_on = false;               // resetting cars draw their start state
+    uint64_t sseed = 0;
 
     hipEvent_t *next_prof_events() {
         if (prof_n >= prof_max) return nullptr;

@@ -3,7 +3,8 @@
 // (Felzenszwalb-Huttenlocher lower envelopes, integer arithmetic) and the tables built from it,
 // the beam-index and sin/cos test hooks, the ray-launch decision (ray_rules, plan_ray_launch), the
 // argument checks of the params / episode / n-step entry points and their host models, the
-// derivation of a track's arrays, and the scan observation's host statement.  It links on its own (tests/host_check runs it under ASan / UBSan).
+// derivation of a track's arrays, and the host statements of the scan observation and the spawn
+// randomization.  It links on its own (tests/host_check runs it under ASan / UBSan).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -23,6 +24,7 @@
 #include "f110_math.h"
 #include "f110_scan_obs.h"
 #include "f110_sincos.h"
+#include "f110_spawn.h"
 #include "f110_step_args.h"
 #include "f110_task_args.h"
 
@@ -549,6 +551,89 @@ extern "C" int f110_host_param_draw(uint64_t seed, int64_t env, int32_t agent, u
     param_draw(seed, (uint64_t)env, agent, episode, range, v);
     *out = *lo;
     std::memcpy(out, v, sizeof(v));
+    return F110_OK;
+}
+
+// ---------------------------------------------------- spawn randomization --
+namespace f110 {
+
+int check_spawn_ranges(const char *who, const f110_spawn_range *ranges, int32_t n_agents, int32_t n_spawn) {
+    if (!ranges || n_agents <= 0) return fail(F110_E_INVALID, std::string(who) + ": null argument");
+    for (int i = 0; i < n_agents; ++i) {
+        const f110_spawn_range &r = ranges[i];
+        const std::string where = " (agent " + std::to_string(i) + ")";
+        const auto bad = [&](const char *field, const char *what) {
+            return fail(F110_E_INVALID, std::string(who) + ": " + field + where + " " + what);
+        };
+        const struct {
+            const char *name;
+            const double *v;
+        } pairs[3] = {{"lateral", r.lateral}, {"heading", r.heading}, {"speed", r.speed}};
+        for (const auto &p : pairs) {
+            if (!std::isfinite(p.v[0]) || !std::isfinite(p.v[1])) return bad(p.name, "is not finite");
+            if (p.v[0] > p.v[1]) return bad(p.name, "has lo > hi");
+            if (!std::isfinite(p.v[1] - p.v[0])) return bad(p.name, "hi - lo is not finite");
+        }
+        if (r.gap[0] < 0 || r.gap[1] < 0) return bad("gap", "is negative");
+        if (r.gap[0] > r.gap[1]) return bad("gap", "has lo > hi");
+        if (!std::isfinite(r.behind)) return bad("behind", "is not finite");
+        if (r.behind < 0.0 || r.behind > 1.0) return bad("behind", "is outside [0, 1]");
+        if (!std::isfinite(r.clearance)) return bad("clearance", "is not finite");
+        if (r.clearance < 0.0) return bad("clearance", "is negative");
+        if (r.gap[1] > 0 && n_spawn <= 0) return bad("gap", "is non-zero on a context without a spawn table");
+    }
+    return F110_OK;
+}
+
+}  // namespace f110
+
+extern "C" int f110_host_check_spawn_ranges(const f110_spawn_range *ranges, int32_t n_agents, int32_t n_spawn) {
+    return check_spawn_ranges("f110_host_check_spawn_ranges", ranges, n_agents, n_spawn);
+}
+
+extern "C" int f110_host_spawn_rows(const f110_spawn_range *ranges, int32_t n_agents, uint64_t seed, uint64_t ctx_seed,
+                                    const double *edt, int32_t H, int32_t W, double resolution, const double origin[3],
+                                    const double *spawn, int32_t n_spawn, const double *poses, const int32_t *rows,
+                                    const int64_t *envs, const uint64_t *episodes, int64_t n, int32_t reset_f32,
+                                    double *out, int32_t *rows_out) {
+    const char *who = "f110_host_spawn_rows";
+    if (!edt || H <= 0 || W <= 0 || !(resolution > 0) || !origin || n < 0 || (n > 0 && (!envs || !out)))
+        return fail(F110_E_INVALID, std::string(who) + ": bad arguments");
+    if (!poses && (!spawn || n_spawn <= 0))
+        return fail(F110_E_INVALID, std::string(who) + ": an autoreset needs a spawn table");
+    const int rc = check_spawn_ranges(who, ranges, n_agents, spawn ? n_spawn : 0);
+    if (rc != F110_OK) return rc;
+    if (!poses)
+        for (int64_t i = 0; i < n; ++i) {
+            if (rows && (rows[i] < 0 || rows[i] >= n_spawn)) return fail(F110_E_INVALID, std::string(who) + ": row out of range");
+            if (!rows && (!episodes || episodes[i] == 0))
+                return fail(F110_E_INVALID, std::string(who) + ": an autoreset's episode is >= 1");
+        }
+    const MapView m = make_map_view(edt, H, W, resolution, origin);
+    const size_t A = (size_t)n_agents;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint64_t env = (uint64_t)envs[i], episode = episodes ? episodes[i] : 0;
+        for (int ag = 0; ag < n_agents; ++ag) {
+            const f110_spawn_range &r = ranges[ag];
+            const SpawnDraws w = spawn_draws(seed, env, ag, episode, r);
+            const double *pz;
+            int32_t row = -1;
+            if (poses) {
+                pz = poses + ((size_t)i * A + (size_t)ag) * 3;
+            } else {
+                uint32_t k = rows ? (uint32_t)rows[i] : spawn_draw(ctx_seed, env, episode - 1) % (uint32_t)n_spawn;
+                int col = ag;
+                if (!spawn_own_column(r)) {
+                    k = spawn_shift_row(k, w.mag, w.behind, (uint32_t)n_spawn);
+                    col = 0;
+                }
+                row = (int32_t)k;
+                pz = spawn + ((size_t)k * A + (size_t)col) * 3;
+            }
+            spawn_pose(m, pz[0], pz[1], pz[2], w, r.clearance, reset_f32 != 0, out + ((size_t)i * A + (size_t)ag) * 4);
+            if (rows_out) rows_out[(size_t)i * A + (size_t)ag] = row;
+        }
+    }
     return F110_OK;
 }
 

@@ -86,6 +86,10 @@ int check_param_row(const char *who, const f110_params &row, const f110_params &
 int check_param_ranges(const char *who, const f110_params *lo, const f110_params *hi, const f110_params *agents,
                        int32_t n_agents);
 
+// ---- spawn randomization --------------------------------------------------------
+// f110_set_spawn_randomization's validation (n_spawn: the rows of the spawn table, 0 = none)
+int check_spawn_ranges(const char *who, const f110_spawn_range *ranges, int32_t n_agents, int32_t n_spawn);
+
 // ---- episode limits and statistics -------------------------------------------
 int check_episode_limits(const char *who, int64_t max_steps, double stall_speed, int32_t stall_steps);
 int check_episode_args(const char *who, const double *rewards, const uint8_t *terminated, const uint8_t *was_reset,

@@ -97,6 +97,10 @@ struct StepArgs {
     int32_t stall_steps;   // standing steps in a row that truncate, 0 = none
     int32_t *stall;        // [E] the stall counters (set when stall_steps != 0)
     uint8_t *truncated;    // [E] the caller's flag buffer, or null
+    // spawn randomization (f110_set_spawn_randomization; appended for the same reason)
+    const f110_spawn_range *srange;  // [A] the agents' ranges (k_agents<., ., SPAWN>), or null: off
+    double *spawn_state;             // [4][E*A] (x, y, yaw, speed) of each car's last drawn reset
+    uint64_t sseed;                  // f110_set_spawn_randomization's seed
 };
 
 // RN(1 / lidar_max) in f32 for k_rays_fxs's obs division, or 0 (the IEEE

@@ -81,6 +81,65 @@ def param_range_rows(ranges, agent_params: list):
     return lo, hi
 
 
+def spawn_range_rows(ranges, n_agents: int):
+    """The f110_spawn_range array [A] (f110_set_spawn_randomization's argument) from one dict for all
+    agents or one dict per agent: "lateral", "heading", "speed" and "gap" -> (lo, hi), "behind" and
+    "clearance" -> a number; names left out stay 0 (no offset, at rest, the agent's own column).
+    Host only."""
+    A = int(n_agents)
+    per_agent = [ranges] * A if isinstance(ranges, dict) else list(ranges)
+    if len(per_agent) != A:
+        raise ValueError(f"spawn ranges: one dict, or one per agent ({A}); got {len(per_agent)}")
+    rows = (_lib.F110SpawnRange * A)()
+    for row, r in zip(rows, per_agent):
+        bad = [k for k in r if k not in _lib.SPAWN_FIELDS]
+        if bad:
+            raise ValueError(f"spawn ranges: unknown name {bad[0]!r} (known: {', '.join(_lib.SPAWN_FIELDS)})")
+        for k, v in r.items():
+            if k in ("behind", "clearance"):
+                setattr(row, k, float(v))
+                continue
+            try:
+                lo, hi = v
+            except (TypeError, ValueError):
+                raise ValueError(f"spawn ranges: {k} must be a (lo, hi) pair") from None
+            if k == "gap":
+                if int(lo) != lo or int(hi) != hi:
+                    raise ValueError("spawn ranges: gap counts whole table rows")
+                row.gap[0], row.gap[1] = int(lo), int(hi)
+            else:
+                getattr(row, k)[0], getattr(row, k)[1] = float(lo), float(hi)
+    return rows
+
+
+def host_spawn_rows(ranges, seed: int, track: TrackMap, envs, n_agents: int, poses=None, spawn=None, rows=None,
+                    episodes=None, ctx_seed: int = 0, reset_f32: bool = False):
+    """The start states resetting envs draw, on the host (f110_host_spawn_rows: the device's row rule
+    over the track's EDT): ([n, A, 4] float64 (x, y, yaw, speed), [n, A] int32 table rows).  ranges: a
+    spawn_range_rows array or its argument; envs: global env ids [n]; poses [n, A, 3]: a reset()'s
+    base poses -- else an autoreset from the table ``spawn`` [S, A, 3], whose rows are ``rows`` [n] or,
+    without them, the draws of a context seeded ``ctx_seed``; episodes [n]: 0 for a reset (the
+    default), the finished episode's number + 1 for an autoreset.  Host only."""
+    L = _lib.load()
+    A = int(n_agents)
+    if not isinstance(ranges, ctypes.Array):
+        ranges = spawn_range_rows(ranges, A)
+    envs = np.ascontiguousarray(envs, dtype=np.int64)
+    n = envs.shape[0]
+    edt = np.ascontiguousarray(track.dt(), dtype=np.float64)  # res * sqrt(k): the table the context uploads
+    origin = (ctypes.c_double * 3)(*track.origin)
+    opt = lambda a, dt, shape: None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(shape)  # noqa: E731
+    poses, rows, episodes = opt(poses, np.float64, (n, A, 3)), opt(rows, np.int32, (n,)), opt(episodes, np.uint64, (n,))
+    spawn = opt(spawn, np.float64, (-1, A, 3))
+    out, rows_out = np.empty((n, A, 4), np.float64), np.empty((n, A), np.int32)
+    p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    _lib.check(L.f110_host_spawn_rows(ranges, A, int(seed) & 0xFFFFFFFFFFFFFFFF, int(ctx_seed) & 0xFFFFFFFFFFFFFFFF,
+                                      p(edt), track.height, track.width, track.resolution, origin, p(spawn),
+                                      0 if spawn is None else spawn.shape[0], p(poses), p(rows), p(envs), p(episodes), n,
+                                      int(bool(reset_f32)), p(out), p(rows_out)), "f110_host_spawn_rows")
+    return out, rows_out
+
+
 class BatchSim:
     """Batched simulator on one device.
 
@@ -290,6 +349,34 @@ class BatchSim:
         sd = (int(self.cfg.seed) if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
         _lib.check(self.L.f110_set_param_randomization(self.ctx, lo.ctypes.data_as(PP), hi.ctypes.data_as(PP), sd,
                                                        self._stream()), "f110_set_param_randomization")
+
+    # ---- spawn randomization (f110_set_spawn_randomization) --------------------
+    def set_spawn_randomization(self, ranges, seed: int | None = None):
+        """Start-state randomization on the device (f110_set_spawn_randomization): every car that
+        resets (reset(), or an autoreset inside step / step_n / a captured graph) starts from its base
+        pose moved sideways by ``lateral`` m (halved up to three times, then dropped, until the EDT
+        there is at least ``clearance``), turned by ``heading`` rad and rolling at ``speed`` m/s; in
+        an autoreset an agent with a ``gap`` takes column 0 of the spawn row ``gap`` rows ahead of the
+        env's (behind it with probability ``behind``).  Keyed by (seed, global env id, agent, episode).
+
+        ranges: one dict for all agents or one per agent (spawn_range_rows).  ``None`` turns it off.
+        seed: default the context's seed."""
+        if ranges is None:
+            _lib.check(self.L.f110_set_spawn_randomization(self.ctx, None, 0, self._stream()),
+                       "f110_set_spawn_randomization")
+            return
+        rows = spawn_range_rows(ranges, self.A)
+        sd = (int(self.cfg.seed) if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
+        _lib.check(self.L.f110_set_spawn_randomization(self.ctx, rows, sd, self._stream()),
+                   "f110_set_spawn_randomization")
+
+    def spawn_state(self) -> torch.Tensor:
+        """[4, E*A] f64 (x, y, yaw, speed; SoA like get_state): what each car's last reset under spawn
+        randomization put into its state before the reset's own zero-action step
+        (f110_get_spawn_state)."""
+        out = torch.empty(4, self.E * self.A, dtype=torch.float64, device=self.device)
+        _lib.check(self.L.f110_get_spawn_state(self.ctx, ptr(out), self._stream()), "f110_get_spawn_state")
+        return out
 
     # ---- episode limits (f110_set_episode_limits) -----------------------------
     @staticmethod

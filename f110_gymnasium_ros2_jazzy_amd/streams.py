@@ -225,6 +225,23 @@ class StreamShards:
             with torch.cuda.stream(self.streams[s]):
                 sm.set_param_randomization(ranges, seed=seed)
 
+    def set_spawn_randomization(self, ranges, seed: int | None = None):
+        """BatchSim.set_spawn_randomization on every sub-shard: the draws are keyed by global env id,
+        so the start states are those of one E-env context."""
+        self._fork()
+        for s, sm in enumerate(self.sims):
+            with torch.cuda.stream(self.streams[s]):
+                sm.set_spawn_randomization(ranges, seed=seed)
+
+    def spawn_state(self) -> torch.Tensor:
+        """[4, E*A] f64 start states of all envs (joined; BatchSim.spawn_state)."""
+        parts = []
+        for s, sm in enumerate(self.sims):
+            with torch.cuda.stream(self.streams[s]):
+                parts.append(sm.spawn_state())
+        self.join()
+        return torch.cat(parts, 1)
+
     def set_episode_limits(self, max_steps=None, stall_speed=0.0, stall_steps=None):
         """BatchSim.set_episode_limits on every sub-shard (the limits are per env: the sub-shards'
         flags are those of one E-env context)."""

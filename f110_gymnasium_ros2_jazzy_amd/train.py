@@ -70,6 +70,43 @@ REWARD_KW = dict(w_prog=5.0, alive_bonus=0.5, grace_steps_wall=25, grace_steps_o
                  w_rel_lead=0.0)
 
 
+def add_spawn_args(ap):
+    """The start-state randomization flags (F110VectorEnv's spawn_ranges; none given: off)."""
+    pair = dict(default=None, metavar="LO,HI")
+    ap.add_argument("--spawn-lateral", **pair,
+                    help="start this far left of the spawn pose, in metres (a negative LO: --spawn-lateral=-0.3,0.3)")
+    ap.add_argument("--spawn-heading", help="start turned by this much, in radians", **pair)
+    ap.add_argument("--spawn-speed", help="start rolling at this speed, in m/s", **pair)
+    ap.add_argument("--spawn-gap", help="autoresets: the opponent starts this many spawn rows from the ego's", **pair)
+    ap.add_argument("--spawn-behind", type=float, default=None, metavar="P",
+                    help="--spawn-gap: probability that the opponent starts behind the ego")
+    ap.add_argument("--spawn-clearance", type=float, default=None, metavar="M",
+                    help="--spawn-lateral: least wall distance accepted at the offset position, in metres")
+
+
+def spawn_ranges_from_args(args, num_agents: int = 2, opponent_idx: int = 1):
+    """F110VectorEnv's spawn_ranges from the --spawn-* flags: one dict per agent (lateral, heading,
+    speed and clearance for every car, gap and behind for the opponent only), or None when no flag
+    was given.  ValueError for a LO,HI that is no pair of numbers."""
+    def pair(name, conv):
+        v = getattr(args, name)
+        if v is None:
+            return None
+        try:
+            lo, hi = (conv(x) for x in v.split(","))
+        except ValueError:
+            raise ValueError(f"--{name.replace('_', '-')} takes LO,HI; got {v!r}") from None
+        return lo, hi
+
+    every = {k: pair("spawn_" + k, float) for k in ("lateral", "heading", "speed")}
+    every["clearance"] = args.spawn_clearance
+    opp = {"gap": pair("spawn_gap", int), "behind": args.spawn_behind}
+    every, opp = ({k: v for k, v in d.items() if v is not None} for d in (every, opp))
+    if not every and not opp:
+        return None
+    return [{**every, **opp} if a == opponent_idx else dict(every) for a in range(num_agents)]
+
+
 class _RowStats:
     """The statistics of the rows [lo, hi) of a step's buffers: an episode.EpisodeStats and a
     race.RaceStats built for hi - lo envs (either may be None)."""
@@ -106,7 +143,7 @@ class VectorTrainer:
                  opponent_speed=None, opponent_lookahead: float | None = None, opponent_rule: str = "gap_follow",
                  action_repeat: int = 1, race_stats: bool = False, track_obs: bool = False, track_preview=None,
                  scan_bins: int | None = None, scan_frames: int = 1, scan_stride: int = 1, scan_reduce: str = "min",
-                 scan_keep_poses: bool = True):
+                 scan_keep_poses: bool = True, spawn_ranges=None, spawn_seed: int | None = None):
         # action_repeat and the opponent arguments: ValueError before anything is built
         from .opponent import check_pursuit_speed
         from .replay import check_action_repeat
@@ -180,6 +217,8 @@ class VectorTrainer:
             env_kw["track_obs"] = tobs_kw
         if sobs_kw is not None:  # the learner, the replay and the snapshot see the compact rows
             env_kw["scan_obs"] = sobs_kw
+        if spawn_ranges is not None:  # start states drawn on the device, evaluation envs included (keyed by env id)
+            env_kw.update(spawn_ranges=spawn_ranges, spawn_seed=spawn_seed)
         learner = lambda obs_dim: DDPGLearner(  # noqa: E731
             obs_dim=obs_dim, act_dim=2, action_low=ACTION_LOW, action_high=ACTION_HIGH, gamma=0.99, tau=0.005,
             actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size, alpha=0.6, beta=0.4,
@@ -517,7 +556,12 @@ def main():
                     help="--scan-bins: a sector's value, the minimum (default) or the mean of its ranges")
     ap.add_argument("--scan-drop-poses", action="store_true",
                     help="--scan-bins: drop the map-frame pose columns from the compact observation")
+    add_spawn_args(ap)
     args = ap.parse_args()
+    try:
+        spawn_ranges = spawn_ranges_from_args(args)
+    except ValueError as exc:
+        ap.error(str(exc))
     if args.track_preview is not None and not args.track_obs:
         ap.error("--track-preview needs --track-obs")
     if args.scan_bins is None and (args.scan_frames is not None or args.scan_stride is not None
@@ -541,7 +585,8 @@ def main():
                        track_preview=None if args.track_preview is None else
                        [float(d) for d in args.track_preview.split(",") if d.strip()],
                        scan_bins=args.scan_bins, scan_frames=args.scan_frames or 1, scan_stride=args.scan_stride or 1,
-                       scan_reduce=args.scan_reduce or "min", scan_keep_poses=not args.scan_drop_poses)
+                       scan_reduce=args.scan_reduce or "min", scan_keep_poses=not args.scan_drop_poses,
+                       spawn_ranges=spawn_ranges)
     best = -float("inf")
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)

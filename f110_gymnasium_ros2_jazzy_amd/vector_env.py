@@ -40,6 +40,13 @@ autoreset redraws the resetting cars' friction, mass, ... from the ranges
 (keyed by global env id and episode); ``env.sim.env_params()`` shows the cars
 in force.  The infos are unchanged.
 
+``spawn_ranges`` ({"lateral": (lo, hi), "heading": (lo, hi), "speed": (lo, hi), "gap": (lo, hi),
+"behind": p, "clearance": c}, or one such dict per agent) turns on the device's start-state
+randomization (BatchSim.set_spawn_randomization), keyed by ``spawn_seed``: every reset and autoreset
+starts the resetting cars off the base pose, turned and rolling, and in autoresets an agent with a
+``gap`` that many spawn rows ahead of or behind the env's row; ``env.sim.spawn_state()`` shows the
+drawn starts.  The infos are unchanged.
+
 ``max_episode_steps`` / ``stall_speed`` + ``stall_steps`` put episode limits on
 the device (BatchSim.set_episode_limits): an env that did not terminate is
 truncated after ``max_episode_steps`` steps since its reset (code 1), or when
@@ -103,7 +110,7 @@ import torch
 from ._dev import device_track, f32_rows, first_track
 from .f110_env import DEFAULT_PARAMS, _box
 from .maps import centerline_spawns, load_map
-from .sim import BatchSim, param_range_rows
+from .sim import BatchSim, param_range_rows, spawn_range_rows
 
 
 class F110VectorEnv:
@@ -118,7 +125,8 @@ class F110VectorEnv:
                  stall_speed: float = 0.0, stall_steps: int | None = None, episode_stats: bool = False,
                  opponent_policy=None, opponent_mask=None, opponent_track=None, opponent_params: dict | None = None,
                  opponent_speed=None, opponent_rule: str = "gap_follow", race_stats: bool = False, race_track=None,
-                 race_params: dict | None = None, track_obs=None, obs_track=None, scan_obs=None, **kwargs):
+                 race_params: dict | None = None, track_obs=None, obs_track=None, scan_obs=None, spawn_ranges=None,
+                 spawn_seed: int | None = None, **kwargs):
         self.num_envs = int(num_envs)
         self.num_agents = int(num_agents)
         self.params = dict(params or DEFAULT_PARAMS)
@@ -129,6 +137,8 @@ class F110VectorEnv:
                              opponent_params, opponent_speed, opponent_rule, device)
         if param_ranges is not None:  # an unknown field: ValueError before anything is built
             param_range_rows(param_ranges, [{**DEFAULT_PARAMS, **self.params}] * self.num_agents)
+        if spawn_ranges is not None:  # an unknown name, a value that is no pair: ValueError before anything is built
+            spawn_range_rows(spawn_ranges, self.num_agents)
         # a track observation without a usable centerline: ValueError before anything is built
         obs_track, tobs_params = self._check_track_obs(track_obs, obs_track, reward_fn, opponent_track, race_track,
                                                        device, int(ego_idx), int(opponent_idx))
@@ -151,6 +161,9 @@ class F110VectorEnv:
         # reset and device autoreset redraws the resetting cars' dynamics; sim.env_params() shows them
         if param_ranges is not None:
             self.sim.set_param_randomization(param_ranges, seed=param_seed)
+        # start-state randomization (BatchSim.set_spawn_randomization), on before the first reset
+        if spawn_ranges is not None:
+            self.sim.set_spawn_randomization(spawn_ranges, seed=spawn_seed)
         # episode limits on the device (BatchSim.set_episode_limits), on before the first reset
         self._limits = bool(limits[0] or limits[2])
         if self._limits:

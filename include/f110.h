@@ -215,6 +215,69 @@ F110_API int f110_get_env_params(f110_ctx *ctx, f110_params *out, void *stream);
 F110_API int f110_set_param_randomization(f110_ctx *ctx, const f110_params *lo, const f110_params *hi, uint64_t seed,
                                           void *stream);
 
+/* ---- spawn randomization (no reference counterpart: the reference resets to
+ * the poses its caller passes) ------------------------------------------------
+ * The start state of an episode, drawn on the device where the reset happens:
+ * a lateral offset from the base pose, a heading offset, a start speed and,
+ * for autoresets, the distance to the ego's spawn row along the table.  One
+ * range block per agent: */
+typedef struct {
+    double  lateral[2];   /* m, along the left normal of the table heading            */
+    double  heading[2];   /* rad, added to the table yaw                              */
+    double  speed[2];     /* m/s, the car's state[3] before the reset's own step      */
+    int32_t gap[2];       /* table rows, 0 <= lo <= hi; {0,0}: the agent's own column */
+    double  behind;       /* in [0,1]: probability that the gap is counted backwards  */
+    double  clearance;    /* m, >= 0: least EDT value accepted at the offset position */
+} f110_spawn_range;
+/* From now on a car that resets -- in f110_reset (its masked envs) or by
+ * autoreset inside f110_step / f110_step_n, a captured graph included -- starts
+ * from a drawn state instead of the base pose at rest.
+ * Draw: Philox4x32-10 under f110_set_param_randomization's key (seed, global
+ * env id = env_offset + env), counter (episode lo, episode hi, tag 0x5FA17,
+ * agent * 2 + j): block j = 0 gives, word by word, the gap magnitude, the
+ * behind decision, the lateral offset and the heading offset; word 0 of block
+ * j = 1 the speed.  A real value is lo + u * (hi - lo) with u = r * 2^-32 in
+ * [0, 1) (hi == lo gives exactly lo), the gap magnitude lo + r % (hi - lo + 1),
+ * and the gap counts backwards when u < behind.  episode is 0 for f110_reset
+ * and the finished episode's number + 1 for an autoreset, as for the param
+ * draw: an explicit reset reproduces the same starts whatever ran before it,
+ * and a shard of the envs (env_offset) draws what the whole batch draws for
+ * them.
+ * Base pose: in f110_reset the caller's pose; the gap does not apply there.
+ * In an autoreset, with k the env's spawn row as without the feature, an agent
+ * whose gap is {0,0} takes column `agent` of row k, any other agent column 0
+ * of row (k + mag) mod n_spawn, or (k - mag) mod n_spawn when the gap counts
+ * backwards: the table must then be ordered along the track (the bundled
+ * centerline tables are).
+ * Offset: with (sin, cos) of the base yaw th, x = px + d * (-sin), y = py +
+ * d * cos, yaw = th + dth.  Clearance: d, d/2, d/4, d/8 are tried in that
+ * order and the first whose position reads an EDT value >= clearance is
+ * taken (a position outside the map reads the map's last cell, as every
+ * lookup does); when none does, d = 0, which is always accepted.  Heading and
+ * speed are never adjusted.  Under F110_F32 resets x, y and yaw are rounded to
+ * float32 after the perturbation (start_rot and the lap logic see the rounded,
+ * perturbed pose); the speed stays float64.
+ * Precedence inside a reset: the pose draw, then the param draw
+ * (f110_set_param_randomization), then the reset's own zero-action step, which
+ * starts from (x, y, yaw, speed) with every other state entry 0.
+ * The ranges of two agents are not checked against each other: cars drawn
+ * onto one another collide in the reset's own step, the episode ends there and
+ * the next one draws afresh.
+ * ranges: HOST [n_agents]; NULL turns it off (resets are the base poses at
+ * rest again).  F110_E_INVALID, with the field named in f110_last_error and
+ * before any device call, for a non-finite value, lo > hi, a negative gap,
+ * behind outside [0, 1], a negative clearance, or a non-zero gap on a context
+ * created without a spawn table.  Ordered on `stream`, applied when the call
+ * returns. */
+F110_API int f110_set_spawn_randomization(f110_ctx *ctx, const f110_spawn_range *ranges, uint64_t seed, void *stream);
+/* What each car's last reset under spawn randomization put into its state
+ * before the reset's own zero-action step: out = device [4][n_envs*n_agents]
+ * f64 (x, y, yaw, speed; SoA like f110_get_state).  Rows of cars that have not
+ * reset since the feature came on are 0; resets while it is off leave the rows
+ * as they stand.  F110_E_INVALID on a context that never turned it on.  Async
+ * on `stream`. */
+F110_API int f110_get_spawn_state(f110_ctx *ctx, double *out, void *stream);
+
 /* ---- episode limits (no reference counterpart: the reference steps one env
  * from a Python loop that simply stops; gymnasium's TimeLimit wrapper is a host
  * wrapper, and here the reset happens on the device) --------------------------

@@ -254,6 +254,29 @@ F110_API int f110_host_check_param_ranges(const f110_params *lo, const f110_para
 F110_API int f110_host_param_draw(uint64_t seed, int64_t env, int32_t agent, uint64_t episode, const f110_params *lo,
                                   const f110_params *hi, f110_params *out);
 
+/* f110_set_spawn_randomization's validation of ranges [n_agents] without a
+ * context (n_spawn: the rows of the context's spawn table, 0 = none): F110_OK,
+ * or F110_E_INVALID with the field named in f110_last_error.  Host test hook. */
+F110_API int f110_host_check_spawn_ranges(const f110_spawn_range *ranges, int32_t n_agents, int32_t n_spawn);
+/* The start states n resetting envs draw (the device's row rule,
+ * csrc/f110_spawn.h, on the host): out [n][n_agents][4] = (x, y, yaw, speed)
+ * of every car of env envs[i] in episode episodes[i] (NULL: 0) under (ranges,
+ * seed), over the HOST EDT edt [H*W] in metres (row-major, the MapView layout)
+ * with the map's resolution and origin.
+ * poses != NULL: f110_reset -- the base poses are poses [n][n_agents][3] and
+ * the gap does not apply.  poses == NULL: an autoreset from spawn
+ * [n_spawn][n_agents][3] -- the env's row k is rows[i] when rows != NULL, else
+ * the context's draw under ctx_seed for the finished episode episodes[i] - 1.
+ * reset_f32: the poses rounded as under F110_F32 resets.  rows_out
+ * [n][n_agents] (or NULL): the table row each car's base pose came from (-1
+ * with poses).  Same validation as f110_set_spawn_randomization.  Host test
+ * hook: the CPU suite and the GPU tests share one statement of the semantics. */
+F110_API int f110_host_spawn_rows(const f110_spawn_range *ranges, int32_t n_agents, uint64_t seed, uint64_t ctx_seed,
+                                  const double *edt, int32_t H, int32_t W, double resolution, const double origin[3],
+                                  const double *spawn, int32_t n_spawn, const double *poses, const int32_t *rows,
+                                  const int64_t *envs, const uint64_t *episodes, int64_t n, int32_t reset_f32,
+                                  double *out, int32_t *rows_out);
+
 /* f110_set_episode_limits' validation without a context: F110_OK, or
  * F110_E_INVALID with the argument named in f110_last_error (negative
  * max_steps / stall_steps, negative or non-finite stall_speed).  Host test hook. */

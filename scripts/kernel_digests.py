@@ -12,6 +12,13 @@ With two file lists (separated by --) the kernels whose lines differ are printed
 
 The second form, over a checkout of the parent commit and this tree, is the proof that a change of
 the headers alone (moving text between csrc/*.h, changing includes) left every kernel as it was.
+
+--layout-free (first argument) hashes the instruction text instead of the encodings, with the
+literal of every `s_add_u32 sN, sN, 0x...` masked: those are the pc-relative address computations
+(s_getpc_b64 + offset of a constant table or an out-of-line function), which move with the file's
+layout -- a kernel added to the file, a longer mangled name -- while the kernel's code does not.
+
+    python scripts/kernel_digests.py --layout-free parent/csrc/f110_agents.hip -- csrc/f110_agents.hip
 """
 import hashlib
 import os
@@ -31,6 +38,9 @@ def llvm(tool):
     return os.path.join(os.path.dirname(os.path.dirname(_build.hipcc())), "llvm", "bin", tool)
 
 
+LAYOUT_FREE = False
+
+
 def digests(path, tmp):
     """(kernels {name: line}, device functions [line]) of one .hip file's code object."""
     co = os.path.join(tmp, os.path.basename(path) + ".co")
@@ -43,7 +53,11 @@ def digests(path, tmp):
             sym = head.group(1)
             code[sym] = hashlib.sha256()
         elif sym and "//" in ln:  # "\tinstruction // address: encoding words"
-            code[sym].update(ln.split("//")[1].split(":", 1)[1].strip().encode())
+            if LAYOUT_FREE:
+                text = re.sub(r"(s_add_u32 s\d+, s\d+, )0x[0-9a-f]+", r"\1<pcrel>", ln.split("//")[0].strip())
+                code[sym].update(text.encode() + b"\n")
+            else:
+                code[sym].update(ln.split("//")[1].split(":", 1)[1].strip().encode())
     records = []  # amdhsa.kernels: "  - .key: value" opens a kernel's record, "    .key: value" continues it
     for ln in subprocess.check_output([llvm("llvm-readelf"), "--notes", co], text=True).splitlines():
         kv = re.match(r"  ([- ]) \.(\w+):\s*(\S*)\s*$", ln)
@@ -68,6 +82,9 @@ def side(files, tmp):
 
 
 def main(argv):
+    global LAYOUT_FREE
+    if argv and argv[0] == "--layout-free":
+        LAYOUT_FREE, argv = True, argv[1:]
     cut = argv.index("--") if "--" in argv else len(argv)
     with tempfile.TemporaryDirectory() as tmp:
         a, fa = side(argv[:cut], tmp)
