@@ -14,7 +14,7 @@ REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libf110.so")
 SOURCES = ["f110_agents.hip", "f110_rays_tiled.hip", "f110_rays_fx.hip", "f110_rays_fxs.hip", "f110_post.hip", "f110_step.cpp",
-           "f110_batch.hip", "f110_opponent.hip", "f110_reward.hip", "f110_pursuit.hip", "f110_race.hip", "f110_track_obs.hip", "f110_scan_obs.hip", "f110_episode.hip", "f110_replay.hip", "f110_adam.hip", "f110_ddpg.hip", "f110_td3.hip", "f110_selfplay.hip", "f110_gemm.hip",
+           "f110_batch.hip", "f110_opponent.hip", "f110_reward.hip", "f110_pursuit.hip", "f110_race.hip", "f110_track_obs.hip", "f110_scan_obs.hip", "f110_sensor.hip", "f110_episode.hip", "f110_replay.hip", "f110_adam.hip", "f110_ddpg.hip", "f110_td3.hip", "f110_selfplay.hip", "f110_gemm.hip",
            "f110_host.cpp", "f110_ctx.cpp", "f110_ctx_debug.cpp", "f110_task_capi.cpp",
            "f110_replay_capi.cpp"]
 ARCH = os.environ.get("F110_OFFLOAD_ARCH", "gfx950")

@@ -108,6 +108,11 @@ class F110SpawnRange(ctypes.Structure):  # f110_spawn_range (zero bytes = the ag
                 ("gap", ctypes.c_int32 * 2), ("behind", ctypes.c_double), ("clearance", ctypes.c_double)]
 
 
+class F110SensorParams(ctypes.Structure):  # f110_sensor_params: (lo, hi) each; the defaults are the identity
+    _fields_ = [(n, ctypes.c_float * 2) for n in ("scale", "noise_abs", "noise_rel", "dropout", "blackout", "quant",
+                                                 "pose_xy", "pose_theta")]
+
+
 class F110RayKnobs(ctypes.Structure):  # f110_ray_knobs (include/f110_debug.h)
     _fields_ = [(n, ctypes.c_int32) for n in
                 ("kernel", "lanes", "refill", "fxs_lds", "count_slots", "wtrace", "heavy_list", "heavy_on",
@@ -148,6 +153,7 @@ _i, _i32, _i64, _u64 = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_ui
 _f32, _f64 = ctypes.c_float, ctypes.c_double
 _PP = ctypes.POINTER(F110Params)
 _SR = ctypes.POINTER(F110SpawnRange)
+_SP = ctypes.POINTER(F110SensorParams)
 _OUT = ctypes.POINTER(F110Outputs)
 _PTRS6 = [ctypes.POINTER(_P)] * 6
 _EXPLORE = [_P] * 5 + [_i32] * 3 + [_P, _P, _f64, _f64, _P, _P, _u64, _P, _i64]  # f110_ddpg_actor_explore less its stream
@@ -305,6 +311,15 @@ _API = {
     "f110_scan_obs_arrays": (_i, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P)]),
     "f110_host_scan_obs_push": (_i, [ctypes.POINTER(F110ScanObsParams), _i64, _i32, _i32, _i32, _P, _i64, _P, _P, _P, _P,
                                      _i64]),
+    "f110_default_sensor_params": (None, [_SP]),
+    "f110_sensor_create": (_i, [ctypes.POINTER(_P), _i32, _i64, _i32, _i32, _i32, _f32, _u64, _i64, _P, _SP]),
+    "f110_sensor_destroy": (_i, [_P]),
+    "f110_sensor_apply": (_i, [_P, _P, _i64, _P, _P, _i64, _P]),
+    "f110_sensor_reset": (_i, [_P, _P, _P]),
+    "f110_sensor_arrays": (_i, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P)]),
+    "f110_host_check_sensor_params": (_i, [_SP, _i32]),
+    "f110_host_sensor_apply": (_i, [_SP, _i64, _i32, _i32, _i32, _f32, _u64, _i64, _P, _P, _i64, _P, _P, _P, _P, _P,
+                                    _i64]),
 }
 EXPORTS = list(_API)
 

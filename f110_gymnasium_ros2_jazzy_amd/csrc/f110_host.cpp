@@ -3,8 +3,8 @@
 // (Felzenszwalb-Huttenlocher lower envelopes, integer arithmetic) and the tables built from it,
 // the beam-index and sin/cos test hooks, the ray-launch decision (ray_rules, plan_ray_launch), the
 // argument checks of the params / episode / n-step entry points and their host models, the
-// derivation of a track's arrays, and the host statements of the scan observation and the spawn
-// randomization.  It links on its own (tests/host_check runs it under ASan / UBSan).
+// derivation of a track's arrays, and the host statements of the scan observation, the spawn
+// randomization and the sensor randomization.  It links on its own (tests/host_check runs it under ASan / UBSan).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -23,6 +23,7 @@
 #include "f110_map.h"
 #include "f110_math.h"
 #include "f110_scan_obs.h"
+#include "f110_sensor.h"
 #include "f110_sincos.h"
 #include "f110_spawn.h"
 #include "f110_step_args.h"
@@ -967,6 +968,59 @@ extern "C" int f110_host_scan_obs_push(const f110_scan_obs_params *params, int64
         }
         const float *src = row + B + (P.keep_mid ? 0 : n_mid);
         std::copy(src, src + n_copy, o + (size_t)F * K);
+    }
+    return F110_OK;
+}
+
+// ---- sensor randomization (f110_sensor.hip; the row rule: f110_sensor.h) ----------------------
+extern "C" void f110_default_sensor_params(f110_sensor_params *p) {
+    if (!p) return;
+    *p = f110_sensor_params{};  // every sigma, dropout, blackout and quant (0, 0)
+    p->scale[0] = p->scale[1] = 1.0f;
+}
+
+extern "C" int f110_host_check_sensor_params(const f110_sensor_params *params, int32_t n_beams) {
+    const char *bad = n_beams < 1 || n_beams > kSensorMaxBeams ? "n_beams must be in [1, 4096]"
+                                                               : sensor_bad_params(params, n_beams);
+    if (bad) return fail(F110_E_INVALID, std::string("f110_host_check_sensor_params: ") + bad);
+    return F110_OK;
+}
+
+extern "C" int f110_host_sensor_apply(const f110_sensor_params *params, int64_t n_envs, int32_t n_beams,
+                                      int32_t n_mid, int32_t n_tail, float range_max, uint64_t seed,
+                                      int64_t env_offset, const uint8_t *env_mask, const float *rows,
+                                      int64_t row_stride, const uint8_t *reset, float *param_rows, int32_t *episode,
+                                      int32_t *step, float *out, int64_t out_stride) {
+    const char *bad = sensor_bad_shape(params, n_envs, n_beams, n_mid, n_tail, range_max, env_offset);
+    if (!bad && (!param_rows || !episode || !step)) bad = "null param_rows, episode or step";
+    if (!bad) bad = sensor_bad_apply(n_envs, n_beams + n_mid + n_tail, rows, row_stride, out, out_stride);
+    if (bad) return fail(F110_E_INVALID, std::string("f110_host_sensor_apply: ") + bad);
+    for (int64_t e = 0; e < n_envs; ++e)
+        if (episode[e] < -1) return fail(F110_E_INVALID, "f110_host_sensor_apply: an episode counter below -1");
+    const int32_t B = n_beams, M = n_mid, W = n_beams + n_mid + n_tail;
+    for (int64_t e = 0; e < n_envs; ++e) {
+        const bool start = sensor_advance(episode[e], step[e], reset ? reset[e] : 0);
+        const SensorKey key = sensor_key(seed, (uint64_t)(env_offset + e));
+        SensorRow *held = reinterpret_cast<SensorRow *>(param_rows) + e;
+        if (start) *held = sensor_draw_row(key, (uint32_t)episode[e], *params, B, range_max);
+        const SensorRow r = *held;
+        const float *row = rows + e * row_stride;
+        float *o = out + e * out_stride;
+        if (env_mask && !env_mask[e]) {
+            if (o != row) std::copy(row, row + W, o);
+            continue;
+        }
+        const uint32_t ep = (uint32_t)episode[e], st = (uint32_t)step[e];
+        const bool draws = sensor_beam_draws(r);
+        for (int32_t b = 0; b < B; ++b) {
+            const U4 k = draws ? sensor_block(key, ep, st, (uint32_t)b) : U4{0u, 0u, 0u, 0u};
+            o[b] = sensor_beam(row[b], b, r, k);
+        }
+        for (int32_t m = 0; m < M; ++m) {
+            const U4 k = sensor_pose_draws(r, m) ? sensor_block(key, ep, st, (uint32_t)(B + m)) : U4{0u, 0u, 0u, 0u};
+            o[B + m] = sensor_pose(row[B + m], m, r, k);
+        }
+        if (o != row) std::copy(row + B + M, row + W, o + B + M);
     }
     return F110_OK;
 }

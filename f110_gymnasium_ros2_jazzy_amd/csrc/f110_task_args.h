@@ -1,6 +1,6 @@
 // f110_task_args.h — the argument blocks and launchers of the kernels beside the env step: the
 // C-ABI batch kernels, gap-follow, the track, the reward and the pure-pursuit opponent, the episode
-// and the race statistics, the track observation, the scan observation.
+// and the race statistics, the track observation, the scan observation, the sensor randomization.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -140,6 +140,24 @@ struct ScanObsArgs {
 };
 hipError_t launch_scan_obs(const ScanObsArgs &a, hipStream_t s);
 hipError_t launch_scan_obs_reset(int32_t *head, const uint8_t *env_mask, int64_t E, hipStream_t s);
+
+// ---- sensor randomization (f110_sensor.hip; the row rule: f110_sensor.h) ----------------------
+struct SensorArgs {
+    const float *rows;       // row e at rows + e * row_stride: [B | M | T]
+    const uint8_t *reset;    // [E] or null
+    const uint8_t *mask;     // [E] or null (every env): rows with 0 are copied through
+    float *param_rows;       // [E][10] the drawn parameters (SensorRow)
+    int32_t *episode;        // [E], -1 = no apply yet
+    int32_t *step;           // [E] applies since the episode's start
+    float *out;              // row e at out + e * out_stride; may be rows itself
+    int64_t E, row_stride, out_stride, env_offset;
+    uint64_t seed;
+    f110_sensor_params p;
+    float range_max;
+    int32_t B, M, T;
+};
+hipError_t launch_sensor(const SensorArgs &a, hipStream_t s);
+hipError_t launch_sensor_reset(int32_t *episode, int32_t *step, const uint8_t *env_mask, int64_t E, hipStream_t s);
 
 // ---- the C-ABI batch kernels (f110_batch.hip) and the task kernels ----------------------------
 hipError_t launch_scan_batch(const ScanArgs &a, hipStream_t s);

@@ -2,9 +2,10 @@
 // progress reward (f110_track_*), f110_reward, f110_gap_follow, f110_pure_pursuit with its host
 // statement, the race statistics with theirs, the track observation with its own (and its entry on
 // a context's live state, which needs both the track's and the context's internals), the scan
-// observation's handle, the collision batches and the episode statistics.  Argument checks and
-// launches; the kernels are in f110_reward.hip, f110_opponent.hip, f110_pursuit.hip, f110_race.hip,
-// f110_track_obs.hip, f110_scan_obs.hip, f110_batch.hip and f110_episode.hip.
+// observation's handle, the sensor randomization's handle, the collision batches and the episode
+// statistics.  Argument checks and launches; the kernels are in f110_reward.hip, f110_opponent.hip,
+// f110_pursuit.hip, f110_race.hip, f110_track_obs.hip, f110_scan_obs.hip, f110_sensor.hip,
+// f110_batch.hip and f110_episode.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +22,7 @@
 #include "f110_host_util.h"
 #include "f110_pursuit.h"
 #include "f110_scan_obs.h"
+#include "f110_sensor.h"
 #include "f110_step_args.h"
 #include "f110_task_args.h"
 #include "f110_track_obs.h"
@@ -564,6 +566,87 @@ extern "C" int f110_scan_obs_arrays(f110_scan_obs *so, float **ring, int32_t **h
     if (!so) return fail(F110_E_INVALID, "f110_scan_obs_arrays: null handle");
     if (ring) *ring = so->a.ring;
     if (head) *head = so->a.head;
+    return F110_OK;
+}
+
+// ---- sensor randomization (f110_sensor.hip; the row rule: f110_sensor.h) ----------------------
+// (f110_default_sensor_params and the host statement: f110_host.cpp)
+struct f110_sensor {
+    DeviceArena arena;
+    SensorArgs a{};  // the shape, the seed, the ranges, the mask, the parameter rows and the counters
+};
+
+extern "C" int f110_sensor_create(f110_sensor **out, int32_t device, int64_t n_envs, int32_t n_beams, int32_t n_mid,
+                                  int32_t n_tail, float range_max, uint64_t seed, int64_t env_offset,
+                                  const uint8_t *env_mask, const f110_sensor_params *params) {
+    const char *bad = !out ? "null out"
+                           : sensor_bad_shape(params, n_envs, n_beams, n_mid, n_tail, range_max, env_offset);
+    if (bad) return fail(F110_E_INVALID, std::string("f110_sensor_create: ") + bad);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
+        return fail(F110_E_NODEVICE, "f110_sensor_create: no such HIP device");
+    if (hipSetDevice(device) != hipSuccess) return fail(F110_E_NODEVICE, "f110_sensor_create: hipSetDevice");
+    auto *sn = new f110_sensor();
+    sn->arena.device = device;
+    SensorArgs &a = sn->a;
+    a.E = n_envs;
+    a.B = n_beams;
+    a.M = n_mid;
+    a.T = n_tail;
+    a.range_max = range_max;
+    a.seed = seed;
+    a.env_offset = env_offset;
+    a.p = *params;
+    const size_t N = (size_t)n_envs;
+    hipError_t e = sn->arena.alloc(&a.param_rows, N * kSensorRowFloats, /*zero=*/true);
+    if (e == hipSuccess) e = sn->arena.alloc(&a.step, N, /*zero=*/true);
+    if (e == hipSuccess) e = sn->arena.alloc(&a.episode, N, /*zero=*/false);
+    if (e == hipSuccess) e = hipMemset(a.episode, 0xff, N * sizeof(int32_t));  // every episode -1: no apply yet
+    if (e == hipSuccess && env_mask) e = sn->arena.upload(&a.mask, env_mask, N);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        delete sn;  // (the arena frees what was allocated)
+        return hip_fail("f110_sensor_create", e, F110_E_ALLOC);
+    }
+    *out = sn;
+    return F110_OK;
+}
+
+extern "C" int f110_sensor_destroy(f110_sensor *sn) {
+    delete sn;
+    return F110_OK;
+}
+
+extern "C" int f110_sensor_apply(f110_sensor *sn, const float *rows, int64_t row_stride, const uint8_t *reset,
+                                 float *out, int64_t out_stride, void *stream) {
+    if (!sn) return fail(F110_E_INVALID, "f110_sensor_apply: null handle");
+    SensorArgs a = sn->a;
+    const char *bad = sensor_bad_apply(a.E, a.B + a.M + a.T, rows, row_stride, out, out_stride);
+    if (bad) return fail(F110_E_INVALID, std::string("f110_sensor_apply: ") + bad);
+    if (hipSetDevice(sn->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_sensor_apply: hipSetDevice");
+    a.rows = rows;
+    a.row_stride = row_stride;
+    a.reset = reset;
+    a.out = out;
+    a.out_stride = out_stride;
+    hipError_t e = launch_sensor(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail("f110_sensor_apply", e);
+    return F110_OK;
+}
+
+extern "C" int f110_sensor_reset(f110_sensor *sn, const uint8_t *env_mask, void *stream) {
+    if (!sn) return fail(F110_E_INVALID, "f110_sensor_reset: null handle");
+    if (hipSetDevice(sn->arena.device) != hipSuccess) return fail(F110_E_HIP, "f110_sensor_reset: hipSetDevice");
+    hipError_t e = launch_sensor_reset(sn->a.episode, sn->a.step, env_mask, sn->a.E, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail("f110_sensor_reset", e);
+    return F110_OK;
+}
+
+extern "C" int f110_sensor_arrays(f110_sensor *sn, float **param_rows, int32_t **episode, int32_t **step) {
+    if (!sn) return fail(F110_E_INVALID, "f110_sensor_arrays: null handle");
+    if (param_rows) *param_rows = sn->a.param_rows;
+    if (episode) *episode = sn->a.episode;
+    if (step) *step = sn->a.step;
     return F110_OK;
 }
 

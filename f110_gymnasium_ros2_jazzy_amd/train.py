@@ -31,6 +31,13 @@ Per vector step, everything on the device:
                 mean), the last --scan-frames pooled frames stacked --scan-stride steps apart, the pose
                 columns kept (or dropped: --scan-drop-poses), the track block after them; the reward,
                 the opponents and the statistics keep reading the full rows
+                with --sensor-noise / --sensor-noise-rel / --sensor-scale / --sensor-dropout /
+                --sensor-blackout / --sensor-quant / --sensor-pose-xy / --sensor-pose-theta LO,HI (no
+                reference counterpart) the rows the policy, the critic and the replay see come through a
+                randomized sensor (sensor.SensorModel, one more launch inside the step graphs, before the
+                scan observation): each parameter is redrawn per env and episode on the device; the
+                --eval-envs rows are masked out and stay noise-free, and the reward, the opponents, the
+                statistics and a self-play snapshot keep reading the clean rows
   reward        CenterlineSafetyProgressReward (:127-146, :179) on the device
   race          with --race-stats (no reference counterpart) the race outcomes per episode on the
                 reward's centerline: progress, lead over the opponent, passes, crash / completed /
@@ -107,6 +114,39 @@ def spawn_ranges_from_args(args, num_agents: int = 2, opponent_idx: int = 1):
     return [{**every, **opp} if a == opponent_idx else dict(every) for a in range(num_agents)]
 
 
+SENSOR_FLAGS = (("noise", "noise_abs", "additive range noise sigma, in metres"),
+                ("noise_rel", "noise_rel", "range-proportional noise sigma, a fraction of the range"),
+                ("scale", "scale", "multiplicative range error (1 = exact)"),
+                ("dropout", "dropout", "per-beam, per-step probability of no return (the beam reads max range)"),
+                ("blackout", "blackout", "width in beams of one blocked sector per episode (it reads 0)"),
+                ("quant", "quant", "range quantization step, in metres (0: off)"),
+                ("pose_xy", "pose_xy", "sigma of the noise on the x and y columns, in metres"),
+                ("pose_theta", "pose_theta", "sigma of the noise on the theta columns, in radians"))
+
+
+def add_sensor_args(ap):
+    """The sensor randomization flags (F110VectorEnv's sensor_ranges; none given: off): each
+    parameter is drawn per env and episode, uniform in LO,HI."""
+    for flag, _, text in SENSOR_FLAGS:
+        ap.add_argument("--sensor-" + flag.replace("_", "-"), default=None, metavar="LO,HI", help="sensor: " + text)
+
+
+def sensor_ranges_from_args(args):
+    """F110VectorEnv's sensor_ranges from the --sensor-* flags, or None when no flag was given.
+    ValueError for a LO,HI that is no pair of numbers."""
+    ranges = {}
+    for flag, name, _ in SENSOR_FLAGS:
+        v = getattr(args, "sensor_" + flag)
+        if v is None:
+            continue
+        try:
+            lo, hi = (float(x) for x in v.split(","))
+        except ValueError:
+            raise ValueError(f"--sensor-{flag.replace('_', '-')} takes LO,HI; got {v!r}") from None
+        ranges[name] = (lo, hi)
+    return ranges or None
+
+
 class _RowStats:
     """The statistics of the rows [lo, hi) of a step's buffers: an episode.EpisodeStats and a
     race.RaceStats built for hi - lo envs (either may be None)."""
@@ -143,7 +183,8 @@ class VectorTrainer:
                  opponent_speed=None, opponent_lookahead: float | None = None, opponent_rule: str = "gap_follow",
                  action_repeat: int = 1, race_stats: bool = False, track_obs: bool = False, track_preview=None,
                  scan_bins: int | None = None, scan_frames: int = 1, scan_stride: int = 1, scan_reduce: str = "min",
-                 scan_keep_poses: bool = True, spawn_ranges=None, spawn_seed: int | None = None):
+                 scan_keep_poses: bool = True, spawn_ranges=None, spawn_seed: int | None = None, sensor_ranges=None,
+                 sensor_seed: int | None = None):
         # action_repeat and the opponent arguments: ValueError before anything is built
         from .opponent import check_pursuit_speed
         from .replay import check_action_repeat
@@ -178,6 +219,13 @@ class VectorTrainer:
             sobs_kw = dict(n_bins=scan_bins, n_frames=scan_frames, stride=scan_stride, reduce=scan_reduce,
                            keep_mid=bool(scan_keep_poses))
             scan_obs_params(_lib.default_config().n_beams, **sobs_kw)  # a value out of range: ValueError
+        if sensor_ranges is not None:  # an unknown name, a value out of range: ValueError
+            from . import _lib, sensor
+            if not isinstance(sensor_ranges, dict):
+                raise ValueError("sensor_ranges must be None or a dict {name: (lo, hi)}")
+            sensor.sensor_ranges(_lib.default_config().n_beams, **sensor_ranges)
+        elif sensor_seed is not None:
+            raise ValueError("sensor_seed needs sensor_ranges")
         self.selfplay = opponent == "self"
         self.selfplay_sync, self.selfplay_fraction = int(selfplay_sync), float(selfplay_fraction)
         if self.selfplay:
@@ -219,6 +267,11 @@ class VectorTrainer:
             env_kw["scan_obs"] = sobs_kw
         if spawn_ranges is not None:  # start states drawn on the device, evaluation envs included (keyed by env id)
             env_kw.update(spawn_ranges=spawn_ranges, spawn_seed=spawn_seed)
+        if sensor_ranges is not None:  # the learner and the replay see the rows through the sensor; the evaluation
+            # envs (the last eval_envs rows) are masked out and stay noise-free; a snapshot sees clean rows
+            mask = np.ones(self.N, np.uint8)
+            mask[self.N - self.eval_envs:] = 0
+            env_kw.update(sensor_ranges=sensor_ranges, sensor_seed=sensor_seed, sensor_mask=mask)
         learner = lambda obs_dim: DDPGLearner(  # noqa: E731
             obs_dim=obs_dim, act_dim=2, action_low=ACTION_LOW, action_high=ACTION_HIGH, gamma=0.99, tau=0.005,
             actor_lr=1e-4, critic_lr=1e-3, memory_size=memory_size, batch_size=batch_size, alpha=0.6, beta=0.4,
@@ -557,9 +610,11 @@ def main():
     ap.add_argument("--scan-drop-poses", action="store_true",
                     help="--scan-bins: drop the map-frame pose columns from the compact observation")
     add_spawn_args(ap)
+    add_sensor_args(ap)
     args = ap.parse_args()
     try:
         spawn_ranges = spawn_ranges_from_args(args)
+        sensor_ranges = sensor_ranges_from_args(args)
     except ValueError as exc:
         ap.error(str(exc))
     if args.track_preview is not None and not args.track_obs:
@@ -586,7 +641,7 @@ def main():
                        [float(d) for d in args.track_preview.split(",") if d.strip()],
                        scan_bins=args.scan_bins, scan_frames=args.scan_frames or 1, scan_stride=args.scan_stride or 1,
                        scan_reduce=args.scan_reduce or "min", scan_keep_poses=not args.scan_drop_poses,
-                       spawn_ranges=spawn_ranges)
+                       spawn_ranges=spawn_ranges, sensor_ranges=sensor_ranges)
     best = -float("inf")
     t0 = time.perf_counter()
     ret = torch.zeros(shard.count, device=tr.device, dtype=torch.float64)

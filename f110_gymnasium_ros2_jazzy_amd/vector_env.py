@@ -98,6 +98,18 @@ step.  ``reset()`` empties the ring; a ``was_reset`` row (a NEXT_STEP autoreset:
 first frame) refills its ring, so all of its stacked frames are that frame.  Off (the default)
 nothing differs.
 
+``sensor_ranges`` ({"scale" | "noise_abs" | "noise_rel" | "dropout" | "blackout" | "quant" | "pose_xy" |
+"pose_theta": (lo, hi)}, see sensor.sensor_ranges) turns on the device's sensor randomization
+(sensor.SensorModel), keyed by ``sensor_seed`` and the global env id: every reset and autoreset
+redraws the env's sensor parameters, and one more launch per step and reset turns the full rows
+into the rows ``step``, ``reset`` and ``step_transition`` return -- the ranges scaled, noised,
+quantized, dropped and blacked out, the pose columns noised.  The stage runs after the opponents,
+the reward and the statistics have read the clean rows (``full_obs`` stays clean) and before the
+scan observation, which then pools the corrupted rows.  ``sensor_mask`` (uint8 [N]): the envs the
+stage touches; an env with 0 gets its clean row (a trainer's evaluation envs).
+``sensor_params()`` shows the drawn rows.  A self-play snapshot (PolicyOpponent) keeps seeing clean
+rows from its own seat.  Off (the default) nothing differs.
+
 Multi-GPU: give each rank its block of envs (distributed.shard_range) and
 ``env_offset`` = the block's first global id; RNG streams are keyed by global
 env id, so results do not depend on the GPU count.
@@ -126,10 +138,14 @@ class F110VectorEnv:
                  opponent_policy=None, opponent_mask=None, opponent_track=None, opponent_params: dict | None = None,
                  opponent_speed=None, opponent_rule: str = "gap_follow", race_stats: bool = False, race_track=None,
                  race_params: dict | None = None, track_obs=None, obs_track=None, scan_obs=None, spawn_ranges=None,
-                 spawn_seed: int | None = None, **kwargs):
+                 spawn_seed: int | None = None, sensor_ranges=None, sensor_seed: int | None = None, sensor_mask=None,
+                 **kwargs):
         self.num_envs = int(num_envs)
         self.num_agents = int(num_agents)
         self.params = dict(params or DEFAULT_PARAMS)
+        # a bad sensor range or mask: ValueError before anything is built
+        sens_params = self._check_sensor(sensor_ranges, sensor_seed, sensor_mask, int(kwargs.get("num_beams", 1080)),
+                                         env_offset)
         # a bad scan-observation parameter: ValueError before anything is built
         sobs_params = self._check_scan_obs(scan_obs, int(kwargs.get("num_beams", 1080)))
         # a bad opponent argument: ValueError before anything is built
@@ -199,6 +215,20 @@ class F110VectorEnv:
             self._wide = torch.zeros(self.num_envs, self._head + self._tobs.width, dtype=torch.float32,
                                      device=self.device)
             obs_low, obs_high = np.concatenate([obs_low, self._tobs.low]), np.concatenate([obs_high, self._tobs.high])
+        # the sensor randomization: every stage keeps reading the clean full rows in the env's own
+        # buffer (the one above, or one of B + 4A columns); one more launch per step and reset makes
+        # the rows seen through the sensor, in a buffer of its own or, when nothing follows, obs_out
+        self._sensor = self._noisy = None
+        if sens_params is not None:
+            from .sensor import SensorModel
+            self._head = B + 4 * A
+            if self._wide is None:
+                self._wide = torch.zeros(self.num_envs, self._head, dtype=torch.float32, device=self.device)
+            lidar_max = float({**DEFAULT_PARAMS, **self.params}["lidar_max"])
+            self._sensor = SensorModel(self.num_envs, B, 4 * A, self._wide.shape[1] - self._head, range_max=lidar_max,
+                                       seed=int(self.sim.cfg.seed) if sensor_seed is None else int(sensor_seed),
+                                       env_offset=env_offset, mask=sensor_mask, device=self.device, **sens_params)
+            self._noisy = torch.zeros_like(self._wide)
         # the scan observation: every stage keeps reading the full rows in the env's own buffer (the
         # one above, or one of B + 4A columns); one more launch per step and reset makes the compact
         # rows the caller gets back
@@ -341,6 +371,30 @@ class F110VectorEnv:
         scan_obs_params(n_beams, **params)  # unknown names, values out of range: ValueError
         return params
 
+    def _check_sensor(self, ranges, seed, mask, n_beams, env_offset):
+        """The sensor-randomization arguments (host values only): the range dict, or None when off."""
+        if ranges is None:
+            if seed is not None or mask is not None:
+                raise ValueError("sensor_seed and sensor_mask need sensor_ranges")
+            return None
+        if not isinstance(ranges, dict):
+            raise ValueError("sensor_ranges must be None or a dict {name: (lo, hi)} of sensor.sensor_ranges names")
+        from .sensor import _mask, sensor_ranges
+        if not 1 <= n_beams <= 4096:
+            raise ValueError(f"sensor_ranges: num_beams must be in [1, 4096]; got {n_beams}")
+        sensor_ranges(n_beams, **ranges)  # unknown names, values out of range: ValueError
+        _mask(mask, self.num_envs)
+        if int(env_offset) < 0:
+            raise ValueError("sensor_ranges: env_offset must be >= 0")
+        return dict(ranges)
+
+    def sensor_params(self):
+        """The sensor parameters in force, as sim.env_params() shows the cars: float32 [N, 10] on the
+        device, one row per env (sensor.PARAM_ROW names the columns).  ValueError with the stage off."""
+        if self._sensor is None:
+            raise ValueError("sensor_params: build the env with sensor_ranges")
+        return self._sensor.arrays()["params"]
+
     def _check_race(self, race_stats, track, params, reward_fn, opponent_track, device, ego_idx, opponent_idx):
         """The race-statistics arguments (host values only): the centerline to use, or None when off."""
         if not race_stats:
@@ -445,6 +499,9 @@ class F110VectorEnv:
         if self._race is not None:
             self._race.reset()
             self._race.begin(src)
+        if self._sensor is not None:  # the counters start over: episode 0 of every env, its parameters redrawn
+            self._sensor.reset()
+            src = self._sensor.apply(src, out=self._noisy)
         if self._sobs is not None:  # an empty ring: every stacked frame is the reset's
             self._sobs.reset()
             src = self._sobs.push(src, out=self._compact)
@@ -488,10 +545,11 @@ class F110VectorEnv:
     def _advance(self, a, obs_out=None):
         """One step of every stage, in order: the simulator (into obs_out, if given), the track
         observation's tail, the next opponent action, the reward, the episode and race statistics,
-        the scan observation's compact rows.  Returns (out, obs, rewards): the simulator's outputs,
-        the rows the caller gets (what every stage read: the simulator's own, the env's wide buffer,
-        or obs_out; with scan_obs on the compact rows made from them, in the env's compact buffer
-        or obs_out) and the reward's own buffer."""
+        the sensor randomization's rows, the scan observation's compact rows.  Returns (out, obs,
+        rewards): the simulator's outputs, the rows the caller gets (what every stage read: the
+        simulator's own, the env's wide buffer, or obs_out; with sensor_ranges on those rows seen
+        through the sensor, in the stage's own buffer or obs_out; with scan_obs on the compact rows
+        made from them, in the env's compact buffer or obs_out) and the reward's own buffer."""
         if self._wide is None:
             out = self.sim.step(a, obs_out=obs_out)  # the simulator writes obs_out itself (no copy)
             obs = out.obs if obs_out is None else obs_out
@@ -499,7 +557,7 @@ class F110VectorEnv:
             obs = self._wide
             if obs_out is not None:  # (checked before the simulator moves)
                 obs_out = f32_rows(obs_out, self.num_envs, self.obs_dim, self.device, "obs_out", copy_ok=False)[0]
-                if self._sobs is None:
+                if self._sobs is None and self._sensor is None:
                     obs = obs_out
             out = self.sim.step(a, obs_out=obs[:, :self._head])
             self._fill_wide(wide=obs)
@@ -514,6 +572,9 @@ class F110VectorEnv:
             self._episode.update(rewards, out.terminated, out.truncated, out.was_reset)
         if self._race is not None:
             self._race.update(obs, out.terminated, out.truncated, out.was_reset)
+        if self._sensor is not None:  # the rows seen through the sensor; a reset row starts its env's next episode
+            last = self._sobs is None and obs_out is not None  # nothing follows: straight into obs_out
+            obs = self._sensor.apply(obs, reset=out.was_reset, out=obs_out if last else self._noisy)
         if self._sobs is not None:  # the compact rows of the full ones; a reset row refills its ring
             obs = self._sobs.push(obs, reset=out.was_reset, out=self._compact if obs_out is None else obs_out)
         return out, obs, rewards
@@ -590,6 +651,9 @@ class F110VectorEnv:
         self._race.reset_totals()
 
     def close(self):
+        if getattr(self, "_sensor", None) is not None:
+            self._sensor.close()
+            self._sensor = None
         if getattr(self, "_sobs", None) is not None:
             self._sobs.close()
             self._sobs = None

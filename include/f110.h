@@ -746,6 +746,96 @@ F110_API int f110_scan_obs_reset(f110_scan_obs *so, const uint8_t *env_mask /* N
 /* The device ring and heads (tests); either may be NULL. */
 F110_API int f110_scan_obs_arrays(f110_scan_obs *so, float **ring, int32_t **head);
 
+/* ---- sensor randomization (no reference counterpart: the reference's scan noise is one std for
+ *      every env, and its poses are exact) ---------------------------------------------------------
+ * The third leg of the domain randomization, beside f110_set_param_randomization (the car) and
+ * f110_set_spawn_randomization (the start state): the full observation row turned into the row the
+ * policy, the replay and the critic see, under sensor parameters drawn per env and episode on the
+ * device.  Everything else that reads the observation (the reward, the statistics, the opponents)
+ * keeps the clean row; off unless a caller asks for it.
+ *   row  [B range columns | M middle columns (4 per agent: x, y, theta, collision) | T tail columns],
+ *        float32, unit column stride; the output row has the same width and layout
+ * Each parameter is uniform in its (lo, hi) pair; f110_default_sensor_params is the identity:
+ *   scale       multiplicative range error                                             (1, 1)
+ *   noise_abs   additive range noise sigma, metres                                     (0, 0)
+ *   noise_rel   range-proportional noise sigma, a fraction of the range                (0, 0)
+ *   dropout     per-beam, per-step probability of no return (the beam reads max range) (0, 0)
+ *   blackout    width in whole beams of one contiguous blocked sector (it reads 0); its first beam
+ *               is drawn once per episode, uniform over [0, B - width]                  (0, 0)
+ *   quant       range quantization step, metres; 0 = off                               (0, 0)
+ *   pose_xy     sigma of the noise on every x and y column, metres                     (0, 0)
+ *   pose_theta  sigma of the noise on every theta column, radians                      (0, 0)
+ * Counters, per env on the device: episode (-1 = no apply yet) and step.  An apply of an env with
+ * episode < 0 or a nonzero reset flag starts an episode: episode = (episode + 1) mod 2^31, step = 0
+ * and the parameter row is redrawn; any other apply has step = step + 1 (mod 2^32).
+ * Draws: Philox4x32-10 (csrc/f110_rng.h) under the key of f110_set_param_randomization,
+ *   k0 = (u32)seed ^ (u32)g, k1 = (u32)(seed >> 32) ^ (u32)(g >> 32) ^ 0xA5A5A5A5, g = env_offset + e
+ * (the global env id: nothing depends on n_envs, the launch shape or the sharding over ranks).
+ *   parameter block j < 3: counter (j, 0, 0x5E250, episode); block 0 = scale, noise_abs, noise_rel,
+ *     dropout; block 1 = blackout width, blackout start, quant, pose_xy; block 2 word 0 = pose_theta.
+ *     A real parameter is lo + u * (hi - lo), u = (float)(word >> 8) * 2^-24; the width is
+ *     lo + mulhi(word, hi - lo + 1), the start mulhi(word, B - width + 1), mulhi(w, n) = (w * n) >> 32
+ *     in 64 bits.  noise_abs and quant are then divided by range_max (the row's units), once;
+ *     the dropout threshold is (u32)(dropout * 2^24).
+ *   column block: counter (column, step, 0x5E251, episode), column = b for beam b, B + m for middle
+ *     column m.  z = (float)(S - 1530) * (1/256) with S the sum of the 12 bytes of words 0..2 (mean
+ *     0, std sqrt(65535)/256, |z| < 5.98); the dropout bits are word 3 >> 8.
+ * One beam of value d, all float32, in this order, no contraction:
+ *   1. d = d * scale
+ *   2. if noise_abs_n > 0 or noise_rel > 0:  d = d + z * (noise_abs_n + noise_rel * d)
+ *   3. if quant_n > 0:  d = quant_n * rintf(d / quant_n)
+ *   4. if the beam's 24 dropout bits < the threshold:  d = 1
+ *   5. if start <= b < start + width:  d = 0
+ *   6. d < 0 gives 0, d > 1 gives 1
+ * One pose column of value v: x and y with pose_xy > 0 become v + z * pose_xy; theta with
+ * pose_theta > 0 becomes t = v + z * pose_theta, then t - 2pi if t > pi, t + 2pi if t < -pi (float32
+ * pi and 2pi).  Collision columns, the tail and columns whose sigma is 0 keep their bits; so the
+ * identity parameters return a row of ranges in [0, 1] bit for bit.
+ * An env whose env_mask byte is 0 is copied through unchanged; its counters and parameter row advance
+ * all the same (a trainer's noise-free evaluation envs).
+ * The device and the host statement (f110_host_sensor_apply, f110_debug.h) agree in every bit.
+ * Limits (by design): 1 <= B <= 4096, M a multiple of 4. */
+typedef struct f110_sensor f110_sensor;
+typedef struct f110_sensor_params {  /* (lo, hi) each */
+    float scale[2];
+    float noise_abs[2];
+    float noise_rel[2];
+    float dropout[2];
+    float blackout[2];
+    float quant[2];
+    float pose_xy[2];
+    float pose_theta[2];
+} f110_sensor_params;
+
+F110_API void f110_default_sensor_params(f110_sensor_params *p);
+
+/* The parameter rows [n_envs][10] float32 (scale, noise_abs / range_max, noise_rel, dropout, blackout
+ * width, blackout start, quant / range_max, pose_xy, pose_theta, dropout threshold), zeros, and the
+ * counters [n_envs] int32 (episode -1, step 0) on `device`.  env_mask: HOST u8 [n_envs] copied to the
+ * device, or NULL (every env is touched).  range_max: what the range columns were divided by (the
+ * context's lidar_max).
+ * F110_E_INVALID, the argument named, before any device call: a null out or params, n_envs < 1, n_beams
+ * outside [1, 4096], n_mid not a multiple of 4, n_mid or n_tail negative, range_max not > 0,
+ * env_offset < 0, a bound that is not finite, lo > hi, scale <= 0, a negative sigma or quant, dropout
+ * outside [0, 1], blackout outside [0, n_beams] or not whole. */
+F110_API int f110_sensor_create(f110_sensor **out, int32_t device, int64_t n_envs, int32_t n_beams, int32_t n_mid,
+                                int32_t n_tail, float range_max, uint64_t seed, int64_t env_offset,
+                                const uint8_t *env_mask, const f110_sensor_params *params);
+F110_API int f110_sensor_destroy(f110_sensor *sn);
+/* One apply of every env: rows / out device float32 (row e at rows + e*row_stride, out + e*out_stride),
+ * reset device u8 [n_envs] or NULL (no env resets).  out is rows itself (same pointer and stride) or
+ * shares no float with it.  One launch, one block per env; the counters and the parameter rows are on
+ * the device: no allocation, no host synchronisation, no atomics (capturable); async on stream.
+ * F110_E_INVALID: a null pointer, row_stride or out_stride below B + M + T, out overlapping rows in
+ * part. */
+F110_API int f110_sensor_apply(f110_sensor *sn, const float *rows, int64_t row_stride, const uint8_t *reset,
+                               float *out, int64_t out_stride, void *stream);
+/* Restarts the counters (episode = -1, step = 0) of the envs with env_mask != 0 (device u8): their
+ * next apply starts episode 0 again. */
+F110_API int f110_sensor_reset(f110_sensor *sn, const uint8_t *env_mask /* NULL = all */, void *stream);
+/* The device parameter rows and counters (tests); any may be NULL. */
+F110_API int f110_sensor_arrays(f110_sensor *sn, float **param_rows, int32_t **episode, int32_t **step);
+
 /* ---- prioritized experience replay ---------------------------------------------
  * Replaces rl_training/DDPG/replay_buffer.py:PrioritizedExperienceReplayBuffer
  * (:6-135), the DDPG agent's memory (agent.py:194): a ring of transitions

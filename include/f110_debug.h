@@ -402,6 +402,21 @@ F110_API int f110_host_scan_obs_push(const f110_scan_obs_params *params, int64_t
                                      const uint8_t *reset, float *ring, int32_t *head, float *out,
                                      int64_t out_stride);
 
+/* What f110_sensor_create refuses of the ranges, without a device (F110_E_INVALID with the reason). */
+F110_API int f110_host_check_sensor_params(const f110_sensor_params *params, int32_t n_beams);
+
+/* f110_sensor_apply over HOST arrays: the same row rule (csrc/f110_sensor.h), envs in ascending
+ * order, with the shape, the seed, the mask (host u8 or NULL) and the state passed in: param_rows
+ * [n_envs][10] float32, episode and step [n_envs] int32 (f110_sensor_arrays' layout; episode -1 = no
+ * apply yet), updated in place.  Same validation (F110_E_INVALID) as create and apply, and an
+ * episode below -1 is refused too.  Pure host code: the sanitizer program links it.  Host test hook:
+ * the CPU suite and the GPU tests share one statement of the semantics. */
+F110_API int f110_host_sensor_apply(const f110_sensor_params *params, int64_t n_envs, int32_t n_beams,
+                                    int32_t n_mid, int32_t n_tail, float range_max, uint64_t seed,
+                                    int64_t env_offset, const uint8_t *env_mask, const float *rows,
+                                    int64_t row_stride, const uint8_t *reset, float *param_rows, int32_t *episode,
+                                    int32_t *step, float *out, int64_t out_stride);
+
 #ifdef __cplusplus
 }
 #endif
